@@ -13,11 +13,22 @@ Other BASELINE configurations (secondary lines, same JSON contract):
                (the per-read statistics and the pA array), then event on the raw samples (it scales on the fly)
   --ragged S   (config 2) log-normal read lengths, sigma S, same mean: the mixed-length line
 
-The oracle is used only in the CPU-baseline leg (rank 0, N=1): as the checker of the benched output and as the
-timed baseline.  Prints ONE JSON line on rank 0 (see the driver contract): value = total samples/s over all ranks;
-`roofline` = algorithmic HBM bytes of one step over the HIP-event-measured duration of the path's
-kernels; `cpu_baseline` = the real reference (oracle/_ref/libsigtk_ref.so, kind "reference") or the oracle
-restatement (kind "port") timed single-threaded on a bounded subsample of the same reads on this host.
+Prints ONE JSON line on rank 0 (see the driver contract): value = total samples/s over all ranks, ms_per_step = the
+wall time of one timed step.  A plain run does only that: set up, warm up, time --steps steps, write the outputs
+(--dump-outputs) and print the line.
+
+--full adds the secondary figures, each of which costs time of its own:
+  `roofline`           algorithmic HBM bytes of one step over the duration of the path's kernels, measured
+                       with HIP events recorded around every launch of the timed steps
+  `parity_spot_check`  three reads of the benched output against the oracle, bit for bit
+  `cpu_baseline`       the real reference (oracle/_ref/libsigtk_ref.so, kind "reference") or the oracle restatement
+                       (kind "port") timed single-threaded on a bounded subsample of the same reads on this host
+The oracle is used only there (rank 0, N=1).
+
+--dump-outputs DIR writes what the last timed step computed on rank 0 as DIR/<name>.npy (float32 / float64):
+per-read arrays (event counts, stat / prefix records) for every read, and the complete events / pA of a fixed,
+seeded sample of reads (at most DUMP_SAMPLE_SAMPLES raw samples).  Inputs are seeded: the same arguments give the
+same inputs in every run, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -32,6 +43,10 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0        # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 HBM_ACHIEVABLE_GBS = 6300.0  # what a copy kernel reaches (same guide)
+# --dump-outputs: raw samples of the sampled reads whose events / pA are written whole (an event covers >= 2 samples,
+# so <= 24 MB of events and 8 MB of pA), and the reads the per-read arrays cover (<= 72 bytes each): under 64 MB
+DUMP_SAMPLE_SAMPLES = 2000000
+DUMP_MAX_READS = 250000
 
 CONFIGS = {
     2: dict(name="sigtk event (DNA params)", reads=10000, kind=0, rna=0, seed=1),
@@ -61,7 +76,14 @@ def main():
                     help="(config 2; NOT the contract line) batches in flight: step i runs on stream i %% N with output "
                          "arena i %% N, as the CLI's jobs do -- the next batch's first waves fill the slots the last "
                          "waves of this one leave empty.  The default, 1, is what the driver measures.")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the secondary figures: per-kernel times and roofline, the parity spot check "
+                         "against the oracle and the single-thread CPU baseline (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     cfg = dict(CONFIGS[args.config])
     if args.reads:
         cfg["reads"] = args.reads
@@ -120,26 +142,30 @@ def main():
     step_no = [0]
 
     def step():
+        """enqueue one step; -> the outputs a caller of the path receives from it"""
         if args.config == 2 and inflight > 1:
             k = step_no[0] % inflight
             step_no[0] += 1
             if k == 0:
                 device.event(batch, arena, rna)
-            else:
-                st_k, ar_k = lanes[k - 1]
-                with torch.cuda.stream(st_k):
-                    device.event(batch, ar_k, rna)
-            return
+                return {"arena": arena}
+            st_k, ar_k = lanes[k - 1]
+            with torch.cuda.stream(st_k):
+                device.event(batch, ar_k, rna)
+            return {"arena": ar_k}
         if args.config == 2:
             device.event(batch, arena, rna)
+            return {"arena": arena}
         elif args.config == 3:
             device.event(batch, arena, rna)
-            device.prefix(batch, rna, 0)
+            return {"arena": arena, "prefix": device.prefix(batch, rna, 0)}
         elif args.config == 4:
-            device.stat_pa(batch, pa_out)
+            stat_rec, _ = device.stat_pa(batch, pa_out)
+            return {"stat": stat_rec, "pa": pa_out}
         else:
             # one call (sgk_pipeline): the fused stat + pA pass, then event on the raw samples (it scales on the fly)
             device.pipeline(batch, arena, rna, pa_out, stat_out)
+            return {"arena": arena, "stat": stat_out, "pa": pa_out}
 
     def barrier():
         torch.cuda.synchronize()
@@ -154,16 +180,18 @@ def main():
     st = arena.status() if arena is not None else None
     E = int(st.n_events_total) if st is not None else 0
     parity = None
-    # ---- timed region: exactly K steps
-    L.sgk_profile_reset()
-    L.sgk_profile_enable(1)
+    # ---- timed region: exactly K steps (--full: with HIP events around every kernel launch, for `roofline`)
+    if args.full:
+        L.sgk_profile_reset()
+        L.sgk_profile_enable(1)
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     barrier()
     t1 = time.perf_counter()
-    L.sgk_profile_enable(0)
+    if args.full:
+        L.sgk_profile_enable(0)
     elapsed = t1 - t0
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
@@ -175,12 +203,45 @@ def main():
         t = torch.tensor([S_all, R_all], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         S_all, R_all = float(t[0].item()), float(t[1].item())
-    prof = api.profile_read()
-    L.sgk_profile_reset()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, batch, last)
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = S_all / (elapsed / args.steps)
+        out = {
+            "metric": "event_raw_samples_per_sec" if args.config in (2, 3) else "raw_samples_per_sec",
+            "value": round(value, 1),
+            "unit": "samples/s",
+            "reads_per_sec": round(R_all / (elapsed / args.steps), 1),
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 4),
+            "higher_is_better": True,
+            "scaling": args.scaling,
+            "vs_baseline": None,
+            "dtype": "f32+f64",
+            "data": "synthetic",
+            "config": {"workload": "%s on %d synthetic reads x %s samples per GPU (BASELINE configs[%d]), "
+                                   "device-resident" % (cfg["name"], R,
+                                                        ("log-normal(sigma %.2f, mean %d)" % (args.ragged, args.read_len))
+                                                        if args.ragged else str(args.read_len), args.config - 1),
+                       "reads_per_gpu": R, "samples_per_read": args.read_len, "samples_per_gpu": int(S),
+                       "events_per_step_rank0": E,
+                       "fallback_reads": int(st.n_fallback_reads) if st is not None else None,
+                       "rerun_chunks": int(st.n_rerun_passes) if st is not None else None,
+                       "long_detector_replays": int(st.n_long_replays) if st is not None else None,
+                       "long_detector_replay_indices": int(st.n_replay_indices) if st is not None else None,
+                       "split_reads": int(st.n_split_reads) if st is not None else None,
+                       "batches_in_flight": inflight,
+                       "parallelism": "reads sharded across ranks, no collective"},
+        }
+    if args.full:
+        prof = api.profile_read()
+        L.sgk_profile_reset()
+
+    if rank == 0 and args.full:
         # per-step device time of each kernel (HIP events on the stream it was launched on, summed over its launches
         # in a step); "path:*" entries bracket a whole subtool (first launch -> last kernel done)
         kern = {k: v[0] / args.steps for k, v in prof.items() if not k.startswith("path:")}
@@ -227,43 +288,63 @@ def main():
         cpu = None
         cpu_reads = args.cpu_reads if args.cpu_reads >= 0 else (2000 if args.config in (2, 3) else 300)
         if cpu_reads > 0 and world == 1:
-            cpu, parity = cpu_leg(args, cfg, batch, arena, cpu_reads, rna)
+            cpu, parity = cpu_leg(args, cfg, batch, last.get("arena"), cpu_reads, rna)
+        out.update({"parity_spot_check": parity, "roofline": roofline, "cpu_baseline": cpu})
 
-        out = {
-            "metric": "event_raw_samples_per_sec" if args.config in (2, 3) else "raw_samples_per_sec",
-            "value": round(value, 1),
-            "unit": "samples/s",
-            "reads_per_sec": round(R_all / (elapsed / args.steps), 1),
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": args.scaling,
-            "vs_baseline": None,
-            "dtype": "f32+f64",
-            "data": "synthetic",
-            "config": {"workload": "%s on %d synthetic reads x %s samples per GPU (BASELINE configs[%d]), "
-                                   "device-resident" % (cfg["name"], R,
-                                                        ("log-normal(sigma %.2f, mean %d)" % (args.ragged, args.read_len))
-                                                        if args.ragged else str(args.read_len), args.config - 1),
-                       "reads_per_gpu": R, "samples_per_read": args.read_len, "samples_per_gpu": int(S),
-                       "events_per_step_rank0": E,
-                       "fallback_reads": int(st.n_fallback_reads) if st is not None else None,
-                       "rerun_chunks": int(st.n_rerun_passes) if st is not None else None,
-                       "long_detector_replays": int(st.n_long_replays) if st is not None else None,
-                       "long_detector_replay_indices": int(st.n_replay_indices) if st is not None else None,
-                       "split_reads": int(st.n_split_reads) if st is not None else None,
-                       "batches_in_flight": inflight,
-                       "parallelism": "reads sharded across ranks, no collective"},
-            "parity_spot_check": parity,
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-        }
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, batch, outs):
+    """What one step computed, as float32 / float64 .npy files under `out_dir` (rank 0's batch).
+    n_events / stat_* / prefix_*: one entry per read (all reads, or the first DUMP_MAX_READS of a seeded permutation,
+    in read order: `per_read_reads`); event_* / pa: the complete output of the reads listed in `sample_reads` (a seeded
+    choice of reads, taken by their lengths alone), concatenated in read order."""
+    import torch
+    from sigtk_amd import api
+    os.makedirs(out_dir, exist_ok=True)
+    n = batch.n_reads
+    lens = batch.lengths_host.astype(np.int64)
+    order = np.random.RandomState(20261016).permutation(n)
+    per_read = np.sort(order[:DUMP_MAX_READS])
+    fits = np.cumsum(lens[order]) <= DUMP_SAMPLE_SAMPLES
+    sample = np.sort(order[:int(np.argmin(fits)) if not fits.all() else n])
+    arrays = {"per_read_reads": per_read.astype(np.float64), "sample_reads": sample.astype(np.float64)}
+    dev = batch.samples.device
+
+    def ranges(starts, counts):
+        """device index tensor of the concatenated ranges [starts[i], starts[i] + counts[i])"""
+        counts = counts.astype(np.int64)
+        idx = np.repeat(starts.astype(np.int64) - np.cumsum(counts) + counts, counts) + np.arange(int(counts.sum()))
+        return torch.from_numpy(idx).to(dev)
+
+    def records(rec_bytes, dtype, prefix):
+        rec = rec_bytes.cpu().numpy().view(dtype)[:n][per_read]
+        for f in dtype.names:
+            if f != "reserved":
+                arrays[prefix + f] = rec[f] if rec[f].dtype == np.float32 else rec[f].astype(np.float64)
+
+    arena = outs.get("arena")
+    if arena is not None:
+        n_ev = arena.n_events[:n].cpu().numpy().astype(np.int64)
+        arrays["n_events"] = n_ev[per_read].astype(np.float64)
+        rec = arena.events[ranges(arena.slots_host[sample], n_ev[sample])].cpu().numpy()
+        arrays["event_start"] = rec[:, 0].view(np.uint32).astype(np.float64)
+        arrays["event_length"] = rec[:, 1].view(np.uint32).astype(np.float64)
+        arrays["event_mean"] = rec[:, 2].view(np.float32).copy()
+        arrays["event_stdv"] = rec[:, 3].view(np.float32).copy()
+    if "stat" in outs:
+        records(outs["stat"], api.STAT_DTYPE, "stat_")
+    if "prefix" in outs:
+        records(outs["prefix"], api.PREFIX_DTYPE, "prefix_")
+    if "pa" in outs:
+        arrays["pa"] = outs["pa"][ranges(batch.offsets_host[sample], lens[sample])].cpu().numpy()
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_leg(args, cfg, batch, arena, nb, rna):

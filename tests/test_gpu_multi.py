@@ -48,7 +48,7 @@ def test_bench_two_ranks_rccl(gpu):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", _free_port(), os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--steps", "3", "--warmup", "1", "--reads", "2000", "--cpu-reads", "0"],
+                        "--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--reads", "2000", "--cpu-reads", "0"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -64,7 +64,7 @@ def test_bench_two_ranks_share_one_gpu_gloo(gpu):
     barrier, MAX over the step time, SUM of the units, strong-scaling partition -- on a 1-GPU box."""
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", _free_port(), os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--steps", "2", "--warmup", "1", "--reads", "1000", "--cpu-reads", "0",
+                        "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--reads", "1000", "--cpu-reads", "0",
                         "--backend", "gloo", "--scaling", "strong", "--ragged", "0.8"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]

@@ -1,17 +1,42 @@
-"""CPU: the oracle restatement against the REAL reference (oracle/_ref/libsigtk_ref.so, compiled
-from /root/reference by oracle/Makefile), function by function on seeded inputs.  Skipped when the
-reference library has not been built."""
+"""CPU: the oracle restatement against the REAL reference, function by function on seeded inputs.
+
+What the reference (oracle/_ref/libsigtk_ref.so, compiled from its sources by oracle/Makefile) returns on these
+inputs is stored in tests/golden/ref_vectors.json: every array as the SHA-256 of its bytes, scalars as they are
+(float32 as their bit patterns).  The oracle is checked against that file always; when the reference library has
+been built, the reference is checked against it too, so the file stays pinned to the reference.
+
+    python tests/test_oracle_vs_ref.py     (with oracle/_ref built: rewrites tests/golden/ref_vectors.json)
+"""
+import hashlib
+import json
+import os
+import sys
+
 import numpy as np
 import pytest
 
-from sigtk_amd import api
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from sigtk_amd import api  # noqa: E402
+
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+VECTORS = os.path.join(GOLDEN, "ref_vectors.json")
+SOAK_FIXTURES = ("soak_seed2024_b6003_r1407.npz", "soak_wvl_seed5_b431_r1525.npz", "soak_wvl_seed5_b797_r3354.npz")
 
 
-@pytest.fixture(scope="module")
-def ref(reflib):
-    if reflib is None:
-        pytest.skip("oracle/_ref/libsigtk_ref.so not built (needs /root/reference)")
-    return reflib
+def _h(a, dtype):
+    return hashlib.sha256(np.ascontiguousarray(a, dtype=dtype).tobytes()).hexdigest()
+
+
+def _bits(x):
+    return int(np.float32(x).view(np.uint32))
+
+
+def _stat(s):
+    """raw_median as an int, the five float32 statistics as their bits"""
+    return [int(s[4])] + [_bits(s[k]) for k in (0, 1, 2, 3, 5)]
 
 
 def _random_reads(seed):
@@ -26,55 +51,89 @@ def _random_reads(seed):
     return reads, dig, off, rng
 
 
-@pytest.mark.parametrize("seed", [1, 2, 3])
-def test_pa_event_stat_bitwise(oracle, ref, seed):
+def observe_pa_event_stat(lib, seed):
+    """pa and stat bit for bit, event (both presets): starts and lengths by value, mean / stdv bit for bit"""
     reads, dig, off, rng = _random_reads(seed)
+    out = {}
     for r, raw in enumerate(reads):
-        assert np.array_equal(oracle.pa(raw, dig[r], off[r], rng[r]).view(np.uint32),
-                              ref.pa(raw, dig[r], off[r], rng[r]).view(np.uint32))
+        out["%d.pa" % r] = _h(lib.pa(raw, dig[r], off[r], rng[r]), np.float32)
         for rna in (0, 1):
-            a = oracle.event_raw(raw, dig[r], off[r], rng[r], rna)
-            b = ref.event_raw(raw, dig[r], off[r], rng[r], rna)
-            assert np.array_equal(a.start, b.start) and np.array_equal(a.length, b.length)
-            assert np.array_equal(a.mean.view(np.uint32), b.mean.view(np.uint32))
-            assert np.array_equal(a.stdv.view(np.uint32), b.stdv.view(np.uint32))
-        sa = oracle.stat(raw, dig[r], off[r], rng[r])
-        sb = ref.stat(raw, dig[r], off[r], rng[r])
-        assert sa[4] == sb[4]
-        for k in (0, 1, 2, 3, 5):
-            assert np.float32(sa[k]).view(np.uint32) == np.float32(sb[k]).view(np.uint32)
+            e = lib.event_raw(raw, dig[r], off[r], rng[r], rna)
+            out["%d.event%d" % (r, rna)] = [_h(e.start, np.uint64), _h(e.length, np.float32),
+                                            _h(e.mean, np.float32), _h(e.stdv, np.float32)]
+        out["%d.stat" % r] = _stat(lib.stat(raw, dig[r], off[r], rng[r]))
+    return out
 
 
-@pytest.mark.parametrize("seed", [4, 5])
-def test_jnn_adaptor_polya(oracle, ref, seed):
+def observe_jnn_adaptor_polya(lib, seed):
     reads, dig, off, rng = api.synth_reads_host(5, [1500, 2500, 30000, 100000, 100000], seed, 1)
+    out = {}
     for r, raw in enumerate(reads):
         for rna in (0, 1):
-            ax, ay = oracle.jnn_raw(raw, rna)
-            bx, by = ref.jnn_raw(raw, rna)
-            assert np.array_equal(ax, bx) and np.array_equal(ay, by)
+            x, y = lib.jnn_raw(raw, rna)
+            out["%d.jnn%d" % (r, rna)] = [_h(x, np.int64), _h(y, np.int64)]
         for pore in (0, 2):
-            assert oracle.find_adaptor(raw, pore) == ref.find_adaptor(raw, pore)
-        pa = oracle.pa(raw, dig[r], off[r], rng[r])
+            out["%d.adaptor%d" % (r, pore)] = list(lib.find_adaptor(raw, pore))
+        pa = lib.pa(raw, dig[r], off[r], rng[r])
         for top, bot in ((120.0, 80.0), (110.5, 90.25)):
-            assert oracle.find_polya(pa, top, bot, 0) == ref.find_polya(pa, top, bot, 0)
+            out["%d.polya_%g_%g" % (r, top, bot)] = list(lib.find_polya(pa, top, bot, 0))
+    return out
 
 
-def test_soak_regression_fixtures_are_pinned(oracle, ref):
-    """the reads the round-2 soaks found GPU bugs on (tests/golden/soak_*.npz): what the GPU tests compare against --
-    the oracle -- equals the real reference on them (event, stat and jnn)."""
-    import os
-    gold = os.path.join(os.path.dirname(__file__), "golden")
-    for name in ("soak_seed2024_b6003_r1407.npz", "soak_wvl_seed5_b431_r1525.npz", "soak_wvl_seed5_b797_r3354.npz"):
-        z = np.load(os.path.join(gold, name))
+def observe_soak_fixtures(lib):
+    """event (starts and means), jnn and stat on the reads the soaks found GPU bugs on (tests/golden/soak_*.npz)"""
+    out = {}
+    for name in SOAK_FIXTURES:
+        z = np.load(os.path.join(GOLDEN, name))
         raw = z["samples"].astype(np.int16)
         dig, off, rng = float(np.ravel(z["dig"])[0]), float(np.ravel(z["off"])[0]), float(np.ravel(z["rng"])[0])
         for rna in (0, 1):
-            a = oracle.event_raw(raw, dig, off, rng, rna)
-            b = ref.event_raw(raw, dig, off, rng, rna)
-            assert np.array_equal(a.start, b.start) and np.array_equal(a.mean.view(np.uint32), b.mean.view(np.uint32))
-            ax, ay = oracle.jnn_raw(raw, rna)
-            bx, by = ref.jnn_raw(raw, rna)
-            assert np.array_equal(ax, bx) and np.array_equal(ay, by)
-        sa, sb = oracle.stat(raw, dig, off, rng), ref.stat(raw, dig, off, rng)
-        assert sa[4] == sb[4] and all(np.float32(sa[k]).view(np.uint32) == np.float32(sb[k]).view(np.uint32) for k in (0, 1, 2, 3, 5))
+            e = lib.event_raw(raw, dig, off, rng, rna)
+            out["%s.event%d" % (name, rna)] = [_h(e.start, np.uint64), _h(e.mean, np.float32)]
+            x, y = lib.jnn_raw(raw, rna)
+            out["%s.jnn%d" % (name, rna)] = [_h(x, np.int64), _h(y, np.int64)]
+        out[name + ".stat"] = _stat(lib.stat(raw, dig, off, rng))
+    return out
+
+
+OBSERVATIONS = {"pa_event_stat_seed%d" % s: (observe_pa_event_stat, (s,)) for s in (1, 2, 3)}
+OBSERVATIONS.update({"jnn_adaptor_polya_seed%d" % s: (observe_jnn_adaptor_polya, (s,)) for s in (4, 5)})
+OBSERVATIONS["soak_fixtures"] = (observe_soak_fixtures, ())
+
+
+def _check(name, oracle, reflib):
+    fn, args = OBSERVATIONS[name]
+    want = json.load(open(VECTORS))[name]
+    libs = [("oracle", oracle)] + ([("reference", reflib)] if reflib is not None else [])
+    for who, lib in libs:
+        got = fn(lib, *args)
+        assert sorted(got) == sorted(want), (who, name)
+        for k in want:
+            assert got[k] == want[k], "%s differs from the stored reference output at %s / %s" % (who, name, k)
+
+
+@pytest.mark.parametrize("seed", [1, 2, 3])
+def test_pa_event_stat_bitwise(oracle, reflib, seed):
+    _check("pa_event_stat_seed%d" % seed, oracle, reflib)
+
+
+@pytest.mark.parametrize("seed", [4, 5])
+def test_jnn_adaptor_polya(oracle, reflib, seed):
+    _check("jnn_adaptor_polya_seed%d" % seed, oracle, reflib)
+
+
+def test_soak_regression_fixtures_are_pinned(oracle, reflib):
+    """the reads the round-2 soaks found GPU bugs on (tests/golden/soak_*.npz): what the GPU tests compare against --
+    the oracle -- equals the real reference on them (event, stat and jnn)."""
+    _check("soak_fixtures", oracle, reflib)
+
+
+if __name__ == "__main__":
+    from oracle.oracle import RefLib
+    if not RefLib.available():
+        raise SystemExit("build the reference first: make -C oracle ref")
+    ref = RefLib()
+    vectors = {name: fn(ref, *args) for name, (fn, args) in OBSERVATIONS.items()}
+    with open(VECTORS, "w") as fh:
+        json.dump(vectors, fh, indent=1, sort_keys=True)
+    print("wrote %s (%d groups)" % (VECTORS, len(vectors)))

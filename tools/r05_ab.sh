@@ -12,7 +12,7 @@ show() { python3 -c "import json,sys; d=json.loads(open('$1').read()); print('$2
 export SIGTK_AMD_LIB=$PWD/sigtk_amd/_variants/libsigtk_gpu_dev.so
 for t in -1 0; do python tools/event_phases.py --steps 5 --tail $t --prio 0,1,0,1 > $O/tail_$t.json 2>$O/err.txt; show $O/tail_$t.json "tail $t"; done
 python tools/event_phases.py --steps 5 --rna 1 --prio 0,1,0,1 > $O/rna.json 2>>$O/err.txt; show $O/rna.json rna
-bench() { python bench.py --cpu-reads 0 --steps 30 --warmup 10 "$@" 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['roofline']['kernels_ms'])"; }
+bench() { python bench.py --full --cpu-reads 0 --steps 30 --warmup 10 "$@" 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['roofline']['kernels_ms'])"; }
 export SIGTK_AMD_LIB=$PWD/sigtk_amd/_variants/libsigtk_gpu_r04.so SIGTK_AMD_LIB_ANY=1
 for t in 1 0; do echo -n "r04 tail $t: "; SGK_EVENT_TAIL=$t bench; done
 echo -n "r04 rna: "; bench --rna 1

@@ -14,5 +14,5 @@ unset SIGTK_AMD_LIB
 for a in "--ragged 0.8" "--ragged 0.8 --rna 1" "--read-len 5000 --reads 200000" "--read-len 5000 --reads 200000 --rna 1"; do
 for lib in r04 base; do
 if [ $lib = base ]; then unset SIGTK_AMD_LIB SIGTK_AMD_LIB_ANY; else export SIGTK_AMD_LIB=$PWD/sigtk_amd/_variants/libsigtk_gpu_$lib.so SIGTK_AMD_LIB_ANY=1; fi
-python bench.py --cpu-reads 0 --steps 20 --warmup 5 $a 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$lib', '$a', d['ms_per_step'], d['roofline']['kernels_ms'])"
+python bench.py --full --cpu-reads 0 --steps 20 --warmup 5 $a 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$lib', '$a', d['ms_per_step'], d['roofline']['kernels_ms'])"
 done; done
