@@ -65,11 +65,7 @@ __global__ __launch_bounds__(256) void k_ent(sgk_batch_t b, sgk_ent_hist_t *out,
 
 int launch_ent(const sgk_batch_t *b, sgk_ent_hist_t *out, uint16_t *over_raw, uint16_t *over_delta, hipStream_t st) {
     if (b->n_reads == 0) return SGK_OK;
-    {
-        ProfScope ps("k_ent", st);
-        hipLaunchKernelGGL(k_ent, dim3(b->n_reads), dim3(256), 0, st, *b, out, over_raw, over_delta);
-    }
-    SGK_HIP_TRY(hipGetLastError());
+    SGK_LAUNCH("k_ent", k_ent, b->n_reads, 256, st, *b, out, over_raw, over_delta);
     return SGK_OK;
 }
 

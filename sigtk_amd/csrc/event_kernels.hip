@@ -38,8 +38,6 @@
 // for x and for the float squares, and that every non-zero |x| lies in [2^-20, 2^20] (the range in which the
 // certified fast arithmetic of tstat_math.h has no subnormal intermediate); reads failing the check take the
 // fallback kernel.
-#include <atomic>
-#include <mutex>
 #include <type_traits>
 #include <utility>
 
@@ -2293,70 +2291,18 @@ __global__ __launch_bounds__(64) void k_event_fallback(EvArgs a) {
 
 // ---------------------------------------------------------------- launcher
 
-// Side streams.  A batch with short AND longer reads runs two detector kernels: k_event (a wavefront per read, and the
-// segments of the long reads) and k_event_multi (several short reads per wavefront).  In one stream the second would
-// wait for the last wave of the first -- two tails instead of one, which costs what the packing gains (50 000 RNA-like
-// reads, log-normal around 20 000 samples: 6.36 ms against 6.29 ms with a wavefront per read).  k_event_multi therefore
-// goes to a side stream of the library's own, forked off the caller's stream behind the dispatch order and joined in
-// front of the fallback kernel; the long reads' seam / builder kernels overlap with it as well.
-// (Tried for the tail split's segments: a stream of the LOWEST priority, so that they would be dispatched into the slots
-// k_event's last waves leave empty -- 5.1 vs 3.8 ms on config 2: its kernels start late and slowly.)
-// A small pool per device and kind, handed out round-robin; a stream's mutex is held while one launch enqueues its
-// fork .. join on it (the events are the stream's), never across launches of other streams or devices.
-constexpr int SIDE_POOL = 4;
-static SideStream g_side[64][3][SIDE_POOL];
-static std::atomic<unsigned> g_side_next[64][3];
-static SideStream *side_acquire_slot(int dev, int kind, int slot, int priority);
-// returns a locked side stream (unlock with x->mu.unlock()), or null
-SideStream *side_acquire(int priority) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-    const int kind = priority < 0 ? 1 : (priority > 0 ? 2 : 0);
-    // the whole pool of this device and kind is made by the first call that needs one (stream creation takes
-    // milliseconds: made one by one, the first SIDE_POOL launches each paid for one -- a two-step warm-up was not enough)
-    static std::atomic<bool> g_side_made[64][3];
-    if (!g_side_made[dev][kind].exchange(true))
-        for (int k = 1; k < SIDE_POOL; ++k) {
-            SideStream *y = side_acquire_slot(dev, kind, k, priority);
-            if (y) y->mu.unlock();
-        }
-    return side_acquire_slot(dev, kind, (int)(g_side_next[dev][kind].fetch_add(1u) % SIDE_POOL), priority);
-}
-static SideStream *side_acquire_slot(int dev, int kind, int slot, int priority) {
-    SideStream &x = g_side[dev][kind][slot];
-    x.mu.lock();
-    if (!x.s && !x.tried) {
-        x.tried = true;
-        hipStream_t s = nullptr;
-        hipEvent_t f = nullptr, j = nullptr;
-        int lo = 0, hi = 0;
-        hipError_t e;
-        if (priority != 0 && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi)
-            e = hipStreamCreateWithPriority(&s, hipStreamNonBlocking, priority < 0 ? lo : hi);   // (lo: the numerically greatest = lowest)
-        else
-            e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-        if (e == hipSuccess) {
-            if (hipEventCreateWithFlags(&f, hipEventDisableTiming) == hipSuccess &&
-                hipEventCreateWithFlags(&j, hipEventDisableTiming) == hipSuccess) {
-                x.s = s; x.fork = f; x.join = j;
-            } else {
-                if (f) (void)hipEventDestroy(f);
-                (void)hipStreamDestroy(s);
-            }
-        }
-    }
-    if (!x.s) {
-        x.mu.unlock();
-        return nullptr;
-    }
-    return &x;
-}
-template <typename T>
-static int launch_event_t(const EvArgs &a, int rna, uint32_t n_fb_blocks, hipStream_t st) {
+// Side streams (side_stream.h).  A batch with short AND longer reads runs two detector kernels: k_event (a wavefront per
+// read, and the segments of the long reads) and k_event_multi (several short reads per wavefront).  In one stream the
+// second would wait for the last wave of the first -- two tails instead of one, which costs what the packing gains
+// (50 000 RNA-like reads, log-normal around 20 000 samples: 6.36 ms against 6.29 ms with a wavefront per read).
+// k_event_multi therefore goes to a side stream of the library's own, forked off the caller's stream behind the dispatch
+// order and joined in front of the fallback kernel; the long reads' seam / builder kernels overlap with it as well.
+// (Tried in round 1: cutting the batch into read slices and running the builder of slice s on a side stream under the
+// detector of slice s+1.  Both kernels contend for VALU issue and the detector needs >= 3072 reads in flight to fill its
+// 12 waves/CU, so the overlapped step was 8.8 ms against 7.8 ms.)
+template <int W1, typename T>
+static int launch_event_t(const EvArgs &a, uint32_t n_fb_blocks, hipStream_t st) {
     if (a.n_reads == 0) return SGK_OK;
-    // (Tried in round 1: cutting the batch into read slices and running the builder of slice s on a side
-    // stream under the detector of slice s+1.  Both kernels contend for VALU issue and the detector needs
-    // >= 3072 reads in flight to fill its 12 waves/CU, so the overlapped step was 8.8 ms against 7.8 ms.)
     ProfScope whole("path:event", st);
     SGK_HIP_TRY(hipMemsetAsync(a.hdr, 0, sizeof(EvHeader), st));
     EvArgs ao = a;
@@ -2364,60 +2310,39 @@ static int launch_event_t(const EvArgs &a, int rna, uint32_t n_fb_blocks, hipStr
         const int rc = launch_order(a.lengths, a.n_reads, a.order, a.order + a.n_reads, st);
         if (rc != SGK_OK) return rc;
     } else ao.order = nullptr;
-    if (ao.max_segs) hipLaunchKernelGGL(k_seg_plan, dim3((a.n_reads + 255) / 256), dim3(256), 0, st, ao);
+    if (ao.max_segs) SGK_LAUNCH_UNTIMED(k_seg_plan, (a.n_reads + 255) / 256, 256, st, ao);
     // The segments' kernel.  Long reads' segments start FIRST: they stay on the caller's stream and k_event goes to a
     // side stream whose start waits for the fork event (the other way round k_event's workgroups -- ten thousand of them
     // -- take every slot and the chains start late: a ragged batch took 3.81 ms instead of 3.65; stat's long reads taught
     // the same, stat_kernels.hip launch_beside_long).  The tail split's segments go LAST, behind k_event on the caller's
-    // stream: small units for the slots the last whole reads leave empty.
+    // stream: small units for the slots the last whole reads leave empty.  (Tried for them: a stream of the LOWEST
+    // priority, to be dispatched into the slots k_event's last waves leave empty -- 5.1 vs 3.8 ms on config 2.)
     const bool tail_only = ao.max_segs && ao.split_seg && !ao.has_long;
-    auto launch_segs = [&](hipStream_t s_) {
-        ProfScope ps("k_event_seg", s_);
-        if (rna) hipLaunchKernelGGL((k_event_seg<7, T>), dim3(ao.max_segs), dim3(64), 0, s_, ao);
-        else hipLaunchKernelGGL((k_event_seg<3, T>), dim3(ao.max_segs), dim3(64), 0, s_, ao);
-    };
     // (no dispatch order and packing on: every read is under multi_max.  k_event would have nothing to do -- unless
     // the segments are test-sized and some of those reads are long: their segments are k_event_seg's)
     const bool all_short = ao.multi_lanes && !ao.order && !ao.max_segs;
-    SideFork multi_side, whole_side;
-    hipStream_t st_multi = st, st_whole = st;
-    if (ao.multi_lanes && !all_short && multi_side.open(0, st)) st_multi = multi_side.stream();
-    if (ao.max_segs && !tail_only && !all_short && whole_side.open(0, st)) st_whole = whole_side.stream();
-    if (ao.max_segs && !tail_only) {
-        launch_segs(st);
-        SGK_HIP_TRY(hipGetLastError());
-    }
+    const bool side_multi = ao.multi_lanes && !all_short, side_whole = ao.max_segs && !tail_only && !all_short;
+    SideFork side;
+    side.open(st, (int)side_multi + (int)side_whole);
+    const hipStream_t st_multi = side_multi ? side.stream(0) : st;
+    const hipStream_t st_whole = side_whole ? side.stream(side_multi ? 1 : 0) : st;
+    if (ao.max_segs && !tail_only) SGK_LAUNCH("k_event_seg", (k_event_seg<W1, T>), ao.max_segs, 64, st, ao);
     if (ao.multi_lanes) {
-        ProfScope ps("k_event_multi", st_multi);
         const uint32_t per_wave = 64u / ao.multi_lanes;
-        const uint32_t grid = (a.n_reads + per_wave - 1) / per_wave;
-        if (rna) hipLaunchKernelGGL((k_event_multi<7, T>), dim3(grid), dim3(64), 0, st_multi, ao);
-        else hipLaunchKernelGGL((k_event_multi<3, T>), dim3(grid), dim3(64), 0, st_multi, ao);
-        SGK_HIP_TRY(hipGetLastError());
+        SGK_LAUNCH("k_event_multi", (k_event_multi<W1, T>), (a.n_reads + per_wave - 1) / per_wave, 64, st_multi, ao);
     }
-    if (!all_short) {
-        ProfScope ps("k_event", st_whole);
-        if (rna) hipLaunchKernelGGL((k_event<7, T>), dim3(a.n_reads), dim3(64), 0, st_whole, ao);
-        else hipLaunchKernelGGL((k_event<3, T>), dim3(a.n_reads), dim3(64), 0, st_whole, ao);
-    }
-    SGK_HIP_TRY(hipGetLastError());
-    if (tail_only) launch_segs(st);
-    SGK_HIP_TRY(hipGetLastError());
+    if (!all_short) SGK_LAUNCH("k_event", (k_event<W1, T>), a.n_reads, 64, st_whole, ao);
+    if (tail_only) SGK_LAUNCH("k_event_seg", (k_event_seg<W1, T>), ao.max_segs, 64, st, ao);
     // join: the fallback kernel (and whatever the caller enqueues next) waits for the side streams as well
-    multi_side.join();
-    whole_side.join();
-    {
-        ProfScope ps("k_event_fallback", st);
-        if (rna) hipLaunchKernelGGL((k_event_fallback<7, T>), dim3(n_fb_blocks), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((k_event_fallback<3, T>), dim3(n_fb_blocks), dim3(64), 0, st, a);
-    }
-    SGK_HIP_TRY(hipGetLastError());
+    side.join();
+    SGK_LAUNCH("k_event_fallback", (k_event_fallback<W1, T>), n_fb_blocks, 64, st, a);
     return SGK_OK;
 }
 
 int launch_event(const EvArgs &a, int rna, bool float_input, uint32_t n_fb_blocks, hipStream_t st) {
-    return float_input ? launch_event_t<float>(a, rna, n_fb_blocks, st)
-                       : launch_event_t<int16_t>(a, rna, n_fb_blocks, st);
+    if (rna)
+        return float_input ? launch_event_t<7, float>(a, n_fb_blocks, st) : launch_event_t<7, int16_t>(a, n_fb_blocks, st);
+    return float_input ? launch_event_t<3, float>(a, n_fb_blocks, st) : launch_event_t<3, int16_t>(a, n_fb_blocks, st);
 }
 
 }  // namespace sgk

@@ -599,9 +599,7 @@ __global__ __launch_bounds__(64) void k_inflate(InfArgs a) {
 
 int launch_inflate(const InfArgs &a, hipStream_t st) {
     if (a.n == 0) return SGK_OK;
-    ProfScope ps("k_inflate", st);
-    hipLaunchKernelGGL(k_inflate, dim3(a.n), dim3(64), 0, st, a);
-    SGK_HIP_TRY(hipGetLastError());
+    SGK_LAUNCH("k_inflate", k_inflate, a.n, 64, st, a);
     return SGK_OK;
 }
 

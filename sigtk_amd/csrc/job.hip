@@ -468,9 +468,8 @@ int sgk_job_submit(sgk_job_t *j, int tool, int rna, int pore, int flags) {
             // device and download only that (sgk_job_wait fetches the arrays once the total is known)
             const int ncopy = (ev && (flags & SGK_JOB_EVENTS_LENGTHS)) ? 1 : ((ev && (flags & SGK_JOB_EVENTS_COMPACT)) ? 2 : narr);
             if ((rc = j->d_doffs.ensure((nr + 1) * 8)) != SGK_OK) return rc;
-            hipLaunchKernelGGL(k_layout, dim3(1), dim3(1024), 0, st, j->d_cnt.as<uint32_t>(), j->d_slots.as<uint64_t>(),
-                               j->n_reads, 1u, j->d_doffs.as<uint64_t>());
-            SGK_HIP_TRY(hipGetLastError());
+            SGK_LAUNCH_UNTIMED(k_layout, 1, 1024, st, j->d_cnt.as<uint32_t>(), j->d_slots.as<uint64_t>(), j->n_reads, 1u,
+                               j->d_doffs.as<uint64_t>());
             GatherArgs g;
             for (int k = 0; k < 4; ++k) { g.src[k] = nullptr; g.dst[k] = nullptr; }
             for (int k = 0; k < ncopy; ++k) {
@@ -479,12 +478,11 @@ int sgk_job_submit(sgk_job_t *j, int tool, int rna, int pore, int flags) {
                 g.dst[k] = j->d_dense[k].as<uint32_t>();
             }
             if (ev)
-                hipLaunchKernelGGL(k_gather_events, dim3(j->n_reads), dim3(256), 0, st, j->d_out[0].as<sgk_event_rec_t>(),
-                                   g, ncopy, j->d_slots.as<uint64_t>(), j->d_cnt.as<uint32_t>(), j->d_doffs.as<uint64_t>());
+                SGK_LAUNCH_UNTIMED(k_gather_events, j->n_reads, 256, st, j->d_out[0].as<sgk_event_rec_t>(), g, ncopy,
+                                   j->d_slots.as<uint64_t>(), j->d_cnt.as<uint32_t>(), j->d_doffs.as<uint64_t>());
             else
-                hipLaunchKernelGGL(k_gather, dim3(j->n_reads), dim3(256), 0, st, g, ncopy, j->d_slots.as<uint64_t>(),
+                SGK_LAUNCH_UNTIMED(k_gather, j->n_reads, 256, st, g, ncopy, j->d_slots.as<uint64_t>(),
                                    j->d_cnt.as<uint32_t>(), j->d_doffs.as<uint64_t>());
-            SGK_HIP_TRY(hipGetLastError());
             if ((rc = d2h(j->h_doffs, j->d_doffs, (nr + 1) * 8, st)) != SGK_OK) return rc;
             if (!ev) {  // sgk_jnn counts the reads whose segments overflowed their slots in the workspace's first word
                 if ((rc = j->h_err.ensure(64)) != SGK_OK) return rc;
@@ -557,9 +555,8 @@ int sgk_job_submit_qts(sgk_job_t *j, int bits, int method, int out_fmt) {
         if ((rc = j->d_out[1].ensure((nr + 1) * 8)) != SGK_OK) return rc;
         if ((rc = j->d_cnt.ensure(nr * 4)) != SGK_OK) return rc;
         if ((rc = sgk_svbzd_size(smp, view.offsets, view.lengths, j->n_reads, j->d_cnt.as<uint32_t>(), st)) != SGK_OK) return rc;
-        hipLaunchKernelGGL(k_layout, dim3(1), dim3(1024), 0, st, j->d_cnt.as<uint32_t>(),
-                           static_cast<const uint64_t *>(nullptr), j->n_reads, 8u, j->d_out[1].as<uint64_t>());
-        SGK_HIP_TRY(hipGetLastError());
+        SGK_LAUNCH_UNTIMED(k_layout, 1, 1024, st, j->d_cnt.as<uint32_t>(), static_cast<const uint64_t *>(nullptr),
+                           j->n_reads, 8u, j->d_out[1].as<uint64_t>());
         rc = sgk_svbzd_encode(smp, view.offsets, view.lengths, j->n_reads, j->d_out[0].as<uint8_t>(),
                               j->d_out[1].as<uint64_t>(), j->d_cnt.as<uint32_t>(), st);
         if (rc != SGK_OK) return rc;

@@ -84,12 +84,8 @@ int launch_pa(const sgk_batch_t *b, float *out, hipStream_t st) {
     const uint32_t spr = (uint32_t)(want < most ? want : most);
     const uint64_t blocks = (uint64_t)b->n_reads * spr;
     const uint32_t grid = blocks < SLAB_GRID_MAX ? (uint32_t)blocks : SLAB_GRID_MAX;
-    {
-        ProfScope ps("k_pa", st);
-        hipLaunchKernelGGL(k_pa, dim3(grid), dim3(256), 0, st, b->samples, b->offsets, b->lengths, b->digitisation,
-                           b->offset, b->range, b->n_reads, spr, out);
-    }
-    SGK_HIP_TRY(hipGetLastError());
+    SGK_LAUNCH("k_pa", k_pa, grid, 256, st, b->samples, b->offsets, b->lengths, b->digitisation, b->offset, b->range,
+               b->n_reads, spr, out);
     return SGK_OK;
 }
 
@@ -123,9 +119,8 @@ int launch_synth(int16_t *samples, const uint64_t *offsets, const uint32_t *leng
     const uint32_t spr = (max_read_len + PA_SLAB - 1) / PA_SLAB;
     const uint64_t blocks = (uint64_t)n_reads * (spr ? spr : 1);
     const uint32_t grid = blocks < SLAB_GRID_MAX ? (uint32_t)blocks : SLAB_GRID_MAX;
-    hipLaunchKernelGGL(k_synth, dim3(grid), dim3(256), 0, st, samples, offsets, lengths, dig, off, rng, n_reads,
-                       spr ? spr : 1, first_read, seed, kind);
-    SGK_HIP_TRY(hipGetLastError());
+    SGK_LAUNCH_UNTIMED(k_synth, grid, 256, st, samples, offsets, lengths, dig, off, rng, n_reads, spr ? spr : 1,
+                       first_read, seed, kind);
     return SGK_OK;
 }
 

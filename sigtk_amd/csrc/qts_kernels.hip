@@ -210,11 +210,7 @@ int sgk_qts(int16_t *samples, const uint64_t *offsets, const uint32_t *lengths, 
     // gridDim.x * 256 threads must stay below 2^32: a bounded grid strides over the (read, slab) pairs
     const uint32_t grid = blocks < (1u << 22) ? (uint32_t)blocks : (1u << 22);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    {
-        ProfScope ps("k_qts", st);
-        hipLaunchKernelGGL(k_qts, dim3(grid), dim3(256), 0, st, samples, offsets, lengths, n_reads, spr, bits, method);
-    }
-    SGK_HIP_TRY(hipGetLastError());
+    SGK_LAUNCH("k_qts", k_qts, grid, 256, st, samples, offsets, lengths, n_reads, spr, bits, method);
     return SGK_OK;
 }
 
@@ -224,11 +220,7 @@ int sgk_svbzd_size(const int16_t *samples, const uint64_t *offsets, const uint32
     if (!samples || !offsets || !lengths || !blob_lengths) return SGK_ERR_ARG;
     EncArgs a = {samples, offsets, lengths, n_reads, nullptr, nullptr, blob_lengths};
     hipStream_t st = static_cast<hipStream_t>(stream);
-    {
-        ProfScope ps("k_svbzd_size", st);
-        hipLaunchKernelGGL(k_svbzd_size, dim3(n_reads), dim3(64), 0, st, a);
-    }
-    SGK_HIP_TRY(hipGetLastError());
+    SGK_LAUNCH("k_svbzd_size", k_svbzd_size, n_reads, 64, st, a);
     return SGK_OK;
 }
 
@@ -238,11 +230,7 @@ int sgk_svbzd_encode(const int16_t *samples, const uint64_t *offsets, const uint
     if (!samples || !offsets || !lengths || !blobs || !blob_offsets || !blob_lengths) return SGK_ERR_ARG;
     EncArgs a = {samples, offsets, lengths, n_reads, blobs, blob_offsets, const_cast<uint32_t *>(blob_lengths)};
     hipStream_t st = static_cast<hipStream_t>(stream);
-    {
-        ProfScope ps("k_svbzd_encode", st);
-        hipLaunchKernelGGL(k_svbzd_encode, dim3(n_reads), dim3(64), 0, st, a);
-    }
-    SGK_HIP_TRY(hipGetLastError());
+    SGK_LAUNCH("k_svbzd_encode", k_svbzd_encode, n_reads, 64, st, a);
     return SGK_OK;
 }
 

@@ -31,6 +31,23 @@ struct ProfScope {
     int slot;
 };
 
+// ---- kernel launches ----------------------------------------------------------------
+// One launch on `stream`, timed under `name` (SGK_LAUNCH) or not (SGK_LAUNCH_UNTIMED); a failed launch returns
+// SGK_ERR_HIP from the enclosing function.
+#define SGK_LAUNCH_UNTIMED(kern, grid, block, stream, ...)                             \
+    do {                                                                               \
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, stream, __VA_ARGS__);     \
+        SGK_HIP_TRY(hipGetLastError());                                                \
+    } while (0)
+#define SGK_LAUNCH(name, kern, grid, block, stream, ...)                               \
+    do {                                                                               \
+        {                                                                              \
+            ::sgk::ProfScope ps_(name, stream);                                        \
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, stream, __VA_ARGS__); \
+        }                                                                              \
+        SGK_HIP_TRY(hipGetLastError());                                                \
+    } while (0)
+
 static inline uint64_t round_up(uint64_t x, uint64_t m) { return (x + m - 1) / m * m; }
 
 // ---- device helpers -----------------------------------------------------------------

@@ -2873,10 +2873,9 @@ __global__ __launch_bounds__(256) void k_order_fill(const uint32_t *lengths, uin
 size_t order_workspace_bytes(uint32_t n_reads) { return 64 + ((size_t)n_reads * 4 + 128 * 4 + 63) / 64 * 64; }
 int launch_order(const uint32_t *lengths, uint32_t nr, uint32_t *order, uint32_t *hist, hipStream_t st) {
     SGK_HIP_TRY(hipMemsetAsync(hist, 0, 128 * 4, st));
-    hipLaunchKernelGGL(k_order_count, dim3((nr + 255) / 256), dim3(256), 0, st, lengths, nr, hist);
-    hipLaunchKernelGGL(k_order_scan, dim3(1), dim3(64), 0, st, hist);
-    hipLaunchKernelGGL(k_order_fill, dim3((nr + 255) / 256), dim3(256), 0, st, lengths, nr, hist, order);
-    SGK_HIP_TRY(hipGetLastError());
+    SGK_LAUNCH_UNTIMED(k_order_count, (nr + 255) / 256, 256, st, lengths, nr, hist);
+    SGK_LAUNCH_UNTIMED(k_order_scan, 1, 64, st, hist);
+    SGK_LAUNCH_UNTIMED(k_order_fill, (nr + 255) / 256, 256, st, lengths, nr, hist, order);
     return SGK_OK;
 }
 // the tile records: 8 bytes per tile and sum for the long reads of the batch, at most LC_POOL_TILES tiles
@@ -2938,9 +2937,8 @@ int prepare_long(StatArgs &a, void *ws, size_t ws_bytes, int32_t opt_long_min, L
     a.long_pool_tiles = pool;
     a.long_min = lm;
     SGK_HIP_TRY(hipMemsetAsync(a.long_hdr, 0, sizeof(LongHdr), st));
-    hipLaunchKernelGGL(k_long_list, dim3((a.b.n_reads + 255) / 256), dim3(256), 0, st, a);
-    if (opt_long_min == 0) hipLaunchKernelGGL(k_long_limit, dim3(1), dim3(64), 0, st, a.long_hdr, LC_AUTO_MAX_READS);
-    SGK_HIP_TRY(hipGetLastError());
+    SGK_LAUNCH_UNTIMED(k_long_list, (a.b.n_reads + 255) / 256, 256, st, a);
+    if (opt_long_min == 0) SGK_LAUNCH_UNTIMED(k_long_limit, 1, 64, st, a.long_hdr, LC_AUTO_MAX_READS);
     return SGK_OK;
 }
 // workgroups of k_long_chains: LC_PARTS per long read the batch can hold, all resident at once (at most 64 reads at a
@@ -2989,44 +2987,27 @@ static bool lane_per_read(int tool, const StatArgs &a) {
     return stat_lane_per_read(tool, a.kernels, a.b.n_reads, a.b.n_samples, a.b.max_read_len);
 }
 
-#define SGK_LAUNCH(name, kern, grid, block, ...)                                   \
-    do {                                                                           \
-        ProfScope ps_(name, st);                                                   \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, st, __VA_ARGS__);     \
-    } while (0)
-
-// The wave kernel (wave_launch(stream)) beside k_long_chains<KIND>.  The long reads' few workgroups go to the caller's
-// stream and the wave kernel to a side stream that first waits for the fork event: launched the other way round the long
-// workgroups found every slot taken by the wave kernel's -- whose first workgroups hold the batch's longest reads -- and
-// started 2 ms late.  The side stream joins when the returned guard goes out of scope (or at guard.join()).
-// Behind the join the wave kernel is launched once more over the long list (wave_launch(stream, redo args): LC_CAP waves)
-// for the reads k_long_chains declined -- a barrier of theirs timed out, lc_barrier; usually none, the launch costs a few
-// microseconds: no read's result depends on the long path having worked.
+// The wave kernel (wave_launch(stream, args, grid) -> int) beside k_long_chains<KIND>.  The long reads' few workgroups
+// go to the caller's stream and the wave kernel to a side stream that first waits for the fork event: launched the other
+// way round the long workgroups found every slot taken by the wave kernel's -- whose first workgroups hold the batch's
+// longest reads -- and started 2 ms late.  Behind the join the wave kernel is launched once more over the long list
+// (redo args: LC_CAP waves) for the reads k_long_chains declined -- a barrier of theirs timed out, lc_barrier; usually
+// none, the launch costs a few microseconds: no read's result depends on the long path having worked.
 template <int KIND, typename WL>
 static int launch_beside_long(const StatArgs &a, const JnnP &p, const AdaptP &ap, const char *name, hipStream_t st,
                               WL wave_launch) {
-    if (!a.longs) {
-        wave_launch(st, a, (a.b.n_reads + 3) / 4);
-        SGK_HIP_TRY(hipGetLastError());
-        return SGK_OK;
-    }
+    if (!a.longs) return wave_launch(st, a, (a.b.n_reads + 3) / 4);
     {
         SideFork side;  // (joins at the end of this block)
-        const bool forked = side.open(0, st);
-        {
-            ProfScope ps_(name, st);
-            hipLaunchKernelGGL((k_long_chains<KIND>), dim3(long_grid(a)), dim3(LC_WG_WAVES * 64), 0, st, a, p, ap);
-        }
-        SGK_HIP_TRY(hipGetLastError());
-        wave_launch(forked ? side.stream() : st, a, (a.b.n_reads + 3) / 4);
-        SGK_HIP_TRY(hipGetLastError());
+        side.open(st, 1);
+        SGK_LAUNCH(name, (k_long_chains<KIND>), long_grid(a), LC_WG_WAVES * 64, st, a, p, ap);
+        const int rc = wave_launch(side.stream(0), a, (a.b.n_reads + 3) / 4);
+        if (rc != SGK_OK) return rc;
     }
     StatArgs redo = a;
     redo.long_redo = 1u;
     redo.order = nullptr;
-    wave_launch(st, redo, LC_CAP / 4);
-    SGK_HIP_TRY(hipGetLastError());
-    return SGK_OK;
+    return wave_launch(st, redo, LC_CAP / 4);
 }
 
 int launch_stat(const StatArgs &a, hipStream_t st) {
@@ -3034,34 +3015,28 @@ int launch_stat(const StatArgs &a, hipStream_t st) {
     if (nr == 0) return SGK_OK;
     if (lane_per_read(a.pa_out ? 3 : 0, a)) {
         if (a.pa_out) {
-            SGK_LAUNCH("k_moments", (k_moments<REG_WHOLE>), (nr + 63) / 64, 64, a);
-            SGK_HIP_TRY(hipGetLastError());
-            SGK_LAUNCH("k_median_pa", (k_median<REG_WHOLE, true>), nr, 256, a);
+            SGK_LAUNCH("k_moments", (k_moments<REG_WHOLE>), (nr + 63) / 64, 64, st, a);
+            SGK_LAUNCH("k_median_pa", (k_median<REG_WHOLE, true>), nr, 256, st, a);
         } else if (nr >= STAT_MOMENTS_MEDIAN_MIN_READS) {
             // the medians come out of the moments' second pass; k_median only for the reads it flagged.  (With fewer reads
             // k_moments has too few wavefronts -- 64 reads each -- to hide what the counting adds, and k_median, a
             // workgroup per read, fills the GPU: 61 035 x 32 768 fused 2.70, apart 2.33 ms; 100 000 x 20 000 2.00 / 2.24.)
-            SGK_LAUNCH("k_moments_median", (k_moments<REG_WHOLE, true>), (nr + 63) / 64, 64, a);
-            SGK_HIP_TRY(hipGetLastError());
-            SGK_LAUNCH("k_median_flagged", (k_median<REG_WHOLE, false, true>), nr, 256, a);
+            SGK_LAUNCH("k_moments_median", (k_moments<REG_WHOLE, true>), (nr + 63) / 64, 64, st, a);
+            SGK_LAUNCH("k_median_flagged", (k_median<REG_WHOLE, false, true>), nr, 256, st, a);
         } else {
-            SGK_LAUNCH("k_moments", (k_moments<REG_WHOLE>), (nr + 63) / 64, 64, a);
-            SGK_HIP_TRY(hipGetLastError());
-            SGK_LAUNCH("k_median", (k_median<REG_WHOLE, false>), nr, 256, a);
+            SGK_LAUNCH("k_moments", (k_moments<REG_WHOLE>), (nr + 63) / 64, 64, st, a);
+            SGK_LAUNCH("k_median", (k_median<REG_WHOLE, false>), nr, 256, st, a);
         }
-        SGK_HIP_TRY(hipGetLastError());
         return SGK_OK;
     }
     // the long reads' workgroups run beside the wave kernel (which skips those reads) when a side stream is to be had
-    {
-        const int rc = launch_beside_long<LC_STAT>(a, JnnP{}, AdaptP{}, "k_long_chains_stat", st, [&](hipStream_t st, const StatArgs &aw, uint32_t grid) {
-            if (aw.pa_out) SGK_LAUNCH(aw.long_redo ? "k_stat_wave_pa_redo" : "k_stat_wave_pa", (k_stat_wave<REG_WHOLE, true>), grid, 256, aw);
-            else SGK_LAUNCH(aw.long_redo ? "k_stat_wave_redo" : "k_stat_wave", (k_stat_wave<REG_WHOLE, false>), grid, 256, aw);
-        });
-        if (rc != SGK_OK) return rc;
-    }
-    SGK_LAUNCH("k_median_flagged", (k_median<REG_WHOLE, false, true>), nr, 256, a);
-    SGK_HIP_TRY(hipGetLastError());
+    const int rc = launch_beside_long<LC_STAT>(a, JnnP{}, AdaptP{}, "k_long_chains_stat", st, [&](hipStream_t st, const StatArgs &aw, uint32_t grid) {
+        if (aw.pa_out) SGK_LAUNCH(aw.long_redo ? "k_stat_wave_pa_redo" : "k_stat_wave_pa", (k_stat_wave<REG_WHOLE, true>), grid, 256, st, aw);
+        else SGK_LAUNCH(aw.long_redo ? "k_stat_wave_redo" : "k_stat_wave", (k_stat_wave<REG_WHOLE, false>), grid, 256, st, aw);
+        return SGK_OK;
+    });
+    if (rc != SGK_OK) return rc;
+    SGK_LAUNCH("k_median_flagged", (k_median<REG_WHOLE, false, true>), nr, 256, st, a);
     return SGK_OK;
 }
 
@@ -3070,55 +3045,74 @@ int launch_jnn(const StatArgs &a, const JnnP &p, hipStream_t st) {
     if (nr == 0) return SGK_OK;
     SGK_HIP_TRY(hipMemsetAsync(a.err_count, 0, 4, st));
     const bool wave_ok = p.error >= 0 && p.error < p.corrector && p.error <= 31 && p.window >= 128;
-    if (lane_per_read(1, a) || !wave_ok) SGK_LAUNCH("k_jnn", k_jnn, (nr + 63) / 64, 64, a, p);
-    else {
-        StatArgs aw = a;
-        if (!(p.std_scale > 0.0f)) aw.longs = nullptr;  // (fixed thresholds: no sums, k_jnn_wave does every read)
-        {
-            const int rc = launch_beside_long<LC_JNN>(aw, p, AdaptP{}, "k_long_chains_jnn", st, [&](hipStream_t st, const StatArgs &ax, uint32_t grid) {
-                SGK_LAUNCH(ax.long_redo ? "k_jnn_wave_redo" : "k_jnn_wave", k_jnn_wave, grid, 256, ax, p);
-            });
-            if (rc != SGK_OK) return rc;
-        }
-        StatArgs redo = a;
-        redo.jnn_redo = 1u;  // the reads the wave kernel gave up on (none, usually: its wavefronts return at once)
-        SGK_LAUNCH("k_jnn_redo", k_jnn, (nr + 63) / 64, 64, redo, p);
+    if (lane_per_read(1, a) || !wave_ok) {
+        SGK_LAUNCH("k_jnn", k_jnn, (nr + 63) / 64, 64, st, a, p);
+        return SGK_OK;
     }
-    SGK_HIP_TRY(hipGetLastError());
+    StatArgs aw = a;
+    if (!(p.std_scale > 0.0f)) aw.longs = nullptr;  // (fixed thresholds: no sums, k_jnn_wave does every read)
+    const int rc = launch_beside_long<LC_JNN>(aw, p, AdaptP{}, "k_long_chains_jnn", st, [&](hipStream_t st, const StatArgs &ax, uint32_t grid) {
+        SGK_LAUNCH(ax.long_redo ? "k_jnn_wave_redo" : "k_jnn_wave", k_jnn_wave, grid, 256, st, ax, p);
+        return SGK_OK;
+    });
+    if (rc != SGK_OK) return rc;
+    StatArgs redo = a;
+    redo.jnn_redo = 1u;  // the reads the wave kernel gave up on (none, usually: its wavefronts return at once)
+    SGK_LAUNCH("k_jnn_redo", k_jnn, (nr + 63) / 64, 64, st, redo, p);
     return SGK_OK;
 }
 
 int launch_adaptor(const StatArgs &a, const AdaptP &p, hipStream_t st) {
     const uint32_t nr = a.b.n_reads;
     if (nr == 0) return SGK_OK;
-    if (lane_per_read(2, a)) SGK_LAUNCH("k_adaptor", k_adaptor, (nr + 63) / 64, 64, a, p);
-    else {
-        const int rc = launch_beside_long<LC_ADAPT>(a, JnnP{}, p, "k_long_chains_adapt", st, [&](hipStream_t st, const StatArgs &ax, uint32_t grid) {
-            SGK_LAUNCH(ax.long_redo ? "k_adaptor_wave_redo" : "k_adaptor_wave", k_adaptor_wave, grid, 256, ax, p);
-        });
-        if (rc != SGK_OK) return rc;
+    if (lane_per_read(2, a)) {
+        SGK_LAUNCH("k_adaptor", k_adaptor, (nr + 63) / 64, 64, st, a, p);
+        return SGK_OK;
     }
-    SGK_HIP_TRY(hipGetLastError());
-    return SGK_OK;
+    return launch_beside_long<LC_ADAPT>(a, JnnP{}, p, "k_long_chains_adapt", st, [&](hipStream_t st, const StatArgs &ax, uint32_t grid) {
+        SGK_LAUNCH(ax.long_redo ? "k_adaptor_wave_redo" : "k_adaptor_wave", k_adaptor_wave, grid, 256, st, ax, p);
+        return SGK_OK;
+    });
 }
 
 int launch_stat_f32(const float *x, int n, float *out3, hipStream_t st) {
-    SGK_LAUNCH("k_stat_f32", k_stat_f32, 1, 256, x, n, out3);
-    SGK_HIP_TRY(hipGetLastError());
+    SGK_LAUNCH("k_stat_f32", k_stat_f32, 1, 256, st, x, n, out3);
     return SGK_OK;
 }
 
 int launch_jnn_f32(const float *x, int64_t n, const JnnP &p, int32_t *seg_x, int32_t *seg_y, uint32_t cap,
                    uint32_t *n_segs, hipStream_t st) {
-    SGK_LAUNCH("k_jnn_f32", k_jnn_f32, 1, 64, x, n, p, seg_x, seg_y, cap, n_segs);
-    SGK_HIP_TRY(hipGetLastError());
+    SGK_LAUNCH("k_jnn_f32", k_jnn_f32, 1, 64, st, x, n, p, seg_x, seg_y, cap, n_segs);
+    return SGK_OK;
+}
+
+// The statistics of one region the prefix finders found (REG_ADAPT / REG_POLYA), under the region's profile names.
+// lane_regions && !lanes: the medians out of the moments' second pass, k_median for the regions it flags.
+template <int REGION>
+static int launch_region_stats(const StatArgs &a, bool lanes, bool lane_regions, hipStream_t st) {
+    static_assert(REGION == REG_ADAPT || REGION == REG_POLYA, "a prefix region");
+    struct Names { const char *moments_median, *median_flagged, *moments, *median, *stat_wave; };
+    static constexpr Names NAMES[2] = {
+        {"k_moments_median_adapt", "k_median_adapt_flagged", "k_moments_adapt", "k_median_adapt", "k_stat_wave_adapt"},
+        {"k_moments_median_polya", "k_median_polya_flagged", "k_moments_polya", "k_median_polya", "k_stat_wave_polya"}};
+    const Names &n = NAMES[REGION == REG_POLYA];
+    const uint32_t nr = a.b.n_reads;
+    if (lane_regions && !lanes) {
+        SGK_LAUNCH(n.moments_median, (k_moments<REGION, true>), (nr + 63) / 64, 64, st, a);
+        SGK_LAUNCH(n.median_flagged, (k_median<REGION, false, true>), nr, 256, st, a);
+    } else if (lane_regions) {
+        SGK_LAUNCH(n.moments, (k_moments<REGION>), (nr + 63) / 64, 64, st, a);
+        SGK_LAUNCH(n.median, (k_median<REGION>), nr, 256, st, a);
+    } else {
+        SGK_LAUNCH(n.stat_wave, (k_stat_wave<REGION, false>), (nr + 3) / 4, 256, st, a);
+        SGK_LAUNCH(n.median_flagged, (k_median<REGION, false, true>), nr, 256, st, a);
+    }
     return SGK_OK;
 }
 
 int launch_prefix(const StatArgs &a, int rna, int pore, hipStream_t st) {
     const uint32_t nr = a.b.n_reads;
     if (nr == 0) return SGK_OK;
-    const uint32_t gw = (nr + 63) / 64;
     // The adaptor and polyA finders: one read per wavefront unless the caller forces the lane kernels (k_adaptor_wave 4.3
     // against k_adaptor 5.5 ms on 400 000 x 5 000, 13.4 against 29 on 125 000 x 100 000; k_polya_wave 0.2 against 1.2 - 5.9).
     // The statistics of the regions they find are a few thousand samples per read whatever the read's length: with enough
@@ -3126,50 +3120,13 @@ int launch_prefix(const StatArgs &a, int rna, int pore, hipStream_t st) {
     // 5 000), 0.9 + 1.2 against 1.1 + 1.4 (50 000 x 100 000 RNA, adaptor + polyA), a tie at 125 000 x 100 000.
     const bool lanes = lane_per_read(2, a);
     const bool lane_regions = lanes || lane_per_read(4, a);
-    if (lanes) SGK_LAUNCH("k_adaptor", k_adaptor, gw, 64, a, adaptor_preset(pore));
-    else {
-        // (joined inside: the kernels behind read every read's adapt_x / adapt_y)
-        const AdaptP ap = adaptor_preset(pore);
-        const int rc = launch_beside_long<LC_ADAPT>(a, JnnP{}, ap, "k_long_chains_adapt", st, [&](hipStream_t st, const StatArgs &ax, uint32_t grid) {
-            SGK_LAUNCH(ax.long_redo ? "k_adaptor_wave_redo" : "k_adaptor_wave", k_adaptor_wave, grid, 256, ax, ap);
-        });
-        if (rc != SGK_OK) return rc;
-    }
-    SGK_HIP_TRY(hipGetLastError());
-    if (lane_regions && !lanes) {  // (the medians out of the moments' second pass, k_median for the regions it flags)
-        SGK_LAUNCH("k_moments_median_adapt", (k_moments<REG_ADAPT, true>), gw, 64, a);
-        SGK_HIP_TRY(hipGetLastError());
-        SGK_LAUNCH("k_median_adapt_flagged", (k_median<REG_ADAPT, false, true>), nr, 256, a);
-    } else if (lane_regions) {
-        SGK_LAUNCH("k_moments_adapt", (k_moments<REG_ADAPT>), gw, 64, a);
-        SGK_HIP_TRY(hipGetLastError());
-        SGK_LAUNCH("k_median_adapt", (k_median<REG_ADAPT>), nr, 256, a);
-    } else {
-        SGK_LAUNCH("k_stat_wave_adapt", (k_stat_wave<REG_ADAPT, false>), (nr + 3) / 4, 256, a);
-        SGK_HIP_TRY(hipGetLastError());
-        SGK_LAUNCH("k_median_adapt_flagged", (k_median<REG_ADAPT, false, true>), nr, 256, a);
-    }
-    SGK_HIP_TRY(hipGetLastError());
-    if (rna) {
-        if (lanes) SGK_LAUNCH("k_polya", k_polya, gw, 64, a);
-        else SGK_LAUNCH("k_polya_wave", k_polya_wave, (nr + 3) / 4, 256, a);
-        SGK_HIP_TRY(hipGetLastError());
-        if (lane_regions && !lanes) {
-            SGK_LAUNCH("k_moments_median_polya", (k_moments<REG_POLYA, true>), gw, 64, a);
-            SGK_HIP_TRY(hipGetLastError());
-            SGK_LAUNCH("k_median_polya_flagged", (k_median<REG_POLYA, false, true>), nr, 256, a);
-        } else if (lane_regions) {
-            SGK_LAUNCH("k_moments_polya", (k_moments<REG_POLYA>), gw, 64, a);
-            SGK_HIP_TRY(hipGetLastError());
-            SGK_LAUNCH("k_median_polya", (k_median<REG_POLYA>), nr, 256, a);
-        } else {
-            SGK_LAUNCH("k_stat_wave_polya", (k_stat_wave<REG_POLYA, false>), (nr + 3) / 4, 256, a);
-            SGK_HIP_TRY(hipGetLastError());
-            SGK_LAUNCH("k_median_polya_flagged", (k_median<REG_POLYA, false, true>), nr, 256, a);
-        }
-        SGK_HIP_TRY(hipGetLastError());
-    }
-    return SGK_OK;
+    // (launch_adaptor joins its side stream inside: the kernels behind read every read's adapt_x / adapt_y)
+    int rc = launch_adaptor(a, adaptor_preset(pore), st);
+    if (rc == SGK_OK) rc = launch_region_stats<REG_ADAPT>(a, lanes, lane_regions, st);
+    if (rc != SGK_OK || !rna) return rc;
+    if (lanes) SGK_LAUNCH("k_polya", k_polya, (nr + 63) / 64, 64, st, a);
+    else SGK_LAUNCH("k_polya_wave", k_polya_wave, (nr + 3) / 4, 256, st, a);
+    return launch_region_stats<REG_POLYA>(a, lanes, lane_regions, st);
 }
 
 }  // namespace sgk

@@ -129,11 +129,7 @@ __global__ __launch_bounds__(64) void k_svbzd_decode(SvbArgs a) {
 
 int launch_svbzd(const SvbArgs &a, hipStream_t st) {
     if (a.n_reads == 0) return SGK_OK;
-    {
-        ProfScope ps("k_svbzd_decode", st);
-        hipLaunchKernelGGL(k_svbzd_decode, dim3(a.n_reads), dim3(64), 0, st, a);
-    }
-    SGK_HIP_TRY(hipGetLastError());
+    SGK_LAUNCH("k_svbzd_decode", k_svbzd_decode, a.n_reads, 64, st, a);
     return SGK_OK;
 }
 

@@ -198,3 +198,67 @@ def test_two_threads_with_different_geometries_on_one_device(gpu, oracle):
         t.join()
     assert not errors, errors
     assert seen["small"] == sum(1 for n in lens if n >= 1025) and seen["default"] == 0
+
+
+def test_more_threads_than_side_stream_slots_on_one_device(gpu, oracle):
+    """The library's side streams (a pool of 4 slots per device) are shared by every launch of the process.  Eight
+    threads drive a job each on device 0 and alternate `event` on a batch that forks both side streams (packed short
+    reads beside 1024-sample segments) with `stat` and `jnn` on reads above a lowered long_min (the long path forks one).
+    Every result equals that of a single-threaded run done first; a thread still alive after 120 s is a deadlock."""
+    import threading
+    import time
+    ev_lens = [5000, 3000, 900, 1500, 12000, 700, 2048, 1025, 1024, 16000, 0, 64, 9000]
+    ev_batch = _batch(gpu, ev_lens, 93, 0)
+    ev_opt = gpu.EventOptions()
+    ev_opt.segment_len, ev_opt.long_min, ev_opt.warmup, ev_opt.lanes_per_short_read = 1024, 1025, 16, 4
+    p = gpu.event_plan(len(ev_lens), sum(ev_lens), max(ev_lens), 0, ev_opt)
+    assert p.lanes_per_short_read > 0 and p.max_segments > 0 and max(ev_lens) >= p.long_min   # k_event_multi and k_event beside
+    st_lens = [60000, 3000, 45000, 800, 25000, 0, 9000, 120000, 5000]
+    st_batch = _batch(gpu, st_lens, 94, 0)
+    st_opt = gpu.StatOptions()
+    st_opt.long_min = 20000
+    for tool in ("stat", "jnn"):
+        q = gpu.stat_plan(tool, len(st_lens), sum(st_lens), max(st_lens), st_opt)
+        assert q.kernels == 2 and q.long_min == 20000, tool   # the wave kernel beside k_long_chains
+
+    tools = (gpu.TOOL_EVENT, gpu.TOOL_STAT, gpu.TOOL_JNN)
+    batches = {gpu.TOOL_EVENT: ev_batch, gpu.TOOL_STAT: st_batch, gpu.TOOL_JNN: st_batch}
+
+    def run(job, tool):   # -> the results as bytes
+        job.submit(tool, *batches[tool])
+        res = job.wait()
+        if tool == gpu.TOOL_EVENT:
+            return [(e.start.tobytes(), e.length.tobytes(), e.mean.tobytes(), e.stdv.tobytes()) for e in res["events"]]
+        return res["stat"].tobytes() if tool == gpu.TOOL_STAT else [(x.tobytes(), y.tobytes()) for x, y in res["segs"]]
+
+    job = gpu.Job(0)
+    job.set_options(ev_opt, st_opt)
+    exp = {t: run(job, t) for t in tools}
+    job.submit(gpu.TOOL_EVENT, *ev_batch)
+    events = job.wait()["events"]
+    job.close()
+    reads, dig, off, rng = ev_batch
+    for i, raw in enumerate(reads):
+        if raw.size:
+            _same_events(events[i], oracle.event_raw(raw, dig[i], off[i], rng[i], 0), "read %d" % i)
+    errors = []
+
+    def worker(k):
+        try:
+            job = gpu.Job(0)
+            job.set_options(ev_opt, st_opt)
+            for it in range(4):
+                for t in tools[k % 3:] + tools[:k % 3]:
+                    assert run(job, t) == exp[t], "thread %d, iteration %d, tool %d" % (k, it, t)
+            job.close()
+        except Exception as ex:   # noqa: BLE001 -- reported below, in the main thread
+            errors.append("thread %d: %r" % (k, ex))
+
+    ts = [threading.Thread(target=worker, args=(k,), daemon=True) for k in range(8)]
+    for t in ts:
+        t.start()
+    deadline = time.monotonic() + 120
+    for t in ts:
+        t.join(max(0.0, deadline - time.monotonic()))
+    assert not any(t.is_alive() for t in ts), "threads still running after 120 s: deadlock"
+    assert not errors, errors
