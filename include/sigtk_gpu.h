@@ -280,7 +280,7 @@ typedef struct sgk_stat_options {
                          * -1 = never; else the threshold (>= 8 192).  Results do not depend on it.  Needs the workspace
                          * sgk_*_workspace_bytes asks for (with less, such reads run on one wavefront). */
     uint32_t debug_fault; /* 0.  Tests only: fault injection into the long-read path's barriers (a withheld workgroup /
-                           * a tiny spin bound, see lc_barrier in csrc/stat_kernels.hip) to exercise the decline-and-redo path */
+                           * a tiny spin bound, see lc_barrier in csrc/stat_long.hip) to exercise the decline-and-redo path */
     uint32_t reserved;
 } sgk_stat_options_t;
 int sgk_stat_opt(const sgk_batch_t *batch, sgk_stat_rec_t *out, void *workspace, size_t workspace_bytes, void *stream,

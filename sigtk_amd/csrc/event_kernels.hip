@@ -2314,7 +2314,7 @@ static int launch_event_t(const EvArgs &a, uint32_t n_fb_blocks, hipStream_t st)
     // The segments' kernel.  Long reads' segments start FIRST: they stay on the caller's stream and k_event goes to a
     // side stream whose start waits for the fork event (the other way round k_event's workgroups -- ten thousand of them
     // -- take every slot and the chains start late: a ragged batch took 3.81 ms instead of 3.65; stat's long reads taught
-    // the same, stat_kernels.hip launch_beside_long).  The tail split's segments go LAST, behind k_event on the caller's
+    // the same, stat_launch.hip launch_beside_long).  The tail split's segments go LAST, behind k_event on the caller's
     // stream: small units for the slots the last whole reads leave empty.  (Tried for them: a stream of the LOWEST
     // priority, to be dispatched into the slots k_event's last waves leave empty -- 5.1 vs 3.8 ms on config 2.)
     const bool tail_only = ao.max_segs && ao.split_seg && !ao.has_long;

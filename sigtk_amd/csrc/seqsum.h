@@ -53,15 +53,16 @@ __device__ __forceinline__ uint32_t ss_opaque_zero() {
     return z;
 }
 
-// per-wave counters of what the chain had to do (debug / bench builds)
-struct SsCount {
-    uint32_t tiles, generic, walks, crossings, composes, serial;
-};
-
 // A chain's terms come from a functor: `template <int E> float get() const` is term lane * SS_SPL + E of the tile
 // (oriented like the accumulator, 0 where the tile has no sample); `with(z)` is the same functor reading its samples
 // through the opaque zero z.  Terms are recomputed from the packed samples where
 // they are needed rather than kept in registers.
+struct TermArr {  // ... unless they are no samples: terms kept in registers (float arrays, rolling means)
+    const float (&x)[SS_SPL];
+    __device__ __forceinline__ TermArr with(uint32_t) const { return *this; }
+    template <int E>
+    __device__ __forceinline__ float get() const { return x[E]; }
+};
 
 // m = fl(m + term) over ALL terms of the lanes l0 .. l1 of the tile, in order (terms the functor masks are 0, and
 // fl(m + 0) = m: the accumulator is never -0).  One readlane and one dependent addition per term.
@@ -187,10 +188,8 @@ __device__ __forceinline__ int ss_fast(float &m, const SsWalk &w, const TF &tf, 
 // w: ss_walk(m, ...) of the same tile (so that the walks of several chains can be issued together, ahead of the
 // branching below); NEG: the terms can be negative.  Returns the accumulator after the tile's 64 * SS_SPL terms.
 template <bool NEG, typename TF>
-__device__ inline float ss_finish(float m, const TF &tf0, SsWalk w, int skip = 0 /* lanes already done (ss_fast) */,
-                                  SsCount *cnt = nullptr) {
+__device__ inline float ss_finish(float m, const TF &tf0, SsWalk w, int skip = 0 /* lanes already done (ss_fast) */) {
     const int lane = lane_id();
-    if (cnt) ++cnt->generic;
     for (;;) {
         m = ss_uniform(m);
         const uint32_t mb = ss_bits(m);
@@ -211,24 +210,20 @@ __device__ inline float ss_finish(float m, const TF &tf0, SsWalk w, int skip = 0
         const int S = (int)((mb & 0x7fffffu) | 0x800000u);
         const uint32_t b0 = (ex << 23) | 0x400000u, b1 = b0 + 1u;
         if (skip) w = ss_walk<NEG>(m, tf0.with(ss_opaque_zero()));
-        if (cnt) ++cnt->walks;
         const bool live = lane >= skip;
         const uint32_t c0 = ss_bits(w.a0), c1 = ss_bits(w.a1);
         const bool inr = ((c0 ^ b0) | (c1 ^ b1)) < 0x800000u;  // both surrogates ended in their binade (NaN: no)
         if (__any(live && (!inr || (NEG && (w.neg >> 31))))) break;
         const int f0 = live ? (int)(c0 - b0) : 0, f1 = live ? (int)(c1 - b1) : 0;
         int f = f0;
-        if (__any(f0 != f1)) {  // some lane met a tie: the parity of S matters
-            if (cnt) ++cnt->composes;
-            f = __builtin_amdgcn_inverse_ballot_w64(ss_parity_in(f0, f1, S)) ? f1 : f0;
-        }
+        // (some lane met a tie: the parity of S matters)
+        if (__any(f0 != f1)) f = __builtin_amdgcn_inverse_ballot_w64(ss_parity_in(f0, f1, S)) ? f1 : f0;
         const int incl = wave_incl_scan_i(f);
         const int tot = wave_last_i(incl);
         const float u = ss_float((ex - 23u) << 23);
         if (S + tot <= (1 << 24)) return (float)(S + tot) * u;
         // the sum leaves the binade inside this tile: the first lane whose end value is beyond the binade's top runs
         // its terms natively from its true start; the lanes behind it repeat with the new binade
-        if (cnt) ++cnt->crossings;
         const int Sl = S + incl - f;
         const unsigned long long cm = __ballot(Sl + f > (1 << 24));
         const int ls = (int)__builtin_amdgcn_readfirstlane(__ffsll((long long)cm) - 1);
@@ -238,7 +233,6 @@ __device__ inline float ss_finish(float m, const TF &tf0, SsWalk w, int skip = 0
         skip = ls + 1;
         if (skip >= 64) return m;
     }
-    if (cnt) ++cnt->serial;
     return ss_serial(m, tf0.with(ss_opaque_zero()), skip, 63);
 }
 

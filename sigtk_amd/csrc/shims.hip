@@ -1,7 +1,7 @@
 // shims.hip -- per-read entry points with the reference's own signatures (SURVEY.md 8b "signatures to keep"):
 // jnn_raw / jnn_pa / jnnv2 / find_adaptor / find_polya (src/jnn.h:104-109) and the six stat.h inlines
 // (src/stat.h:17-73).  Each is a batch of one over the batched kernels (or, for float input, over the single-array
-// compatibility kernels of stat_kernels.hip); results are malloc'd by the callee and freed by the caller, as in the
+// compatibility kernels k_jnn_f32 / k_stat_f32 below); results are malloc'd by the callee and freed by the caller, as in the
 // reference.  They exist so that a maintainer can diff every function against the original; throughput comes from
 // the batch API.  On any failure (no device, out of memory, unsupported parameter) they return NULL / {-1,-1} / NaN
 // and sgk_shim_status() tells why.
@@ -12,8 +12,141 @@
 #include <vector>
 
 #include "host_util.h"
+#include "seqsum.h"
 #include "sgk_common.h"
 #include "stat_args.h"
+#include "stat_device.h"
+
+namespace sgk {
+
+// jnn_pa (src/jnn.c:295-306) on ONE float array: jnn_core over rm_outlierf(x).  A compatibility entry (the batched
+// path never holds pA in memory); every lane of the single wave walks the array, lane 0 stores.
+__global__ __launch_bounds__(64) void k_jnn_f32(const float *x, int64_t n, JnnP p, int32_t *seg_x, int32_t *seg_y,
+                                                uint32_t cap, uint32_t *n_segs) {
+    float top = p.top, bot = p.bot;
+    if (p.std_scale > 0.0f) {
+        float s = 0.0f;
+        for (int64_t j = 0; j < n; ++j) s = s + clampf_pa(x[j]);
+        const float mn = s / (float)(int)n;
+        float q = 0.0f;
+        for (int64_t j = 0; j < n; ++j) {
+            const float d = clampf_pa(x[j]) - mn;
+            q = q + d * d;
+        }
+        const float sd = sqrtf(q / (float)(int)n);
+        top = mn + sd * p.std_scale;
+        bot = mn - sd * p.std_scale;
+    }
+    JnnAuto A;
+    A.init(top, bot, p.corrector, p.seg_dist, p.window, p.stall_len, p.error);
+    bool overflow = false;
+    const bool writer = lane_id() == 0;
+    auto emit = [&](int k, int sx, int sy) {
+        if ((uint32_t)k < cap) { if (writer) { seg_x[k] = sx; seg_y[k] = sy; } }
+        else overflow = true;
+    };
+    for (int64_t j = 0; j < n; ++j) A.step((int)j, A.in_mask_f(clampf_pa(x[j])), emit);
+    A.finish(emit);
+    if (writer) {
+        n_segs[0] = (uint32_t)A.nseg;
+        n_segs[1] = overflow ? 1u : 0u;
+    }
+}
+
+// meanf / stdvf / medianf (src/stat.h:17-27, 36-44, 56-63) of ONE float array, for the reference-signature shims:
+// the sequential float sums on every lane of the wave (lane 0 stores), the order statistic of rank n/2 by a
+// three-level (11 + 11 + 10 bit) radix select on the order-preserving integer image of the floats.
+// one seqsum.h chain over a float array: term(x[i]) for i = 0 .. n-1, by one wave (the other waves of the workgroup
+// skip it).  Terms can have any sign: the chain is oriented by the sign of its accumulator, tiles holding a term of
+// the other sign are added natively.
+template <typename F>
+__device__ float ss_chain_f32(const float *x, int n, F term) {
+    const int lane = lane_id(), q0 = lane * SS_SPL;
+    float m = 0.0f, sg = 1.0f;
+    const int ntiles = (n + SS_TILE - 1) / SS_TILE;
+    const int head = n < SS_HEAD ? n : SS_HEAD;
+    for (int t = 0; t < ntiles; ++t) {
+        float v[SS_SPL], y[SS_SPL];
+#pragma unroll
+        for (int e = 0; e < SS_SPL; ++e) {
+            const int i = t * SS_TILE + q0 + e;
+            v[e] = i < n ? term(x[i]) * sg : 0.0f;  // (* +-1: exact)
+        }
+        if (t == 0) {  // the head natively; its terms are zeroed for the tile chain
+#pragma unroll
+            for (int e = 0; e < SS_SPL; ++e) y[e] = (q0 + e < head) ? v[e] : 0.0f;
+            if (head > 0) m = ss_serial(m, TermArr{y}, 0, (head - 1) / SS_SPL);
+#pragma unroll
+            for (int e = 0; e < SS_SPL; ++e) v[e] = (q0 + e < head) ? 0.0f : v[e];
+        }
+        const SsWalk w = ss_walk<true>(m, TermArr{v});
+        int sk;
+        if (ss_fast<true>(m, w, TermArr{v}, sk)) m = ss_finish<true>(m, TermArr{v}, w, sk);
+        if (m < 0.0f) { m = -m; sg = -sg; }
+    }
+    return m == 0.0f ? 0.0f : m * sg;
+}
+
+__global__ __launch_bounds__(256) void k_stat_f32(const float *x, int n, float *out3) {
+    __shared__ uint32_t hist[2048];
+    __shared__ uint32_t sel_prefix, sel_rank;
+    if (threadIdx.x < 64) {  // wave 0: the sequential float sums through seqsum.h
+        const float s = ss_chain_f32(x, n, [](float v) { return v; });
+        const float mn = s / n;
+        const float q = ss_chain_f32(x, n, [&](float v) { return (v - mn) * (v - mn); });
+        if (threadIdx.x == 0) { out3[0] = mn; out3[1] = sqrtf(q / n); }
+    }
+    auto key = [](float f) -> uint32_t {
+        const uint32_t u = __float_as_uint(f);
+        return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    };
+    uint32_t prefix = 0u, rank = (uint32_t)(n / 2);
+    const int shifts[3] = {21, 10, 0};
+    const int bitsn[3] = {11, 11, 10};
+    uint32_t known = 0u;  // mask of the key bits fixed so far
+    for (int lvl = 0; lvl < 3; ++lvl) {
+        for (int k = threadIdx.x; k < 2048; k += 256) hist[k] = 0u;
+        __syncthreads();
+        for (int j = threadIdx.x; j < n; j += 256) {
+            const uint32_t kk = key(x[j]);
+            if ((kk & known) == prefix) atomicAdd(&hist[(kk >> shifts[lvl]) & ((1u << bitsn[lvl]) - 1u)], 1u);
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint32_t acc = 0u, b = 0u;
+            const uint32_t nb = 1u << bitsn[lvl];
+            for (; b < nb; ++b) {
+                if (acc + hist[b] > rank) break;
+                acc += hist[b];
+            }
+            sel_prefix = prefix | (b << shifts[lvl]);
+            sel_rank = rank - acc;
+        }
+        __syncthreads();
+        prefix = sel_prefix;
+        rank = sel_rank;
+        known |= ((1u << bitsn[lvl]) - 1u) << shifts[lvl];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const uint32_t u = (prefix & 0x80000000u) ? (prefix & 0x7fffffffu) : ~prefix;
+        out3[2] = __uint_as_float(u);
+    }
+}
+
+static int launch_stat_f32(const float *x, int n, float *out3, hipStream_t st) {
+    SGK_LAUNCH("k_stat_f32", k_stat_f32, 1, 256, st, x, n, out3);
+    return SGK_OK;
+}
+
+static int launch_jnn_f32(const float *x, int64_t n, const JnnP &p, int32_t *seg_x, int32_t *seg_y, uint32_t cap,
+                          uint32_t *n_segs, hipStream_t st) {
+    SGK_LAUNCH("k_jnn_f32", k_jnn_f32, 1, 64, st, x, n, p, seg_x, seg_y, cap, n_segs);
+    return SGK_OK;
+}
+
+
+}  // namespace sgk
 
 using namespace sgk;
 

@@ -1,4 +1,5 @@
-// stat_args.h -- argument block of the stat / jnn / prefix kernels.
+// stat_args.h -- argument block of the stat / jnn / prefix kernels, and what their translation units (stat_lane.hip,
+// stat_wave.hip, stat_long.hip, stat_launch.hip, shims.hip; the map is in stat_device.h) export to one another.
 #pragma once
 #include "sgk_common.h"
 
@@ -164,10 +165,25 @@ int launch_stat(const StatArgs &a, hipStream_t st);  // a.pa_out != null: fused 
 int launch_jnn(const StatArgs &a, const JnnP &p, hipStream_t st);
 int launch_prefix(const StatArgs &a, int rna, int pore, hipStream_t st);
 int launch_adaptor(const StatArgs &a, const AdaptP &p, hipStream_t st);  // jnnv2 only: prefix[r].adapt_x / adapt_y
-// reference-signature shims on float input (one array per call): sequential float moments + order statistic, and
-// jnn_core over rm_outlierf(x); device pointers
-int launch_stat_f32(const float *x, int n, float *out3, hipStream_t st);
-int launch_jnn_f32(const float *x, int64_t n, const JnnP &p, int32_t *seg_x, int32_t *seg_y, uint32_t cap,
-                   uint32_t *n_segs, hipStream_t st);
+
+// ---- one launch per kernel, defined in the unit that holds the kernel (without relocatable device code a kernel is
+// launched from its own translation unit); the launchers above (stat_launch.hip) are made of these.  name: the profile
+// name of this launch, where it varies; a kernel's template arguments come as values (a combination nobody launches:
+// SGK_ERR_ARG); grid: workgroups, where the kernel does not take every read of the batch.
+// stat_lane.hip -- one read per lane, 64 per workgroup (k_median: a workgroup per read)
+int launch_k_moments(const char *name, int region, bool hist, hipStream_t st, const StatArgs &a);
+int launch_k_median(const char *name, int region, bool pa, bool flagged, hipStream_t st, const StatArgs &a);
+int launch_k_jnn(const char *name, hipStream_t st, const StatArgs &a, const JnnP &p);
+int launch_k_polya(hipStream_t st, const StatArgs &a);
+int launch_k_adaptor(hipStream_t st, const StatArgs &a, const AdaptP &p);
+// stat_wave.hip -- one read per wavefront, four per workgroup
+int launch_k_stat_wave(const char *name, int region, bool pa, uint32_t grid, hipStream_t st, const StatArgs &a);
+int launch_k_jnn_wave(const char *name, uint32_t grid, hipStream_t st, const StatArgs &a, const JnnP &p);
+int launch_k_polya_wave(hipStream_t st, const StatArgs &a);
+int launch_k_adaptor_wave(const char *name, uint32_t grid, hipStream_t st, const StatArgs &a, const AdaptP &p);
+// stat_long.hip -- k_long_chains<kind>, LC_PARTS workgroups per long read the batch can hold
+enum { LC_STAT = 0, LC_JNN = 1, LC_ADAPT = 2 };
+int launch_k_long_chains(const char *name, int kind, hipStream_t st, const StatArgs &a, const JnnP &p, const AdaptP &ap);
+
 
 }  // namespace sgk

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Model (CPU, numpy) of k_long_chains (sigtk_amd/csrc/stat_kernels.hip): a sequential float32 sum over a LONG read whose
+"""Model (CPU, numpy) of k_long_chains (sigtk_amd/csrc/stat_long.hip): a sequential float32 sum over a LONG read whose
 1024-term tiles are SUMMARISED independently by many wavefronts and COMPOSED by one.
 
 seqsum_proto.py models what a wave does with the 16 terms of a lane (surrogate starts inside the accumulator's binade,
