@@ -401,6 +401,48 @@ int sgk_svbzd_size(const int16_t *samples, const uint64_t *offsets, const uint32
 int sgk_svbzd_encode(const int16_t *samples, const uint64_t *offsets, const uint32_t *lengths, uint32_t n_reads,
                      uint8_t *blobs, const uint64_t *blob_offsets, const uint32_t *blob_lengths, void *stream);
 
+/* ---- text: the TSV rows of pa / event / event -c written on the device (csrc/text_kernels.hip) -------------------- */
+/* The batch's whole stdout body (header line excluded) as one dense byte range in file order, byte for byte what the
+ * reference's printf calls give (src/cfunc.c:16-61, 85-102: ids and len_raw_signal included, the empty line after every
+ * read of the long event form, zero-length events skipped in the compact form, ".\t.\t.\t." for a read without events).
+ * Two calls, because a byte's position depends on every byte in front of it:
+ *   sgk_text_measure   counts: row_offsets[r] = byte offset of read r's rows, row_offsets[n_reads] = the total
+ *   sgk_text_write     the characters: text[0 .. row_offsets[n_reads])
+ * both asynchronous on `stream`, with the same inputs and the same workspace (which carries the layout from the first
+ * call to the second).  pa text is made from the int16 samples (the float array is never written); event text from the
+ * arena sgk_event left on the device (ev_slots / events / n_events as there: a read whose events overflowed its slots is
+ * written with what fitted).  ids: the read ids, device pointers -- id r is bytes[offsets[r] .. offsets[r + 1]).
+ * n_items_capacity: the samples of the batch (pa: the sum of the lengths or more) or the slots of the arena
+ * (ev_slots[n_reads]); text may start at any byte address. */
+#define SGK_TEXT_PA 0
+#define SGK_TEXT_EVENT 1
+#define SGK_TEXT_EVENT_COMPACT 2
+typedef struct sgk_text_ids {
+    const uint8_t *bytes;
+    const uint32_t *offsets; /* n_reads + 1 */
+} sgk_text_ids_t;
+typedef struct sgk_text_status {
+    uint32_t overflow; /* 1: the text needed more than text_capacity bytes; nothing was written behind it */
+    uint32_t n_tiles;  /* tiles of 256 items the batch was cut into (diagnostic) */
+    uint64_t n_bytes;  /* row_offsets[n_reads] */
+} sgk_text_status_t;
+size_t sgk_text_workspace_bytes(int kind, uint32_t n_reads, uint64_t n_items_capacity);
+int sgk_text_measure(int kind, const sgk_batch_t *batch, const sgk_text_ids_t *ids, const uint64_t *ev_slots,
+                     const sgk_event_rec_t *events, const uint32_t *n_events, uint64_t *row_offsets, void *workspace,
+                     size_t workspace_bytes, void *stream);
+/* text_capacity is checked ON THE DEVICE (the total is not known on the host when the call is made): a tile of rows that
+ * would end behind it is not written and the workspace's status word says so. */
+int sgk_text_write(int kind, const sgk_batch_t *batch, const sgk_text_ids_t *ids, const uint64_t *ev_slots,
+                   const sgk_event_rec_t *events, const uint32_t *n_events, uint8_t *text, uint64_t text_capacity,
+                   void *workspace, size_t workspace_bytes, void *stream);
+/* after the caller has synchronised the stream: SGK_ERR_CAPACITY if the text did not fit, SGK_ERR_WORKSPACE if the
+ * workspace was sized for fewer items than the batch has (nothing was written then) */
+int sgk_text_status(const void *workspace, sgk_text_status_t *out);
+/* test entries: printf("%f") / "%ld" of n values, value i into slots48[48 * i ..), its byte count into lengths[i]
+ * (255 if the writer and its length-only form disagree); device pointers */
+int sgk_text_numbers_f32(const float *v, uint64_t n, uint8_t *slots48, uint8_t *lengths, void *stream);
+int sgk_text_numbers_i64(const int64_t *v, uint64_t n, uint8_t *slots48, uint8_t *lengths, void *stream);
+
 /* ---- synthetic reads (BASELINE configs 2-5) ---------------------------- */
 /* Deterministic counter-based generator, identical on host and device (integer only).
  * kind 0: DNA-like (mean dwell 9 samples); kind 1: RNA-like (mean dwell 36, adaptor +
@@ -491,6 +533,12 @@ typedef struct sgk_job sgk_job_t;
                                   * (src/events.c:491-501), so start_i is the sum of the lengths in front of event i: half
                                   * of SGK_JOB_EVENTS_COMPACT's bytes over PCIe, which is what `event -c` waits for */
 
+#define SGK_JOB_TEXT 4           /* submit flag, SGK_TOOL_PA and SGK_TOOL_EVENT (additive; sgk_job_set_ids first): the rows are
+                                  * written on the device (sgk_text_*; with _COMPACT or _LENGTHS the compact event grammar,
+                                  * else the long form) and the job downloads row_offsets and the text and nothing else --
+                                  * no pA floats, no event arrays.  sgk_job_text hands them out after sgk_job_wait, which
+                                  * returns SGK_ERR_CAPACITY for a read whose events overflowed its slots, as without the flag */
+
 typedef struct sgk_job_input {
     int16_t *samples;             /* pinned host (SGK_SIGNAL_INT16): read r at samples + offsets[r] */
     uint8_t *blobs;               /* pinned host (SGK_SIGNAL_SVBZD): blob r at blobs + blob_offsets[r] */
@@ -555,6 +603,16 @@ int sgk_job_output(const sgk_job_t *job, sgk_job_output_t *out);
  * the wave-per-read kernel redid -- sgk_long_status_t::n_timeouts of the job's last submit.  The records are right
  * either way; non-zero means the GPU did not dispatch a grid's workgroups the way the long path assumes (0.2.2). */
 uint32_t sgk_job_long_declined(const sgk_job_t *job);
+/* The read ids of the staged batch, between sgk_job_begin* and sgk_job_submit (arbitrary bytes, 0 - 65 535 per id; id r
+ * is bytes[offsets[r] .. offsets[r + 1]), offsets[0] = 0): copied into the job's pinned staging, uploaded with the batch. */
+int sgk_job_set_ids(sgk_job_t *job, const uint8_t *bytes, const uint32_t *offsets);
+typedef struct sgk_job_text {
+    const uint8_t *text;         /* pinned host: the rows of read r are text[row_offsets[r] .. row_offsets[r + 1]) */
+    const uint64_t *row_offsets; /* n_reads + 1 */
+    uint64_t n_bytes;            /* row_offsets[n_reads] */
+} sgk_job_text_t;
+/* after sgk_job_wait of a submit with SGK_JOB_TEXT; valid until the job's next sgk_job_begin */
+int sgk_job_text(const sgk_job_t *job, sgk_job_text_t *out);
 
 /* ---- per-read shims with the reference's own signatures (batch of one) ------------- */
 /* event_t / event_table exactly as src/sigtk.h:55-70 */

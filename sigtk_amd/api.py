@@ -176,10 +176,24 @@ class JobOutput(C.Structure):
                 ("ent", C.c_void_p), ("ent_over_raw", C.c_void_p), ("ent_over_delta", C.c_void_p)]
 
 
+class TextIds(C.Structure):      # sgk_text_ids_t (device pointers)
+    _fields_ = [("bytes", C.c_void_p), ("offsets", C.c_void_p)]
+
+
+class TextStatus(C.Structure):   # sgk_text_status_t
+    _fields_ = [("overflow", C.c_uint32), ("n_tiles", C.c_uint32), ("n_bytes", C.c_uint64)]
+
+
+class JobText(C.Structure):      # sgk_job_text_t
+    _fields_ = [("text", C.c_void_p), ("row_offsets", C.POINTER(C.c_uint64)), ("n_bytes", C.c_uint64)]
+
+
 TOOL_PA, TOOL_EVENT, TOOL_STAT, TOOL_JNN, TOOL_PREFIX, TOOL_ENT, TOOL_QTS = range(7)
 ENT_HIST_BYTES = 4 * (4 + 8192 + 4096 + 512)   # sizeof(sgk_ent_hist_t)
 SIGNAL_INT16, SIGNAL_SVBZD = 0, 1
 JOB_EVENTS_COMPACT = 1
+JOB_TEXT = 4             # pa / event: the rows are written on the device; wait() returns "text" and "row_offsets"
+TEXT_PA, TEXT_EVENT, TEXT_EVENT_COMPACT = 0, 1, 2
 JOB_EVENTS_LENGTHS = 2   # only the lengths come back; the starts are their running sums (events are contiguous from 0)
 
 STAT_DTYPE = np.dtype([("raw_mean", "<f4"), ("pa_mean", "<f4"), ("raw_std", "<f4"), ("pa_std", "<f4"),
@@ -204,6 +218,9 @@ ABI_SYMBOLS = [
     "sgk_job_create", "sgk_job_destroy", "sgk_job_device", "sgk_job_begin", "sgk_job_submit", "sgk_job_submit_qts",
     "sgk_job_wait",
     "sgk_job_output",
+    # the TSV rows written on the device (csrc/text_kernels.hip)
+    "sgk_text_workspace_bytes", "sgk_text_measure", "sgk_text_write", "sgk_text_status", "sgk_text_numbers_f32",
+    "sgk_text_numbers_i64", "sgk_job_set_ids", "sgk_job_text",
     # per-read shims with the reference's signatures (csrc/shims.hip)
     "sgk_jnn_raw", "sgk_jnn_pa", "sgk_jnnv2", "sgk_find_adaptor", "sgk_find_polya",
     "sgk_meanf", "sgk_meani16", "sgk_stdvf", "sgk_stdvi16", "sgk_medianf", "sgk_mediani16", "sgk_shim_status",
@@ -298,6 +315,17 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.sgk_job_wait.argtypes = [C.c_void_p]
     L.sgk_job_output.argtypes = [C.c_void_p, C.POINTER(JobOutput)]
     L.sgk_job_set_options.argtypes = [C.c_void_p, OE, OS]
+    L.sgk_job_set_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sgk_job_begin_zrec.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 5 + [C.POINTER(JobInput)]
+    L.sgk_job_text.argtypes = [C.c_void_p, C.POINTER(JobText)]
+    L.sgk_text_workspace_bytes.restype = C.c_size_t
+    L.sgk_text_workspace_bytes.argtypes = [C.c_int, C.c_uint32, C.c_uint64]
+    L.sgk_text_measure.argtypes = [C.c_int, C.POINTER(Batch), C.POINTER(TextIds)] + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]
+    L.sgk_text_write.argtypes = [C.c_int, C.POINTER(Batch), C.POINTER(TextIds)] + [C.c_void_p] * 4 + \
+                                [C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.sgk_text_status.argtypes = [C.c_void_p, C.POINTER(TextStatus)]
+    L.sgk_text_numbers_f32.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sgk_text_numbers_i64.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.sgk_event_host.argtypes = [C.POINTER(HostBatch), C.c_int, C.POINTER(EventsHost)]
     L.sgk_event_host_opt.argtypes = L.sgk_event_host.argtypes + [OE]
     L.sgk_events_host_free.argtypes = [C.POINTER(EventsHost)]
@@ -587,8 +615,38 @@ class Job:
         except Exception:   # interpreter shutdown: module globals may already be gone
             pass
 
-    def stage(self, signals, dig, off, rng, counts=None):
-        """sgk_job_begin + fill the pinned staging (int16 arrays, or svb-zd blobs when `counts` is given)"""
+    def set_ids(self, ids):
+        """sgk_job_set_ids: the read ids (bytes or str, one per read) of the batch staged last"""
+        raw = [i.encode() if isinstance(i, str) else bytes(i) for i in ids]
+        offs = np.zeros(len(raw) + 1, dtype=np.uint32)
+        np.cumsum([len(i) for i in raw], out=offs[1:])
+        blob = b"".join(raw)
+        check(self.L.sgk_job_set_ids(self.h, blob if blob else None, offs.ctypes.data), "sgk_job_set_ids")
+
+    def stage(self, signals, dig, off, rng, counts=None, ids=None):
+        """sgk_job_begin + fill the pinned staging (int16 arrays, or svb-zd blobs when `counts` is given); `ids`: the
+        read ids, for submits with JOB_TEXT"""
+        self._stage(signals, dig, off, rng, counts)
+        if ids is not None:
+            self.set_ids(ids)
+
+    def stage_zrec(self, records, lengths, sig_offset, sig_bytes, rec_room, dig, off, rng, ids=None):
+        """sgk_job_begin_zrec: `records` are zlib-compressed BLOW5 records (bytes) with an svb-zd signal blob at
+        sig_offset[r] (sig_bytes[r] long) of the inflated record, which is rec_room[r] bytes at most"""
+        n = len(records)
+        u32 = lambda x: np.ascontiguousarray(x, dtype=np.uint32)
+        lengths, sig_offset, sig_bytes, rec_room = u32(lengths), u32(sig_offset), u32(sig_bytes), u32(rec_room)
+        rbytes = u32([len(b) for b in records])
+        jin = JobInput()
+        check(self.L.sgk_job_begin_zrec(self.h, n, lengths.ctypes.data, rbytes.ctypes.data, sig_offset.ctypes.data,
+                                        sig_bytes.ctypes.data, rec_room.ctypes.data, C.byref(jin)), "sgk_job_begin_zrec")
+        for r in range(n):
+            jin.digitisation[r] = float(dig[r]); jin.offset[r] = float(off[r]); jin.range[r] = float(rng[r])
+            C.memmove(jin.blobs + jin.blob_offsets[r], records[r], len(records[r]))
+        if ids is not None:
+            self.set_ids(ids)
+
+    def _stage(self, signals, dig, off, rng, counts=None):
         n = len(signals)
         svb = counts is not None
         lengths = np.asarray(counts if svb else [len(x) for x in signals], dtype=np.uint32)
@@ -607,16 +665,18 @@ class Job:
     def launch(self, tool: int, rna: int = 0, pore: int = 0, flags: int = 0):
         """sgk_job_submit on the staged batch (asynchronous; may be repeated after wait())"""
         self._tool = tool
+        self._text = bool(flags & JOB_TEXT)
         check(self.L.sgk_job_submit(self.h, tool, rna, pore, flags), "sgk_job_submit")
 
     def launch_qts(self, bits: int, method: int, out_svb: bool):
         self._tool = TOOL_QTS
+        self._text = False
         self._qts_svb = out_svb
         check(self.L.sgk_job_submit_qts(self.h, bits, method, SIGNAL_SVBZD if out_svb else SIGNAL_INT16),
               "sgk_job_submit_qts")
 
-    def submit(self, tool: int, signals, dig, off, rng, rna: int = 0, pore: int = 0, flags: int = 0, counts=None):
-        self.stage(signals, dig, off, rng, counts)
+    def submit(self, tool: int, signals, dig, off, rng, rna: int = 0, pore: int = 0, flags: int = 0, counts=None, ids=None):
+        self.stage(signals, dig, off, rng, counts, ids)
         self.launch(tool, rna, pore, flags)
 
     def wait(self):
@@ -626,7 +686,14 @@ class Job:
         check(self.L.sgk_job_output(self.h, C.byref(o)), "sgk_job_output")
         n = o.n_reads
         res = {"n_reads": n, "lengths": _np_from(o.lengths, n, np.uint32).copy()}
-        if self._tool == TOOL_PA:
+        if getattr(self, "_text", False) and self._tool in (TOOL_PA, TOOL_EVENT):
+            t = JobText()
+            check(self.L.sgk_job_text(self.h, C.byref(t)), "sgk_job_text")
+            res["text"] = C.string_at(t.text, t.n_bytes) if t.n_bytes else b""
+            res["row_offsets"] = _np_from(t.row_offsets, n + 1, np.uint64)
+            if self._tool == TOOL_EVENT:
+                res["status"] = o.event_status
+        elif self._tool == TOOL_PA:
             res["pa"] = [_np_from(C.cast(C.addressof(o.pa.contents) + 4 * o.offsets[r], C.POINTER(C.c_float)),
                                   int(o.lengths[r]), np.float32).copy() if o.lengths[r] else np.zeros(0, np.float32)
                          for r in range(n)]

@@ -23,7 +23,7 @@ CLI_ASAN = os.path.join(PKG, "sigtk-amd-asan")
 
 HIP_SOURCES = ["api.hip", "api_stat.hip", "event_kernels.hip", "stat_launch.hip", "stat_lane.hip", "stat_wave.hip",
                "stat_long.hip", "misc_kernels.hip", "svb_kernels.hip", "inflate_kernels.hip", "ent_kernels.hip",
-               "qts_kernels.hip", "job.hip", "shims.hip"]
+               "qts_kernels.hip", "text_kernels.hip", "job.hip", "shims.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
                "-fhip-fp32-correctly-rounded-divide-sqrt", "-fPIC", "-shared", "-Wall",
                "-Wno-unused-function", "-Wno-bitwise-instead-of-logical", "-Wno-c++20-extensions", "-Wno-pass-failed"]
@@ -111,6 +111,7 @@ def build_cli(force: bool = False, verbose: bool = False) -> str:
         return ""
     deps = srcs + [os.path.join(HOST, f) for f in os.listdir(HOST) if f.endswith(".h")]
     deps.append(os.path.join(ROOT, "include", "sigtk_gpu.h"))
+    deps.append(os.path.join(CSRC, "text_format.h"))  # the device writer's number formatting, checked by `_textcheck`
     if not force and _newer(CLI, deps) and _newer(CLI, [LIB]):
         return CLI
     cmd = ["gcc", "-O2", "-std=c99", "-D_GNU_SOURCE", "-Wall", "-I", os.path.join(ROOT, "include"), "-o", CLI, *srcs,
@@ -129,6 +130,7 @@ def build_cli_asan(force: bool = False, verbose: bool = False) -> str:
     srcs = sorted(os.path.join(HOST, f) for f in os.listdir(HOST) if f.endswith(".c"))
     deps = srcs + [os.path.join(HOST, f) for f in os.listdir(HOST) if f.endswith(".h")]
     deps.append(os.path.join(ROOT, "include", "sigtk_gpu.h"))
+    deps.append(os.path.join(CSRC, "text_format.h"))
     if not os.path.exists(LIB):
         build_lib(verbose=verbose)
     if not force and _newer(CLI_ASAN, deps) and _newer(CLI_ASAN, [LIB]):

@@ -95,6 +95,15 @@ struct sgk_job {
     bool long_fetched = false;        // stat / jnn / prefix: the long-read header of the call is on its way to h_long
     uint32_t long_declined = 0;       // ... long reads the long path declined (n_timeouts of sgk_long_status_t), after wait
     int n_dense = 0;                  // arrays to fetch in sgk_job_wait once the dense total is known
+    // SGK_JOB_TEXT: the read ids (sgk_job_set_ids), the text workspace, the rows and their offsets
+    GrowPin h_idb, h_ido, h_roffs, h_text;
+    GrowDev d_idb, d_ido, d_roffs, d_text, d_tws;
+    bool have_ids = false;
+    bool text_written = false;        // the write pass was enqueued at submit, into the buffer earlier batches grew
+    int text_kind = 0;
+    size_t tws_bytes = 0, id_bytes = 0;
+    uint64_t text_bytes = 0;          // after wait: row_offsets[n_reads]
+    sgk_batch_t text_view;
     size_t ws_bytes = 0;
     int tool = -1, flags = 0;
     bool begun = false, submitted = false, ent_over = false;
@@ -256,6 +265,25 @@ static int job_begin(sgk_job_t *j, uint32_t n_reads, const uint32_t *lengths, in
     in->range = j->h_rng.as<double>();
     in->n_samples = j->n_samples;
     j->begun = true;
+    j->have_ids = false;
+    j->text_bytes = 0;
+    return SGK_OK;
+}
+
+int sgk_job_set_ids(sgk_job_t *j, const uint8_t *bytes, const uint32_t *offsets) {
+    if (!j || !j->begun || j->submitted || !offsets || offsets[0] != 0) return SGK_ERR_ARG;
+    const size_t nr = j->n_reads;
+    for (size_t r = 0; r < nr; ++r)
+        if (offsets[r + 1] < offsets[r] || offsets[r + 1] - offsets[r] > 65535u) return SGK_ERR_ARG;
+    if (offsets[nr] && !bytes) return SGK_ERR_ARG;
+    SGK_HIP_TRY(hipSetDevice(j->device));
+    int rc;
+    if ((rc = j->h_ido.ensure((nr + 1) * 4)) != SGK_OK) return rc;
+    if ((rc = j->h_idb.ensure((size_t)offsets[nr] + 16)) != SGK_OK) return rc;
+    memcpy(j->h_ido.p, offsets, (nr + 1) * 4);
+    if (offsets[nr]) memcpy(j->h_idb.p, bytes, offsets[nr]);
+    j->id_bytes = offsets[nr];
+    j->have_ids = true;
     return SGK_OK;
 }
 
@@ -407,9 +435,65 @@ __global__ __launch_bounds__(256) void k_gather_events(const sgk_event_rec_t *sr
     }
 }
 
+// SGK_JOB_TEXT: the write pass over the measured batch, into d_text as far as it reaches (checked on the device)
+static int job_text_write(sgk_job_t *j) {
+    const bool ev = j->text_kind != SGK_TEXT_PA;
+    const sgk_text_ids_t ids = {j->d_idb.as<uint8_t>(), j->d_ido.as<uint32_t>()};
+    return sgk_text_write(j->text_kind, &j->text_view, &ids, ev ? j->d_slots.as<uint64_t>() : nullptr,
+                          ev ? j->d_out[0].as<sgk_event_rec_t>() : nullptr, ev ? j->d_cnt.as<uint32_t>() : nullptr,
+                          j->d_text.as<uint8_t>(), j->d_text.cap, j->d_tws.p, j->tws_bytes, j->st);
+}
+
+// ids up, measure pass, row_offsets home; the write pass too when the job already owns a text buffer (sgk_job_wait
+// learns the total, grows the buffer and writes again if that one was too small -- the first batches of a job)
+static int job_text_submit(sgk_job_t *j, int kind, const sgk_batch_t *view, uint64_t n_items) {
+    const size_t nr = j->n_reads;
+    hipStream_t st = j->st;
+    int rc;
+    if ((rc = h2d(j->d_idb, j->h_idb, j->id_bytes, st)) != SGK_OK) return rc;
+    if ((rc = h2d(j->d_ido, j->h_ido, (nr + 1) * 4, st)) != SGK_OK) return rc;
+    j->tws_bytes = sgk_text_workspace_bytes(kind, j->n_reads, n_items);
+    if ((rc = j->d_tws.ensure(j->tws_bytes)) != SGK_OK) return rc;
+    if ((rc = j->d_roffs.ensure((nr + 1) * 8)) != SGK_OK) return rc;
+    j->text_kind = kind;
+    j->text_view = *view;
+    const bool ev = kind != SGK_TEXT_PA;
+    const sgk_text_ids_t ids = {j->d_idb.as<uint8_t>(), j->d_ido.as<uint32_t>()};
+    rc = sgk_text_measure(kind, view, &ids, ev ? j->d_slots.as<uint64_t>() : nullptr,
+                          ev ? j->d_out[0].as<sgk_event_rec_t>() : nullptr, ev ? j->d_cnt.as<uint32_t>() : nullptr,
+                          j->d_roffs.as<uint64_t>(), j->d_tws.p, j->tws_bytes, st);
+    if (rc != SGK_OK) return rc;
+    if ((rc = d2h(j->h_roffs, j->d_roffs, (nr + 1) * 8, st)) != SGK_OK) return rc;
+    j->text_written = false;
+    if (j->d_text.cap) {
+        if ((rc = job_text_write(j)) != SGK_OK) return rc;
+        j->text_written = true;
+    }
+    return SGK_OK;
+}
+
+// after the stream has drained: the total is known -- write (again) if the rows are not in d_text yet, fetch them
+static int job_text_fetch(sgk_job_t *j) {
+    const uint64_t total = j->h_roffs.as<uint64_t>()[j->n_reads];
+    int rc;
+    if (!j->text_written || total > j->d_text.cap) {
+        if ((rc = j->d_text.ensure((size_t)total)) != SGK_OK) return rc;
+        SGK_HIP_TRY(hipMemsetAsync(j->d_tws.p, 0, 4, j->st));  // the overflow flag of the attempt at submit
+        if ((rc = job_text_write(j)) != SGK_OK) return rc;
+    }
+    if ((rc = d2h(j->h_text, j->d_text, (size_t)total, j->st)) != SGK_OK) return rc;
+    SGK_HIP_TRY(hipStreamSynchronize(j->st));
+    sgk_text_status_t ts;
+    if ((rc = sgk_text_status(j->d_tws.p, &ts)) != SGK_OK) return rc;
+    j->text_bytes = total;
+    return SGK_OK;
+}
+
 int sgk_job_submit(sgk_job_t *j, int tool, int rna, int pore, int flags) {
     if (!j || !j->begun || j->submitted) return SGK_ERR_ARG;
     if (tool < SGK_TOOL_PA || tool > SGK_TOOL_ENT) return SGK_ERR_ARG;
+    const bool text = (flags & SGK_JOB_TEXT) != 0;
+    if (text && ((tool != SGK_TOOL_PA && tool != SGK_TOOL_EVENT) || !j->have_ids)) return SGK_ERR_ARG;
     SGK_HIP_TRY(hipSetDevice(j->device));
     j->tool = tool;
     j->flags = flags;
@@ -417,6 +501,10 @@ int sgk_job_submit(sgk_job_t *j, int tool, int rna, int pore, int flags) {
     hipStream_t st = j->st;
     int rc;
     if (nr == 0) {
+        if (text) {
+            if ((rc = j->h_roffs.ensure(8)) != SGK_OK) return rc;
+            j->h_roffs.as<uint64_t>()[0] = 0;
+        }
         j->submitted = true;
         return SGK_OK;
     }
@@ -426,6 +514,10 @@ int sgk_job_submit(sgk_job_t *j, int tool, int rna, int pore, int flags) {
     // ---- kernels + results
     switch (tool) {
         case SGK_TOOL_PA: {
+            if (text) {  // the rows are made from the int16 samples: no float array, on the device or over PCIe
+                if ((rc = job_text_submit(j, SGK_TEXT_PA, &view, j->n_samples)) != SGK_OK) return rc;
+                break;
+            }
             const size_t bytes = j->n_samples * sizeof(float);
             if ((rc = j->d_out[0].ensure(bytes)) != SGK_OK) return rc;
             if ((rc = sgk_pa(&view, j->d_out[0].as<float>(), st)) != SGK_OK) return rc;
@@ -463,6 +555,12 @@ int sgk_job_submit(sgk_job_t *j, int tool, int rna, int pore, int flags) {
                                  j->d_out[1].as<int32_t>(), j->d_cnt.as<uint32_t>(), j->d_ws.p, j->d_ws.cap, st, &j->st_opt);
             if (rc != SGK_OK) return rc;
             if (!ev && (rc = fetch_long_hdr(j, st)) != SGK_OK) return rc;
+            if (text) {  // rows straight from the arena: no counts, no dense arrays over PCIe
+                const int kind = (flags & (SGK_JOB_EVENTS_COMPACT | SGK_JOB_EVENTS_LENGTHS)) ? SGK_TEXT_EVENT_COMPACT : SGK_TEXT_EVENT;
+                if ((rc = job_text_submit(j, kind, &view, s)) != SGK_OK) return rc;
+                j->n_dense = 0;
+                break;
+            }
             if ((rc = d2h(j->h_cnt, j->d_cnt, nr * 4, st)) != SGK_OK) return rc;
             // the arena is capacity-sized (sgk_event_slots_for(n) slots per read): gather what was produced into dense ranges on the
             // device and download only that (sgk_job_wait fetches the arrays once the total is known)
@@ -599,7 +697,10 @@ int sgk_job_wait(sgk_job_t *j) {
         for (uint32_t r = 0; r < j->n_reads; ++r)
             if (ds[r] != 0) return SGK_ERR_FORMAT;
     }
-    if (j->tool == SGK_TOOL_EVENT || j->tool == SGK_TOOL_JNN) {
+    if ((j->flags & SGK_JOB_TEXT) && j->tool != SGK_TOOL_QTS) {
+        const int rc = job_text_fetch(j);
+        if (rc != SGK_OK) return rc;
+    } else if (j->tool == SGK_TOOL_EVENT || j->tool == SGK_TOOL_JNN) {
         const uint64_t total = j->h_doffs.as<uint64_t>()[j->n_reads];
         int rc;
         for (int k = 0; k < j->n_dense; ++k)
@@ -635,6 +736,15 @@ int sgk_job_wait(sgk_job_t *j) {
 
 uint32_t sgk_job_long_declined(const sgk_job_t *j) { return j ? j->long_declined : 0u; }
 
+int sgk_job_text(const sgk_job_t *j, sgk_job_text_t *out) {
+    if (!j || !out) return SGK_ERR_ARG;
+    if (!(j->flags & SGK_JOB_TEXT) || (j->tool != SGK_TOOL_PA && j->tool != SGK_TOOL_EVENT)) return SGK_ERR_ARG;
+    out->text = j->h_text.as<uint8_t>();
+    out->row_offsets = j->h_roffs.as<uint64_t>();
+    out->n_bytes = j->n_reads ? j->text_bytes : 0;
+    return SGK_OK;
+}
+
 int sgk_job_output(const sgk_job_t *j, sgk_job_output_t *out) {
     if (!j || !out) return SGK_ERR_ARG;
     memset(out, 0, sizeof *out);
@@ -642,6 +752,10 @@ int sgk_job_output(const sgk_job_t *j, sgk_job_output_t *out) {
     out->offsets = j->h_offsets.as<uint64_t>();
     out->lengths = j->h_lengths.as<uint32_t>();
     out->decode_status = (j->fmt == SGK_SIGNAL_SVBZD || j->fmt == SGK_SIGNAL_ZREC) ? j->h_dstat.as<uint32_t>() : nullptr;
+    if ((j->flags & SGK_JOB_TEXT) && (j->tool == SGK_TOOL_PA || j->tool == SGK_TOOL_EVENT)) {
+        out->event_status = j->ev_status;  // the results are the rows: sgk_job_text
+        return SGK_OK;
+    }
     switch (j->tool) {
         case SGK_TOOL_PA:
             out->pa = j->h_out[0].as<float>();

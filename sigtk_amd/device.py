@@ -352,3 +352,87 @@ def inflate(streams, caps=None, device: Optional[torch.device] = None):
     st = d_st.cpu().numpy()[:n]
     kept = [out[int(out_off[r]):int(out_off[r]) + min(int(olen[r]), int(caps_a[r]))].tobytes() for r in range(n)]
     return kept, olen, st
+
+
+# ---------------------------------------------------------------------- TSV rows written on the device (sgk_text_*)
+
+class TextWriter:
+    """sgk_text_measure + sgk_text_write over one resident batch: ids, workspace and row offsets on the device.
+
+    kind: api.TEXT_PA (rows from the batch's int16 samples) or api.TEXT_EVENT / api.TEXT_EVENT_COMPACT (rows from the
+    arena a device.event() call filled).  measure() and write() only enqueue; status() synchronises."""
+
+    def __init__(self, b: DeviceReads, ids, kind: int, arena: Optional[EventArena] = None):
+        L = api.load_library()
+        dev = b.samples.device
+        raw = [i.encode() if isinstance(i, str) else bytes(i) for i in ids]
+        assert len(raw) == b.n_reads
+        offs = np.zeros(b.n_reads + 1, dtype=np.int64)
+        np.cumsum([len(i) for i in raw], out=offs[1:])
+        blob = np.frombuffer(b"".join(raw) + b"\0" * 16, dtype=np.uint8).copy()
+        self.b, self.kind, self.arena = b, int(kind), arena
+        self.id_bytes = torch.from_numpy(blob).to(dev)
+        self.id_offs = torch.from_numpy(offs.astype(np.int32)).to(dev)
+        self.ids = api.TextIds(_ptr(self.id_bytes), _ptr(self.id_offs))
+        items = b.n_samples if kind == api.TEXT_PA else arena.n_slots
+        self.ws_bytes = int(L.sgk_text_workspace_bytes(self.kind, b.n_reads, items))
+        self.ws = torch.zeros(self.ws_bytes, dtype=torch.uint8, device=dev)
+        self.row_offsets = torch.zeros(b.n_reads + 1, dtype=torch.int64, device=dev)
+
+    def _arena_ptrs(self):
+        a = self.arena
+        return (_ptr(a.slots), _ptr(a.events), _ptr(a.n_events)) if a is not None else (None, None, None)
+
+    def measure(self) -> None:
+        view = self.b.view()
+        api.check(api.load_library().sgk_text_measure(self.kind, C.byref(view), C.byref(self.ids), *self._arena_ptrs(),
+                                                      _ptr(self.row_offsets), _ptr(self.ws), self.ws_bytes, _stream_ptr()),
+                  "sgk_text_measure")
+
+    def write(self, text: torch.Tensor, capacity: Optional[int] = None) -> None:
+        """text: uint8 tensor (or a view of one starting at any byte); capacity defaults to its length"""
+        view = self.b.view()
+        api.check(api.load_library().sgk_text_write(self.kind, C.byref(view), C.byref(self.ids), *self._arena_ptrs(),
+                                                    _ptr(text), int(text.numel() if capacity is None else capacity),
+                                                    _ptr(self.ws), self.ws_bytes, _stream_ptr()), "sgk_text_write")
+
+    def status(self):
+        """-> (return code of sgk_text_status: 0 or api.SGK_ERR_CAPACITY, api.TextStatus); synchronises"""
+        torch.cuda.synchronize()
+        st = api.TextStatus()
+        rc = api.load_library().sgk_text_status(_ptr(self.ws), C.byref(st))
+        if rc not in (api.SGK_OK, api.SGK_ERR_CAPACITY):
+            api.check(rc, "sgk_text_status")
+        return rc, st
+
+    def run(self) -> bytes:
+        """measure, allocate exactly, write -> the rows as bytes (and self.row_offsets_host)"""
+        self.measure()
+        torch.cuda.synchronize()
+        self.row_offsets_host = self.row_offsets.cpu().numpy().astype(np.uint64)
+        total = int(self.row_offsets_host[-1])
+        text = torch.zeros(max(total, 1), dtype=torch.uint8, device=self.b.samples.device)
+        self.write(text, total)
+        rc, _ = self.status()
+        api.check(rc, "sgk_text_write")
+        return text[:total].cpu().numpy().tobytes()
+
+
+def text_numbers(values: np.ndarray):
+    """sgk_text_numbers_f32 / _i64 (by dtype): printf("%f") / "%ld" of every value, made on the device
+    -> (uint8 array [n, 48] of the slots, filled with '#' beforehand; uint8 array [n] of the byte counts)"""
+    L = api.load_library()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    values = np.ascontiguousarray(values)
+    n = values.size
+    if values.dtype == np.float32:
+        d_v = torch.from_numpy(values.view(np.int32)).to(dev)
+        fn = L.sgk_text_numbers_f32
+    else:
+        d_v = torch.from_numpy(values.astype(np.int64)).to(dev)
+        fn = L.sgk_text_numbers_i64
+    slots = torch.full((max(n, 1) * 48,), 35, dtype=torch.uint8, device=dev)
+    lens = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
+    api.check(fn(_ptr(d_v), n, _ptr(slots), _ptr(lens), _stream_ptr()), "sgk_text_numbers")
+    torch.cuda.synchronize()
+    return slots.cpu().numpy().reshape(-1, 48)[:n], lens.cpu().numpy()[:n]

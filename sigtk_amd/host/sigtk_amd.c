@@ -29,6 +29,7 @@
 
 #include "blow5.h"
 #include "fmt.h"
+#include "../csrc/text_format.h"
 #include "sigtk_gpu.h"
 
 #define SIGTK_VERSION "0.2.0" /* the reference version whose CLI this mirrors (src/sigtk.h:11) */
@@ -312,6 +313,9 @@ typedef struct batch {
     int svb;        /* signal staged as svb-zd blobs (GPU decode) */
     int zrec;       /* whole zlib records staged: inflated and decoded on the GPU */
     int last;       /* sentinel: no more batches */
+    uint8_t *id_blob;   /* --gpu-text: the batch's read ids back to back, id r at id_offs[r] .. id_offs[r + 1] */
+    uint32_t *id_offs;
+    uint64_t id_blob_cap, id_offs_cap;
     struct batch *next;
 } batch_t;
 
@@ -359,6 +363,8 @@ static batch_t *q_try_pop(queue_t *q) {
 typedef struct {
     b5_file_t *f;
     int mode, nthreads, host_decode;
+    int gpu_text;        /* --gpu-text (pa / event, whole-file mode): the rows come from the GPU as text */
+    uint64_t text_bytes; /* ... their bytes over PCIe */
     int zrec;            /* records go to the GPU as they sit in the file (zlib records, svb-zd signal, fixed-size auxiliary fields) */
     int64_t aux_bytes;   /* ... the bytes of a record's auxiliary fields then */
     opt_t opt;
@@ -483,6 +489,34 @@ static void batch_launch(pipe_t *P, batch_t *b) {
         case MODE_JNN: tool = SGK_TOOL_JNN; break;
         case MODE_ENT: tool = SGK_TOOL_ENT; break;
         default: break;
+    }
+    if (P->gpu_text) {
+        /* the ids travel with the batch; the job hands back the rows as the reference prints them */
+        uint64_t total = 0;
+        for (uint32_t i = 0; i < b->n; i++) total += b->recs[i].v.id_len;
+        if (total > 0xffffffffull) {
+            ERROR("cmain", "%s", "the read ids of one batch exceed 4 GB: use a smaller --batch-samples");
+            die_now();
+        }
+        if ((uint64_t)b->n + 1 > b->id_offs_cap) {
+            b->id_offs_cap = (uint64_t)b->n + 1;
+            b->id_offs = (uint32_t *)realloc(b->id_offs, sizeof(uint32_t) * b->id_offs_cap);
+        }
+        if (total + 1 > b->id_blob_cap) {
+            b->id_blob_cap = total + 1;
+            b->id_blob = (uint8_t *)realloc(b->id_blob, b->id_blob_cap);
+        }
+        if (!b->id_offs || !b->id_blob) die_mem();
+        uint32_t o = 0;
+        for (uint32_t i = 0; i < b->n; i++) {
+            b->id_offs[i] = o;
+            memcpy(b->id_blob + o, b->recs[i].v.read_id, b->recs[i].v.id_len);
+            o += (uint32_t)b->recs[i].v.id_len;
+        }
+        b->id_offs[b->n] = o;
+        rc = sgk_job_set_ids(b->job, b->id_blob, b->id_offs);
+        if (rc != SGK_OK) gpu_fail("sgk_job_set_ids", rc);
+        flags |= SGK_JOB_TEXT;
     }
     if (P->mode == MODE_QTS)
         rc = sgk_job_submit_qts(b->job, P->q_bits, P->q_method, P->f->signal_press == 1 ? SGK_SIGNAL_SVBZD : SGK_SIGNAL_INT16);
@@ -773,6 +807,23 @@ static void *writer_main(void *arg) {
         if (rc != SGK_OK) gpu_fail("sgk_job_output", rc);
         double t1 = realtime();
         P->t_wait += t1 - t0;
+        if (P->gpu_text) {
+            /* the batch's rows arrived as text: one buffered write, nothing to format */
+            sgk_job_text_t tx;
+            rc = sgk_job_text(b->job, &tx);
+            if (rc != SGK_OK) gpu_fail("sgk_job_text", rc);
+            if (tx.n_bytes && fwrite(tx.text, 1, tx.n_bytes, P->out_fp) != tx.n_bytes) {
+                ERROR("writer", "%s", "write to the output failed");
+                die_now();
+            }
+            P->text_bytes += tx.n_bytes;
+            P->t_write += realtime() - t1;
+            b->n = 0;
+            b->raw_len = 0;
+            b->bytes = 0;
+            q_push(&P->free_q, b);
+            continue;
+        }
         /* contiguous chunks of reads with about equal sample counts; a few per thread for balance */
         uint32_t nchunks = (uint32_t)wthreads * 4;
         if (nchunks > b->n) nchunks = b->n;
@@ -934,6 +985,9 @@ static void run_pipeline(pipe_t *P, int n_gpus, double t_init) {
                 "stage+submit %.3f s | wait-for-GPU %.3f s, format %.3f s, write %.3f s | HIP init %.3f s, job create %.3f s\n",
                 (unsigned long)P->n_reads, (unsigned long)P->n_samples, P->nthreads, n_gpus, P->t_read, P->t_parse,
                 P->t_stage, P->t_wait, P->t_format, P->t_write, t_init, t_jobs);
+    if (getenv("SGK_CLI_TIMING") && P->gpu_text)
+        fprintf(stderr, "[sigtk-amd] --gpu-text: %lu bytes of rows over PCIe (formatted on the GPU; no pA floats / event arrays)\n",
+                (unsigned long)P->text_bytes);
     /* The process is about to leave through _exit (main): the jobs' pinned and device buffers go with it.  Releasing
      * them one hipHostFree / hipFree at a time costs more than a small input's whole pipeline (SGK_CLI_TIMING shows
      * it), so they are only released when asked to (leak checkers: SGK_CLI_FREE=1). */
@@ -942,6 +996,7 @@ static void run_pipeline(pipe_t *P, int n_gpus, double t_init) {
             sgk_job_destroy(pool[i].job);
             for (uint32_t k = 0; k < pool[i].cap; k++) free(pool[i].recs[k].scratch);
             free(pool[i].recs); free(pool[i].raw); free(pool[i].lengths); free(pool[i].blob_bytes); free(pool[i].sig_off); free(pool[i].sig_len); free(pool[i].room);
+            free(pool[i].id_blob); free(pool[i].id_offs);
         }
         free(pool);
     }
@@ -981,7 +1036,7 @@ static struct option long_options[] = {
     {"output", required_argument, 0, 'o'},  {"print-stat", no_argument, 0, 0},   {"no-header", no_argument, 0, 'n'},
     {"compact", no_argument, 0, 'c'},       {"gpus", required_argument, 0, 0},   {"batch-samples", required_argument, 0, 0},
     {"threads", required_argument, 0, 't'}, {"host-decode", no_argument, 0, 0},  {"host-inflate", no_argument, 0, 0},
-    {0, 0, 0, 0}};
+    {"gpu-text", no_argument, 0, 0},        {0, 0, 0, 0}};
 
 static int cmain(int argc, char *argv[], const char *mode_s) {
     /* `ent` has its own front end in the reference (src/ent.c:63-105): only -h/-V (and --no-header) are options,
@@ -992,7 +1047,7 @@ static int cmain(int argc, char *argv[], const char *mode_s) {
     FILE *fp_help = stderr;
     int8_t hdr = 1;
     opt_t opt = {0, 0, 0, 0};
-    int n_gpus = 1, nthreads = 0, host_decode = 0, host_inflate = 0, batch_set = 0;
+    int n_gpus = 1, nthreads = 0, host_decode = 0, host_inflate = 0, batch_set = 0, gpu_text = 0;
     /* default batch: small (16 M samples) where the GPU stage is short -- a job's buffers are then cheap to set up
      * and the host stages overlap sooner; 64 M for jnn / prefix, whose one-read-per-lane kernels take as long for
      * a small batch as for a large one */
@@ -1021,6 +1076,8 @@ static int cmain(int argc, char *argv[], const char *mode_s) {
             host_decode = 1;
         } else if (c == 0 && longindex == 11) {
             host_inflate = 1;
+        } else if (c == 0 && longindex == 12) {
+            gpu_text = 1;
         }
     }
     if (is_ent && (argc - optind != 1 || fp_help == stdout)) {
@@ -1044,6 +1101,7 @@ static int cmain(int argc, char *argv[], const char *mode_s) {
         fprintf(fp_help, "   -t, --threads INT          host threads for inflating records / formatting rows [auto]\n");
         fprintf(fp_help, "   --host-decode              decode svb-zd signals on the host instead of the GPU\n");
         fprintf(fp_help, "   --host-inflate             inflate zlib records on the host threads instead of the GPU\n");
+        fprintf(fp_help, "   --gpu-text                 pa / event, whole-file mode: format the rows on the GPU and fetch them as text\n");
         exit(fp_help == stdout ? EXIT_SUCCESS : EXIT_FAILURE);
     }
 
@@ -1120,6 +1178,9 @@ static int cmain(int argc, char *argv[], const char *mode_s) {
     P.limit_bytes = batch_samples;
     P.ids = argv + optind + 1;
     P.n_ids = argc - optind - 1;
+    /* rows as text from the GPU: the three large-output grammars, when the whole file is read in order (with read ids
+     * on the command line, and for the other subtools, the option changes nothing) */
+    P.gpu_text = gpu_text && (mode == MODE_PA || mode == MODE_EVENT) && P.n_ids == 0;
     run_pipeline(&P, n_gpus, t_init);
     fflush(stdout);
     b5_close(f);
@@ -1135,6 +1196,7 @@ static struct option qts_long_options[] = {
     {"verbose", required_argument, 0, 'v'}, {"help", no_argument, 0, 'h'},   {"version", no_argument, 0, 'V'},
     {"output", required_argument, 0, 'o'},  {"bits", required_argument, 0, 'b'}, {"method", required_argument, 0, 'm'},
     {"gpus", required_argument, 0, 0},      {"batch-samples", required_argument, 0, 0}, {"threads", required_argument, 0, 't'},
+    {"gpu-text", no_argument, 0, 0}, /* accepted, changes nothing: qts writes records, not rows */
     {0, 0, 0, 0}};
 
 static int qtsmain(int argc, char *argv[]) {
@@ -1383,6 +1445,82 @@ static int fmtcheckmain(int argc, char *argv[]) {
     return bad ? 1 : 0;
 }
 
+/* hidden helper for tests: csrc/text_format.h (the header the device-side writer compiles for gfx950), compiled here
+ * by the host compiler, against snprintf -- the bytes and the length-only form */
+static uint64_t textcheck_f32(uint32_t w, const char *want, uint64_t *bad) {
+    char a[64], b[512];
+    float f;
+    memcpy(&f, &w, 4);
+    memset(a, '#', sizeof a);
+    const int n = sgk_tf_f32(a, f);
+    const int m = snprintf(b, sizeof b, "%f", f);
+    const int ok = n == m && n <= SGK_TF_F32_MAX_BYTES && memcmp(a, b, (size_t)m) == 0 && a[n] == '#' &&
+                   sgk_tf_f32_len(f) == m && (!want || strcmp(b, want) == 0);
+    if (!ok && (*bad)++ < 10) printf("MISMATCH %08x: %.*s (%d, length form %d) vs %s\n", w, n > 0 && n < 64 ? n : 0, a, n, sgk_tf_f32_len(f), b);
+    return 1;
+}
+static uint64_t textcheck_i64(int64_t v, uint64_t *bad) {
+    char a[64], b[64];
+    memset(a, '#', sizeof a);
+    const int n = sgk_tf_i64(a, v);
+    const int m = snprintf(b, sizeof b, "%ld", (long)v);
+    const int ok = n == m && memcmp(a, b, (size_t)m) == 0 && a[n] == '#' && sgk_tf_i64_len(v) == m;
+    if (!ok && (*bad)++ < 10) printf("MISMATCH int %ld: length %d, length form %d vs %s\n", (long)v, n, sgk_tf_i64_len(v), b);
+    if (v >= 0) {
+        memset(a, '#', sizeof a);
+        const int nu = sgk_tf_u64(a, (uint64_t)v);
+        if ((nu != m || memcmp(a, b, (size_t)m) != 0 || a[nu] != '#' || sgk_tf_u64_len((uint64_t)v) != m) && (*bad)++ < 10)
+            printf("MISMATCH unsigned %ld\n", (long)v);
+    }
+    return 1;
+}
+static int textcheckmain(int argc, char *argv[]) {
+    /* _textcheck [stride [first last]]: every stride-th float bit pattern in [first, last] (defaults: all), then the
+     * fixed cases: powers of two and their neighbours, ties and carries, both sides of 1e15, FLT_MAX, denormals, zeros,
+     * infinities, NaNs of both signs; "%ld" on 0, +-1, powers of ten +- 1 and the ends of the range */
+    const uint32_t stride = argc > 1 ? (uint32_t)strtoul(argv[1], NULL, 10) : 9973u;
+    const uint64_t first = argc > 3 ? strtoull(argv[2], NULL, 0) : 0, last = argc > 3 ? strtoull(argv[3], NULL, 0) : 0xffffffffull;
+    uint64_t bad = 0, n = 0;
+    for (uint64_t u = first; u <= last; u += stride ? stride : 1) n += textcheck_f32((uint32_t)u, NULL, &bad);
+    for (uint32_t e = 0; e < 256; e++)
+        for (int d = -2; d <= 2; d++)
+            for (uint32_t sgn = 0; sgn < 2; sgn++) n += textcheck_f32(((e << 23) + (uint32_t)d) ^ (sgn << 31), NULL, &bad);
+    for (int m = 1; m <= 30; m++)
+        for (int k = 1; k < 4000; k += 2) {
+            const float f = (float)k / (float)(1u << m);
+            const float g[4] = {f, -f, f + 123456.0f, 999999.0f + f};
+            for (int t = 0; t < 4; t++) {
+                uint32_t w;
+                memcpy(&w, &g[t], 4);
+                n += textcheck_f32(w, NULL, &bad);
+            }
+        }
+    n += textcheck_f32(0x3c000000u, "0.007812", &bad);                 /* 2^-7 = 0.0078125: the tie goes to even */
+    n += textcheck_f32(0x58635fa8u, "999999919882240.000000", &bad);
+    n += textcheck_f32(0x58635fa9u, "999999986991104.000000", &bad);   /* the last float below 1e15 */
+    n += textcheck_f32(0x58635faau, "1000000054099968.000000", &bad);  /* the first one above: the multi-limb path */
+    n += textcheck_f32(0xd8635faau, "-1000000054099968.000000", &bad);
+    n += textcheck_f32(0x7f7fffffu, "340282346638528859811704183484516925440.000000", &bad);
+    n += textcheck_f32(0xff7fffffu, "-340282346638528859811704183484516925440.000000", &bad);
+    n += textcheck_f32(0x00000000u, "0.000000", &bad);
+    n += textcheck_f32(0x80000000u, "-0.000000", &bad);
+    n += textcheck_f32(0x7f800000u, "inf", &bad);
+    n += textcheck_f32(0xff800000u, "-inf", &bad);
+    n += textcheck_f32(0x7fc00000u, "nan", &bad);
+    n += textcheck_f32(0xffc00000u, "-nan", &bad);
+    n += textcheck_f32(0x7f800001u, "nan", &bad);
+    n += textcheck_f32(0xffffffffu, "-nan", &bad);
+    for (uint32_t w = 0; w < 64; w++) n += textcheck_f32(w, NULL, &bad) + textcheck_f32(0x007fffffu - w, NULL, &bad) + textcheck_f32(0x80000000u | w, NULL, &bad);
+    n += textcheck_i64(0, &bad);
+    int64_t p10 = 1;
+    for (int k = 0; k < 19; k++, p10 *= 10)
+        for (int d = -1; d <= 1; d++) n += textcheck_i64(p10 + d, &bad) + textcheck_i64(-(p10 + d), &bad);
+    const int64_t iv[] = {12345, -98765, 2147483647LL, -2147483648LL, 4294967295LL, 4294967296LL, 9223372036854775807LL, (-9223372036854775807LL - 1)};
+    for (size_t i = 0; i < sizeof iv / sizeof iv[0]; i++) n += textcheck_i64(iv[i], &bad);
+    printf("checked %lu values, %lu mismatches\n", (unsigned long)n, (unsigned long)bad);
+    return bad ? 1 : 0;
+}
+
 /* ------------------------------------------------------------------ main (src/main.c:49-123) */
 
 static void print_usage(FILE *fp) {
@@ -1415,6 +1553,8 @@ int main(int argc, char *argv[]) {
         return dumpmain(argc - 1, argv + 1);
     } else if (strcmp(argv[1], "_fmtcheck") == 0) {
         return fmtcheckmain(argc - 1, argv + 1);
+    } else if (strcmp(argv[1], "_textcheck") == 0) {
+        return textcheckmain(argc - 1, argv + 1);
     } else if (strcmp(argv[1], "--version") == 0 || strcmp(argv[1], "-V") == 0) {
         fprintf(stdout, "sigtk %s\n", SIGTK_VERSION);
         exit(EXIT_SUCCESS);

@@ -9,7 +9,12 @@ base file the large one is made of.
 The large file is `copies` concatenations of the records of a base file (4 000 synthetic reads, written by
 sigtk_amd.blow5 as slow5lib would write them): what the CLI must print for it is the header line and `copies` times the
 body it prints for the base file -- which is compared, byte for byte, with the reference binary's output on the base file
-(the 1 / copies subsample VERDICT asked for), and with an md5 of the large run's stdout."""
+(the 1 / copies subsample VERDICT asked for), and with an md5 of the large run's stdout.
+
+`--tools` takes any `;`-separated list of subtool command lines, `event` (long form) and `pa` included: their output is
+70 B per event / 10 B per sample, so size the file for the sink (e.g. `--tools "event;pa" --base-reads 1000 --copies 10`:
+1e9 samples, ~10 GB of pa text; the base file's whole output is held in memory once).  `--extra --gpu-text` runs the rows
+through the device-side writer; the JSON records it ("cli_extra", "gpu_text") and the text bytes the CLI reports."""
 import argparse
 import hashlib
 import json
@@ -48,6 +53,9 @@ def stages(stderr):
                 out["reads"], out["samples"], out["threads"], out["gpus"] = (int(x) for x in m.groups())
             for name, v in re.findall(r"([A-Za-z+\- ]+?) ([0-9.]+) s", ln.split(":", 1)[1]):
                 out[name.strip(" |,")] = float(v)
+        m = re.match(r"\[sigtk-amd\] --gpu-text: (\d+) bytes of rows over PCIe", ln)
+        if m:
+            out["text_bytes_over_pcie"] = int(m.group(1))
     return out
 
 
@@ -75,7 +83,8 @@ def main():
         replicate(base, big, a.copies)
     out = {"base_file_mb": round(os.path.getsize(base) / 1e6, 1), "big_file_mb": round(os.path.getsize(big) / 1e6, 1),
            "copies": a.copies, "reads": a.base_reads * a.copies, "samples": a.base_reads * a.copies * a.read_len,
-           "host_cpus": os.cpu_count(), "made_in_s": round(time.perf_counter() - t0, 1), "cli_extra": a.extra, "tools": {}}
+           "host_cpus": os.cpu_count(), "made_in_s": round(time.perf_counter() - t0, 1), "cli_extra": a.extra,
+           "gpu_text": "--gpu-text" in a.extra.split(), "tools": {}}
     env = dict(os.environ, SGK_CLI_TIMING="1")
     targ = (["-t", str(a.threads)] if a.threads else []) + (["--gpus", str(a.gpus)] if a.gpus != 1 else []) + a.extra.split()
     for tool in [t.split() for t in a.tools.split(";")]:
