@@ -443,6 +443,67 @@ int sgk_text_status(const void *workspace, sgk_text_status_t *out);
 int sgk_text_numbers_f32(const float *v, uint64_t n, uint8_t *slots48, uint8_t *lengths, void *stream);
 int sgk_text_numbers_i64(const int64_t *v, uint64_t n, uint8_t *slots48, uint8_t *lengths, void *stream);
 
+/* ---- sref: the synthetic reference signal of a sequence (csrc/sref_kernels.hip) -------------------------------------- */
+/* `sigtk sref` (src/sref.c:100-210): position j of a strand's row is level_mean[rank(bases j .. j + k)], rank with the
+ * first base most significant, A/a 0, C/c 1, G/g 2, T/t 3 and every other byte 0; the '-' strand is the reverse
+ * complement, where the complement of a non-ACGT byte is T.  The pore model is an argument: `levels` holds level_mean by
+ * k-mer rank, 4^k floats.  The library carries no model.
+ * The unit of work is a span: signal positions [first, first + count) of one strand of one sequence of l = seq_len
+ * bases, whose row has ref_len = l + 1 - k values.  The caller uploads only the forward bases a span needs: forward base
+ * f sits at bases[base_offset + (f - base_pos0)].  A '+' span needs forward bases [first, first + count + k - 1), a '-'
+ * span [l - first - count - k + 1, l - first).  A base in front of a span's window or outside `bases` reads as 'A' (never
+ * out of bounds); behind a window that is too small the kernel reads what follows it in `bases`.
+ * Text of a span: the row head "name \t l \t strand \t ref_len \t" if first == 0, then every value as printf("%f")
+ * followed by ',' -- position ref_len - 1, the row's last, by '\n'.  A row with ref_len <= 0 is one span with count 0:
+ * its head and no line end, as the reference prints it.  The spans of a row, in order, concatenate to the reference's row.
+ * measure / write / status work as for sgk_text_* (same workspace in both calls, capacity checked on the device,
+ * sgk_text_status afterwards); names: the sequence names, indexed by span.seq. */
+typedef struct sgk_sref_span {
+    uint64_t base_offset; /* where forward base base_pos0 of this span's sequence sits in `bases` */
+    uint64_t base_pos0;
+    uint32_t seq_len;      /* l, as printed */
+    uint32_t first, count; /* signal positions [first, first + count) of this strand's row */
+    uint32_t seq;          /* index into the names */
+    uint8_t strand;        /* 0 '+', 1 '-' */
+    uint8_t reserved[7];
+} sgk_sref_span_t;
+typedef struct sgk_sref_batch {
+    const uint8_t *bases; /* device, ASCII as read from the file */
+    uint64_t n_bases;
+    const sgk_sref_span_t *spans; /* device */
+    uint32_t n_spans;
+    uint32_t k;          /* 1..6 */
+    const float *levels; /* device, 4^k floats: level_mean by k-mer rank */
+    uint32_t table_in_lds; /* EXPERIMENTAL, leave 0: text only, identical output.  0 the per-call table of the levels' text
+                            * is read from global memory through L2; 1 every workgroup keeps a copy in LDS.  Kept until the
+                            * two are timed (profiles/sref.md); the slower one and this field then go */
+    uint32_t reserved;
+} sgk_sref_batch_t;
+/* out[out_offsets[s] + i] = the level of position first + i of span s (device pointers) */
+int sgk_sref_levels(const sgk_sref_batch_t *batch, const uint64_t *out_offsets, float *out, void *stream);
+size_t sgk_sref_text_workspace_bytes(uint32_t n_spans, uint64_t n_positions_capacity);
+int sgk_sref_text_measure(const sgk_sref_batch_t *batch, const sgk_text_ids_t *names, uint64_t *row_offsets /* n_spans + 1 */,
+                          void *workspace, size_t workspace_bytes, void *stream);
+int sgk_sref_text_write(const sgk_sref_batch_t *batch, const sgk_text_ids_t *names, uint8_t *text, uint64_t text_capacity,
+                        void *workspace, size_t workspace_bytes, void *stream);
+/* Host pipe for callers without device memory of their own (the CLI): batches of spans in, their text out.  Two slots;
+ * a slot goes begin -> (the caller fills the pinned staging) -> submit -> wait.  submit uploads, measures, sizes the
+ * text buffers, writes and starts the download; it returns once the size is known.  wait returns the slot's text in
+ * pinned host memory, valid until the slot's next begin.  `levels` is a host pointer here, 4^k floats. */
+typedef struct sgk_sref_pipe sgk_sref_pipe_t;
+typedef struct sgk_sref_stage {
+    uint8_t *bases;          /* n_bases bytes */
+    sgk_sref_span_t *spans;  /* n_spans; base_offset relative to `bases` */
+    uint8_t *name_bytes;     /* name i is name_bytes[name_offsets[i] .. name_offsets[i + 1]) */
+    uint32_t *name_offsets;  /* n_names + 1 */
+} sgk_sref_stage_t;
+int sgk_sref_pipe_create(int device, const float *levels, uint32_t k, sgk_sref_pipe_t **out);
+void sgk_sref_pipe_destroy(sgk_sref_pipe_t *pipe);
+int sgk_sref_pipe_begin(sgk_sref_pipe_t *pipe, int slot, uint64_t n_bases, uint32_t n_spans, uint32_t n_names,
+                        uint64_t name_bytes, sgk_sref_stage_t *out);
+int sgk_sref_pipe_submit(sgk_sref_pipe_t *pipe, int slot);
+int sgk_sref_pipe_wait(sgk_sref_pipe_t *pipe, int slot, const uint8_t **text, uint64_t *n_bytes);
+
 /* ---- synthetic reads (BASELINE configs 2-5) ---------------------------- */
 /* Deterministic counter-based generator, identical on host and device (integer only).
  * kind 0: DNA-like (mean dwell 9 samples); kind 1: RNA-like (mean dwell 36, adaptor +

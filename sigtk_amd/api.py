@@ -19,6 +19,7 @@ LIB_PATH = os.path.join(PKG, "libsigtk_gpu.so")
 LIB_PATH = os.environ.get("SIGTK_AMD_LIB", LIB_PATH)
 
 SGK_OK = 0
+SGK_ERR_NODEVICE = -3
 SGK_ERR_CAPACITY = -5
 
 
@@ -184,6 +185,25 @@ class TextStatus(C.Structure):   # sgk_text_status_t
     _fields_ = [("overflow", C.c_uint32), ("n_tiles", C.c_uint32), ("n_bytes", C.c_uint64)]
 
 
+class SrefSpan(C.Structure):     # sgk_sref_span_t
+    _fields_ = [("base_offset", C.c_uint64), ("base_pos0", C.c_uint64), ("seq_len", C.c_uint32), ("first", C.c_uint32),
+                ("count", C.c_uint32), ("seq", C.c_uint32), ("strand", C.c_uint8), ("reserved", C.c_uint8 * 7)]
+
+
+#: sgk_sref_span_t as a numpy record (40 bytes)
+SREF_SPAN_DTYPE = np.dtype([("base_offset", "<u8"), ("base_pos0", "<u8"), ("seq_len", "<u4"), ("first", "<u4"),
+                            ("count", "<u4"), ("seq", "<u4"), ("strand", "u1"), ("reserved", "u1", (7,))])
+
+
+class SrefBatch(C.Structure):    # sgk_sref_batch_t (device pointers)
+    _fields_ = [("bases", C.c_void_p), ("n_bases", C.c_uint64), ("spans", C.c_void_p), ("n_spans", C.c_uint32),
+                ("k", C.c_uint32), ("levels", C.c_void_p), ("table_in_lds", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SrefStage(C.Structure):    # sgk_sref_stage_t (pinned host pointers)
+    _fields_ = [("bases", C.c_void_p), ("spans", C.c_void_p), ("name_bytes", C.c_void_p), ("name_offsets", C.c_void_p)]
+
+
 class JobText(C.Structure):      # sgk_job_text_t
     _fields_ = [("text", C.c_void_p), ("row_offsets", C.POINTER(C.c_uint64)), ("n_bytes", C.c_uint64)]
 
@@ -221,10 +241,41 @@ ABI_SYMBOLS = [
     # the TSV rows written on the device (csrc/text_kernels.hip)
     "sgk_text_workspace_bytes", "sgk_text_measure", "sgk_text_write", "sgk_text_status", "sgk_text_numbers_f32",
     "sgk_text_numbers_i64", "sgk_job_set_ids", "sgk_job_text",
+    # sref: the synthetic reference signal as floats and as rows (csrc/sref_kernels.hip)
+    "sgk_sref_levels", "sgk_sref_text_workspace_bytes", "sgk_sref_text_measure", "sgk_sref_text_write",
+    "sgk_sref_pipe_create", "sgk_sref_pipe_destroy", "sgk_sref_pipe_begin", "sgk_sref_pipe_submit", "sgk_sref_pipe_wait",
     # per-read shims with the reference's signatures (csrc/shims.hip)
     "sgk_jnn_raw", "sgk_jnn_pa", "sgk_jnnv2", "sgk_find_adaptor", "sgk_find_polya",
     "sgk_meanf", "sgk_meani16", "sgk_stdvf", "sgk_stdvi16", "sgk_medianf", "sgk_mediani16", "sgk_shim_status",
 ]
+
+
+def sref_spans(seq_lens, k: int, rna: bool = False, max_span: Optional[int] = None, cuts=None):
+    """The spans (SREF_SPAN_DTYPE) of `sigtk sref` over sequences of the given lengths, uploaded whole and back to back
+    (base_offset = the sequence's start, base_pos0 = 0): per sequence the '+' row and, unless rna, the '-' row, each cut
+    at every multiple of max_span and at every position of `cuts` that falls inside it.  A row with l + 1 - k <= 0 is
+    one span of count 0.  -> (spans, row_of_span: index of the row every span belongs to)"""
+    seq_lens = np.asarray(seq_lens, dtype=np.int64)
+    starts = np.zeros(seq_lens.size + 1, dtype=np.int64)
+    np.cumsum(seq_lens, out=starts[1:])
+    recs, rows = [], []
+    for i, l in enumerate(seq_lens.tolist()):
+        ref_len = l + 1 - k
+        for strand in ((0,) if rna else (0, 1)):
+            row = len(rows) and rows[-1] + 1
+            if ref_len <= 0:
+                bounds = [0, 0]
+            else:
+                b = {0, ref_len}
+                if max_span:
+                    b.update(range(max_span, ref_len, max_span))
+                if cuts is not None:
+                    b.update(int(c) for c in cuts if 0 < int(c) < ref_len)
+                bounds = sorted(b)
+            for lo, hi in zip(bounds[:-1], bounds[1:]):
+                recs.append((int(starts[i]), 0, l, lo, hi - lo, i, strand, (0,) * 7))
+                rows.append(row)
+    return np.array(recs, dtype=SREF_SPAN_DTYPE), np.asarray(rows, dtype=np.int64)
 
 
 def event_slots_for(n):
@@ -326,6 +377,18 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.sgk_text_status.argtypes = [C.c_void_p, C.POINTER(TextStatus)]
     L.sgk_text_numbers_f32.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.sgk_text_numbers_i64.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sgk_sref_levels.argtypes = [C.POINTER(SrefBatch), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sgk_sref_text_workspace_bytes.restype = C.c_size_t
+    L.sgk_sref_text_workspace_bytes.argtypes = [C.c_uint32, C.c_uint64]
+    L.sgk_sref_text_measure.argtypes = [C.POINTER(SrefBatch), C.POINTER(TextIds), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.sgk_sref_text_write.argtypes = [C.POINTER(SrefBatch), C.POINTER(TextIds), C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t,
+                                      C.c_void_p]
+    L.sgk_sref_pipe_create.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.sgk_sref_pipe_destroy.argtypes = [C.c_void_p]
+    L.sgk_sref_pipe_destroy.restype = None
+    L.sgk_sref_pipe_begin.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(SrefStage)]
+    L.sgk_sref_pipe_submit.argtypes = [C.c_void_p, C.c_int]
+    L.sgk_sref_pipe_wait.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     L.sgk_event_host.argtypes = [C.POINTER(HostBatch), C.c_int, C.POINTER(EventsHost)]
     L.sgk_event_host_opt.argtypes = L.sgk_event_host.argtypes + [OE]
     L.sgk_events_host_free.argtypes = [C.POINTER(EventsHost)]

@@ -32,27 +32,22 @@
 // neither ever reads or rewrites a byte of the other.  A tile that does not fit the image (ids of thousands of
 // bytes in every `event` row) writes its characters straight to global memory, each lane its own bytes.
 //
+// The tile list, the scan and the staged stores do not depend on the grammar: they are text_tiles.h, which
+// sref_kernels.hip uses for a fourth grammar.
+//
 // text_capacity is checked on the device (the call is asynchronous and the total is not known on the host): a tile
 // that would end behind it writes nothing and raises TEXT_FLAG_OVERFLOW in the workspace's header.
 #include "sgk_common.h"
 #include "text_format.h"
+#include "text_tiles.h"
 
 namespace sgk {
 
 int check_batch(const sgk_batch_t *b);
 
-constexpr int TEXT_TILE = 256;             // items per tile = threads per workgroup
-constexpr uint32_t TEXT_STAGE = 24576;     // bytes of a tile's LDS image (a pa tile needs at most 256 * 48)
-constexpr uint32_t TEXT_GRID_MAX = 16384;  // workgroups stride over the tile list
-constexpr uint32_t TEXT_FLAG_OVERFLOW = 1u, TEXT_FLAG_WORKSPACE = 2u;
+constexpr uint32_t TEXT_STAGE = 24576;  // bytes of a tile's LDS image (a pa tile needs at most 256 * 48)
 
-struct TextHdr {  // first 64 bytes of the workspace
-    uint32_t flags, n_tiles;
-    uint64_t n_bytes;
-    uint32_t reserved[12];
-};
-
-struct TextArgs {
+struct TextArgs : TileList {  // (n_rows = the batch's reads)
     const int16_t *samples;
     const uint64_t *offsets;
     const uint32_t *lengths;
@@ -62,30 +57,10 @@ struct TextArgs {
     const uint64_t *ev_slots;
     const sgk_event_rec_t *events;
     const uint32_t *n_events;
-    uint32_t n_reads, n_tiles_max;
-    TextHdr *hdr;
-    uint32_t *tile_first;  // n_reads + 1
-    uint32_t *tile_bytes;  // n_tiles_max
-    uint64_t *tile_off;    // n_tiles_max + 1
     uint64_t *row_offsets; // n_reads + 1 (measure)
     uint8_t *text;         // (write)
     uint64_t text_cap;
 };
-
-struct TextLayout {
-    size_t off_first, off_bytes, off_off, total;
-    uint32_t n_tiles_max;
-};
-static TextLayout text_layout(uint32_t n_reads, uint64_t n_items_capacity) {
-    TextLayout l;
-    const uint64_t nt = n_items_capacity / TEXT_TILE + (uint64_t)n_reads + 1;
-    l.n_tiles_max = nt < 0xfffffff0ull ? (uint32_t)nt : 0xfffffff0u;
-    l.off_first = sizeof(TextHdr);
-    l.off_bytes = round_up(l.off_first + ((size_t)n_reads + 1) * 4, 16);
-    l.off_off = round_up(l.off_bytes + (size_t)l.n_tiles_max * 4, 16);
-    l.total = l.off_off + ((size_t)l.n_tiles_max + 1) * 8;
-    return l;
-}
 
 // items of read r: samples (pa), the events that fitted the read's slots (event kinds)
 template <int KIND>
@@ -99,66 +74,12 @@ __device__ inline uint32_t text_items(const TextArgs &a, uint32_t r) {
 // ---- tiles of every read, one 1024-thread workgroup (the shape of k_layout in job.hip)
 template <int KIND>
 __global__ __launch_bounds__(1024) void k_text_tiles(TextArgs a) {
-    __shared__ uint32_t part[1024];
-    const uint32_t t = threadIdx.x, n = a.n_reads;
-    const uint32_t per = (n + 1023u) / 1024u;
-    const uint32_t lo = t * per < n ? t * per : n, hi = lo + per < n ? lo + per : n;
-    uint32_t sum = 0;
-    for (uint32_t r = lo; r < hi; ++r) {
-        const uint32_t it = text_items<KIND>(a, r);
-        sum += it ? (it + TEXT_TILE - 1) / TEXT_TILE : 1u;
-    }
-    part[t] = sum;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024; d <<= 1) {
-        const uint32_t v = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    // (the sum cannot wrap: it is at most n_items / 256 + n_reads, both below 2^32 / 2 for any batch that exists)
-    const bool fits = part[1023] <= a.n_tiles_max;
-    uint32_t o = part[t] - sum;
-    for (uint32_t r = lo; r < hi; ++r) {
-        a.tile_first[r] = fits ? o : 0u;
-        const uint32_t it = text_items<KIND>(a, r);
-        o += it ? (it + TEXT_TILE - 1) / TEXT_TILE : 1u;
-    }
-    if (t == 1023) {
-        a.tile_first[n] = fits ? part[1023] : 0u;
-        a.hdr->flags = fits ? 0u : TEXT_FLAG_WORKSPACE;  // a workspace sized for a smaller batch: nothing is written
-        a.hdr->n_tiles = fits ? part[1023] : 0u;
-        a.hdr->n_bytes = 0;
-    }
+    text_tiles_body(a, [&](uint32_t r) { return text_items<KIND>(a, r); });
 }
 
 // ---- tile offsets and row offsets, one 1024-thread workgroup
 __global__ __launch_bounds__(1024) void k_text_scan(TextArgs a) {
-    __shared__ uint64_t part[1024];
-    const uint32_t t = threadIdx.x, n = a.hdr->n_tiles;
-    const uint32_t per = (n + 1023u) / 1024u;
-    const uint32_t lo = (uint64_t)t * per < n ? t * per : n, hi = (uint64_t)lo + per < n ? lo + per : n;
-    uint64_t sum = 0;
-    for (uint32_t k = lo; k < hi; ++k) sum += a.tile_bytes[k];
-    part[t] = sum;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024; d <<= 1) {
-        const uint64_t v = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    uint64_t o = part[t] - sum;
-    for (uint32_t k = lo; k < hi; ++k) {
-        a.tile_off[k] = o;
-        o += a.tile_bytes[k];
-    }
-    if (t == 1023) {
-        a.tile_off[n] = part[1023];
-        a.hdr->n_bytes = part[1023];
-    }
-    __syncthreads();
-    for (uint32_t r = t; r <= a.n_reads; r += 1024) a.row_offsets[r] = a.tile_off[a.tile_first[r]];
+    text_scan_body(a, a.row_offsets);
 }
 
 // The sign of a NaN is printed ("nan" / "-nan"), and the reference runs on x86: there an invalid operation (0 * inf,
@@ -198,13 +119,7 @@ struct TileCtx {
 
 template <int KIND>
 __device__ inline TileCtx tile_ctx(const TextArgs &a, uint32_t t) {
-    // the read of tile t: tile_first[r] <= t < tile_first[r + 1] (strictly increasing: every read has a tile)
-    uint32_t lo = 0, hi = a.n_reads;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (a.tile_first[mid] <= t) lo = mid;
-        else hi = mid;
-    }
+    const uint32_t lo = text_tile_row(a, t);
     TileCtx c;
     c.r = lo;
     c.j0 = (t - a.tile_first[lo]) * TEXT_TILE;
@@ -324,16 +239,7 @@ template <int KIND>
 __device__ inline uint32_t tile_offsets(const TileCtx &c, uint32_t *wave_tot, uint32_t &my_len, uint32_t &my_off) {
     const uint32_t j = c.j0 + threadIdx.x;
     my_len = j < c.n_items ? item_len<KIND>(c, j) : 0u;
-    const int incl = wave_incl_scan_i((int)my_len);
-    const uint32_t w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63u) == 63u) wave_tot[w] = (uint32_t)incl;
-    __syncthreads();
-    uint32_t base = prefix_len<KIND>(c), sum = base;
-    for (uint32_t k = 0; k < TEXT_TILE / 64; ++k) {
-        if (k < w) base += wave_tot[k];
-        sum += wave_tot[k];
-    }
-    my_off = base + (uint32_t)incl - my_len;
+    const uint32_t sum = text_lane_offsets(my_len, prefix_len<KIND>(c), wave_tot, my_off);
     return sum + (c.last ? 1u : 0u);  // every read ends with one '\n' (event: the empty line)
 }
 
@@ -365,18 +271,12 @@ __global__ __launch_bounds__(TEXT_TILE) void k_text_write(TextArgs a) {
             if (threadIdx.x == 0) atomicOr(&a.hdr->flags, TEXT_FLAG_OVERFLOW);
         } else if (total <= TEXT_STAGE) {
             uint8_t *dst = a.text + b0;
-            const uint32_t al = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u);
-            char *img = stage + al;  // img + k and dst + k are congruent modulo 16
+            char *img = stage + text_image_align(dst);  // img + k and dst + k are congruent modulo 16
             prefix_emit<KIND>(c, img);
             if (my_len) item_emit<KIND>(c, j, img + my_off);
             if (c.last && threadIdx.x == 0) img[total - 1] = '\n';
             __syncthreads();
-            const uint32_t head0 = (16u - al) & 15u, head = head0 < total ? head0 : total;
-            const uint32_t nvec = (total - head) / 16u, tail0 = head + nvec * 16u;
-            if (threadIdx.x < head) dst[threadIdx.x] = (uint8_t)img[threadIdx.x];
-            for (uint32_t v = threadIdx.x; v < nvec; v += TEXT_TILE)
-                *reinterpret_cast<uint4 *>(dst + head + 16u * v) = *reinterpret_cast<const uint4 *>(img + head + 16u * v);
-            if (threadIdx.x < total - tail0) dst[tail0 + threadIdx.x] = (uint8_t)img[tail0 + threadIdx.x];
+            text_image_flush(dst, img, total);
         } else {
             char *dst = reinterpret_cast<char *>(a.text + b0);
             prefix_emit<KIND>(c, dst);
@@ -411,12 +311,7 @@ static int text_args(int kind, const sgk_batch_t *b, const sgk_text_ids_t *ids, 
     if (b->n_reads && (!ids || !ids->bytes || !ids->offsets)) return SGK_ERR_ARG;
     if (b->n_reads && kind != SGK_TEXT_PA && (!ev_slots || !events || !n_events)) return SGK_ERR_ARG;
     if (kind != SGK_TEXT_PA && (reinterpret_cast<uintptr_t>(events) & 15u)) return SGK_ERR_ALIGN;
-    // the tile capacity is what the workspace holds: (ws_bytes - header - tile_first) / (4 + 8 bytes per tile)
-    const size_t fixed = round_up(sizeof(TextHdr) + ((size_t)b->n_reads + 1) * 4, 16) + 16 + 8;
-    if (ws_bytes < fixed + 12) return SGK_ERR_WORKSPACE;
-    uint64_t nt = (ws_bytes - fixed) / 12;
-    if (nt > 0xfffffff0ull) nt = 0xfffffff0ull;
-    char *w = static_cast<char *>(ws);
+    if (!tile_list_carve(ws, ws_bytes, b->n_reads, a)) return SGK_ERR_WORKSPACE;
     a->samples = b->samples;
     a->offsets = b->offsets;
     a->lengths = b->lengths;
@@ -428,13 +323,6 @@ static int text_args(int kind, const sgk_batch_t *b, const sgk_text_ids_t *ids, 
     a->ev_slots = ev_slots;
     a->events = events;
     a->n_events = n_events;
-    a->n_reads = b->n_reads;
-    a->n_tiles_max = (uint32_t)nt;
-    a->hdr = reinterpret_cast<TextHdr *>(w);
-    a->tile_first = reinterpret_cast<uint32_t *>(w + sizeof(TextHdr));
-    const size_t off_bytes = round_up(sizeof(TextHdr) + ((size_t)b->n_reads + 1) * 4, 16);
-    a->tile_bytes = reinterpret_cast<uint32_t *>(w + off_bytes);
-    a->tile_off = reinterpret_cast<uint64_t *>(w + round_up(off_bytes + (size_t)nt * 4, 16));
     a->row_offsets = nullptr;
     a->text = nullptr;
     a->text_cap = 0;
@@ -449,7 +337,7 @@ extern "C" {
 
 size_t sgk_text_workspace_bytes(int kind, uint32_t n_reads, uint64_t n_items_capacity) {
     (void)kind;
-    return text_layout(n_reads, n_items_capacity).total + 64;
+    return tile_list_bytes(n_reads, n_items_capacity) + 64;
 }
 
 int sgk_text_measure(int kind, const sgk_batch_t *b, const sgk_text_ids_t *ids, const uint64_t *ev_slots,

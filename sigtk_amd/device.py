@@ -418,6 +418,106 @@ class TextWriter:
         return text[:total].cpu().numpy().tobytes()
 
 
+# ---------------------------------------------------------------------- sref: synthetic reference signal (sgk_sref_*)
+
+class SrefBatch:
+    """Sequences (bytes, as read from a FASTA file), their names and a pore model (`levels`: 4^k float32 by k-mer rank)
+    on the device, with the spans api.sref_spans cuts their rows into (max_span / cuts force seams)."""
+
+    def __init__(self, seqs, names, levels, k: int, rna: bool = False, max_span: Optional[int] = None, cuts=None,
+                 table_in_lds: bool = False, device: Optional[torch.device] = None):
+        dev = device or torch.device("cuda", torch.cuda.current_device())
+        levels = np.ascontiguousarray(levels, dtype=np.float32)
+        assert levels.size == 4 ** k, "the model must hold 4^k levels"
+        seqs = [bytes(s) for s in seqs]
+        raw = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
+        assert len(raw) == len(seqs)
+        self.spans_host, self.row_of_span = api.sref_spans([len(s) for s in seqs], k, rna, max_span, cuts)
+        self.n_spans = int(self.spans_host.size)
+        self.n_positions = int(self.spans_host["count"].astype(np.int64).sum()) if self.n_spans else 0
+        blob = np.frombuffer(b"".join(seqs) + b"\0" * 16, dtype=np.uint8).copy()
+        self.n_bases = blob.size - 16
+        self.bases = torch.from_numpy(blob).to(dev)
+        self.spans = torch.from_numpy(np.frombuffer(self.spans_host.tobytes() + b"\0" * 40, dtype=np.uint8).copy()).to(dev)
+        self.levels = torch.from_numpy(levels.view(np.int32).copy()).to(dev)
+        offs = np.zeros(len(raw) + 1, dtype=np.int64)
+        np.cumsum([len(n) for n in raw], out=offs[1:])
+        self.name_bytes = torch.from_numpy(np.frombuffer(b"".join(raw) + b"\0" * 16, dtype=np.uint8).copy()).to(dev)
+        self.name_offs = torch.from_numpy(offs.astype(np.int32)).to(dev)
+        self.names = api.TextIds(_ptr(self.name_bytes), _ptr(self.name_offs))
+        self.k, self.device, self.table_in_lds = int(k), dev, bool(table_in_lds)
+
+    def view(self) -> api.SrefBatch:
+        return api.SrefBatch(_ptr(self.bases), self.n_bases, _ptr(self.spans), self.n_spans, self.k, _ptr(self.levels),
+                             int(self.table_in_lds), 0)
+
+
+def sref_levels(seqs, levels, k: int, rna: bool = False, max_span: Optional[int] = None, cuts=None,
+                device: Optional[torch.device] = None, batch: Optional[SrefBatch] = None, to_host: bool = True):
+    """sgk_sref_levels -> one float32 array per row ('+' then, unless rna, '-' of every sequence), its spans joined;
+    to_host=False: the device tensor of all rows back to back, not synchronised"""
+    b = batch or SrefBatch(seqs, [b""] * len(seqs), levels, k, rna, max_span, cuts, device=device)
+    counts = b.spans_host["count"].astype(np.int64) if b.n_spans else np.zeros(0, dtype=np.int64)
+    offs = np.zeros(b.n_spans + 1, dtype=np.int64)
+    np.cumsum(counts, out=offs[1:])
+    d_offs = torch.from_numpy(offs).to(b.device)
+    out = torch.zeros(max(int(offs[-1]), 1), dtype=torch.float32, device=b.device)
+    view = b.view()
+    api.check(api.load_library().sgk_sref_levels(C.byref(view), _ptr(d_offs), _ptr(out), _stream_ptr()), "sgk_sref_levels")
+    if not to_host:
+        return out
+    torch.cuda.synchronize()
+    flat = out.cpu().numpy()
+    n_rows = int(b.row_of_span[-1]) + 1 if b.n_spans else 0
+    row_lo = np.searchsorted(b.row_of_span, np.arange(n_rows), side="left")
+    row_hi = np.searchsorted(b.row_of_span, np.arange(n_rows), side="right")
+    return [flat[int(offs[lo]):int(offs[hi])].copy() for lo, hi in zip(row_lo, row_hi)]
+
+
+class SrefText(SrefBatch):
+    """sgk_sref_text_measure + sgk_sref_text_write over one resident batch of spans, in the manner of TextWriter:
+    measure() and write() only enqueue; status() synchronises; row_offsets has n_spans + 1 entries."""
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        L = api.load_library()
+        self.ws_bytes = int(L.sgk_sref_text_workspace_bytes(self.n_spans, self.n_positions))
+        self.ws = torch.zeros(self.ws_bytes, dtype=torch.uint8, device=self.device)
+        self.row_offsets = torch.zeros(self.n_spans + 1, dtype=torch.int64, device=self.device)
+
+    def measure(self) -> None:
+        view = self.view()
+        api.check(api.load_library().sgk_sref_text_measure(C.byref(view), C.byref(self.names), _ptr(self.row_offsets),
+                                                           _ptr(self.ws), self.ws_bytes, _stream_ptr()), "sgk_sref_text_measure")
+
+    def write(self, text: torch.Tensor, capacity: Optional[int] = None) -> None:
+        view = self.view()
+        api.check(api.load_library().sgk_sref_text_write(C.byref(view), C.byref(self.names), _ptr(text),
+                                                         int(text.numel() if capacity is None else capacity), _ptr(self.ws),
+                                                         self.ws_bytes, _stream_ptr()), "sgk_sref_text_write")
+
+    def status(self):
+        """-> (return code of sgk_text_status: 0 or api.SGK_ERR_CAPACITY, api.TextStatus); synchronises"""
+        torch.cuda.synchronize()
+        st = api.TextStatus()
+        rc = api.load_library().sgk_text_status(_ptr(self.ws), C.byref(st))
+        if rc not in (api.SGK_OK, api.SGK_ERR_CAPACITY):
+            api.check(rc, "sgk_text_status")
+        return rc, st
+
+    def run(self) -> bytes:
+        """measure, allocate exactly, write -> the rows as bytes (and self.row_offsets_host)"""
+        self.measure()
+        torch.cuda.synchronize()
+        self.row_offsets_host = self.row_offsets.cpu().numpy().astype(np.uint64)
+        total = int(self.row_offsets_host[-1])
+        text = torch.zeros(max(total, 1), dtype=torch.uint8, device=self.device)
+        self.write(text, total)
+        rc, _ = self.status()
+        api.check(rc, "sgk_sref_text_write")
+        return text[:total].cpu().numpy().tobytes()
+
+
 def text_numbers(values: np.ndarray):
     """sgk_text_numbers_f32 / _i64 (by dtype): printf("%f") / "%ld" of every value, made on the device
     -> (uint8 array [n, 48] of the slots, filled with '#' beforehand; uint8 array [n] of the byte counts)"""

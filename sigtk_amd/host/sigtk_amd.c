@@ -29,10 +29,11 @@
 
 #include "blow5.h"
 #include "fmt.h"
+#include "sref.h"
+#include "version.h"
 #include "../csrc/text_format.h"
 #include "sigtk_gpu.h"
 
-#define SIGTK_VERSION "0.2.0" /* the reference version whose CLI this mirrors (src/sigtk.h:11) */
 
 #define INFO(fn, msg) fprintf(stderr, "[%s::INFO]\033[1;34m %s\033[0m\n", fn, msg)
 #define WARNING(fn, ...)                                         \
@@ -1533,7 +1534,8 @@ static void print_usage(FILE *fp) {
     fprintf(fp, "         jnn       print segments found using JNN segmenter\n");
     fprintf(fp, "         ent       calculate entropies\n");
     fprintf(fp, "         qts       quantise the raw signal in a S/BLOW5 files\n");
-    fprintf(fp, "\n(sigtk-amd: the per-read raw-signal subtools on MI355X; sref/ss are not part of it)\n");
+    fprintf(fp, "         sref      print synthetic reference signal (needs --kmer-model FILE)\n");
+    fprintf(fp, "\n(sigtk-amd: the raw-signal subtools and sref on MI355X; ss is not part of it)\n");
     exit(fp == stdout ? EXIT_SUCCESS : EXIT_FAILURE);
 }
 
@@ -1549,6 +1551,12 @@ int main(int argc, char *argv[]) {
         ret = cmain(argc - 1, argv + 1, argv[1]);
     } else if (strcmp(argv[1], "qts") == 0) {
         ret = qtsmain(argc - 1, argv + 1);
+    } else if (strcmp(argv[1], "sref") == 0) {
+        ret = srefmain(argc - 1, argv + 1);
+    } else if (strcmp(argv[1], "_fadump") == 0) {
+        return fadumpmain(argc - 1, argv + 1);
+    } else if (strcmp(argv[1], "_modelcheck") == 0) {
+        return modelcheckmain(argc - 1, argv + 1);
     } else if (strcmp(argv[1], "_dump") == 0) {
         return dumpmain(argc - 1, argv + 1);
     } else if (strcmp(argv[1], "_fmtcheck") == 0) {
