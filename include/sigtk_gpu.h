@@ -380,8 +380,9 @@ int sgk_svbzd_decode(const uint8_t *blobs, const uint64_t *blob_offsets, const u
  * stream; out: 16-byte aligned device buffer, stream r's bytes go to out + out_offsets[r] (offsets multiples of 16), which
  * must have room for out_caps[r] bytes >= what the stream inflates to (matches that reach far back read the stream's own
  * earlier bytes from there); out_lengths[r]: what the stream inflated to; status[r]: 0 ok, 1 bad zlib header / preset
- * dictionary, 2 bad block type / stored length, 3 bad code lengths, 4 invalid code, 5 distance in front of the stream,
- * 6 truncated input, 7 Adler-32 mismatch, 8 the stream inflates to more than out_caps[r] (1 - 8: the bytes are undefined). */
+ * dictionary, 2 bad block type / stored length, 3 bad code lengths (an invalid, over-subscribed or incomplete set),
+ * 4 invalid code, 5 distance in front of the stream, 6 truncated input, 7 Adler-32 mismatch, 8 the stream inflates to
+ * more than out_caps[r] (1 - 8: the bytes are undefined). */
 int sgk_inflate(const uint8_t *in, const uint64_t *in_offsets, const uint32_t *in_lengths, uint32_t n, uint8_t *out,
                 const uint64_t *out_offsets, const uint32_t *out_caps, uint32_t *out_lengths, uint32_t *status,
                 void *stream);

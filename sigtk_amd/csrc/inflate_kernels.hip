@@ -20,8 +20,8 @@
 //   * Huffman tables are built in parallel (a lane per symbol: rank within its code length by ballots, bit-reversed
 //     replication into a 10-bit / 8-bit look-up table); codes longer than the table walk the canonical first-code /
 //     count arrays (puff.c's decode), which is rare.
-// Everything a zlib inflate checks is checked: header, block types, stored-block length complement, over-subscribed code
-// length sets, invalid codes, distances in front of the stream, truncated input, Adler-32.  A stream that fails leaves a
+// Everything a zlib inflate checks is checked: header, block types, stored-block length complement, over-subscribed and
+// incomplete code length sets, invalid codes, distances in front of the stream, truncated input, Adler-32.  A stream that fails leaves a
 // non-zero status and the host decides (the CLI reports it as the reference does a slow5_get_next error).
 #include "sgk_common.h"
 
@@ -38,7 +38,7 @@ enum {
     INF_OK = 0,
     INF_ERR_HEADER = 1,     // not a zlib stream (CMF / FLG), or a preset dictionary
     INF_ERR_BLOCK = 2,      // reserved block type / stored-block length check
-    INF_ERR_LENGTHS = 3,    // invalid or over-subscribed code length set, no end-of-block code
+    INF_ERR_LENGTHS = 3,    // invalid, over-subscribed or incomplete code length set, no end-of-block code
     INF_ERR_CODE = 4,       // invalid literal / length or distance code
     INF_ERR_DISTANCE = 5,   // distance reaches in front of the stream
     INF_ERR_TRUNCATED = 6,  // input ends inside the stream
@@ -151,9 +151,11 @@ struct InfBits {
 };
 
 // ---- Huffman tables, built by the whole wave from lens[0 .. nsym) (in LDS)
-// returns false for an over-subscribed set of code lengths
+// returns -1 for an over-subscribed set of code lengths (no tables then), else what the set leaves of the code space in
+// units of 2^-15 (0: complete, INF_LEFT_NONE: no codes at all) -- see inf_complete()
+constexpr int INF_LEFT_NONE = 1 << 15;
 template <int TB, int NS>
-__device__ bool inf_build(InfTables<TB, NS> *t, const uint8_t *lens, int nsym) {
+__device__ int inf_build(InfTables<TB, NS> *t, const uint8_t *lens, int nsym) {
     const int l = lane_id();
     if (l < 16) t->count[l] = 0u;
     for (int k = l; k < (1 << TB); k += 64) t->fast[k] = 0;
@@ -175,7 +177,7 @@ __device__ bool inf_build(InfTables<TB, NS> *t, const uint8_t *lens, int nsym) {
         code = (code + c) << 1;
         off += c;
     }
-    if (!ok) return false;
+    if (!ok) return -1;
     __syncthreads();
     // rank of every symbol within its length (symbol order), 64 symbols at a time
     uint32_t seen[16];
@@ -202,7 +204,13 @@ __device__ bool inf_build(InfTables<TB, NS> *t, const uint8_t *lens, int nsym) {
         }
     }
     __syncthreads();
-    return true;
+    return left;
+}
+// zlib's rule for the literal / length and the distance code of a dynamic block (inflate_table: left > 0 && max != 1 is
+// an error): complete, or one single code of one bit -- half the code space left and one code of length 1 is just that
+template <int TB, int NS>
+__device__ __forceinline__ bool inf_complete(const InfTables<TB, NS> *t, int left) {
+    return left == 0 || (left == INF_LEFT_NONE / 2 && uni(t->count[1]) == 1u);
 }
 
 // one symbol (wave-uniform); -1: invalid code.  At least 15 valid bits in the buffer (zeros behind the stream's end).
@@ -419,7 +427,7 @@ __global__ __launch_bounds__(64) void k_inflate(InfArgs a) {
                 if (l == 0) L.lens[INF_CLORDER[k]] = (uint8_t)v;
             }
             __syncthreads();
-            if (!inf_build(&L.cl, L.lens, 19)) { st = INF_ERR_LENGTHS; break; }
+            if (inf_build(&L.cl, L.lens, 19) != 0) { st = INF_ERR_LENGTHS; break; }   // (incomplete too)
             // the code lengths of the two alphabets, with repeats (serial)
             int i = 0, prev = 0;
             bool bad = false;
@@ -452,8 +460,14 @@ __global__ __launch_bounds__(64) void k_inflate(InfArgs a) {
             if (bad || b.overrun()) { st = bad ? INF_ERR_LENGTHS : INF_ERR_TRUNCATED; break; }
             if (uni(L.lens[256]) == 0u) { st = INF_ERR_LENGTHS; break; }
         }
-        if (!inf_build(&L.lit, L.lens, nlit)) { st = INF_ERR_LENGTHS; break; }
-        if (!inf_build(&L.dist, L.lens + nlit, ndist)) { st = INF_ERR_LENGTHS; break; }
+        // (the fixed block's sets are what they are: 30 of 32 distance codes, the other two invalid where they are met)
+        const int left_lit = inf_build(&L.lit, L.lens, nlit);
+        if (left_lit < 0 || (type == 2u && !inf_complete(&L.lit, left_lit))) { st = INF_ERR_LENGTHS; break; }
+        const int left_dist = inf_build(&L.dist, L.lens + nlit, ndist);   // (no distance code at all: a block of literals)
+        if (left_dist < 0 || (type == 2u && left_dist != INF_LEFT_NONE && !inf_complete(&L.dist, left_dist))) {
+            st = INF_ERR_LENGTHS;
+            break;
+        }
         // ---- the symbols of the block
         uint32_t misses = 0u, pause = 0u;   // the literal runs pause where matches follow each other
         bool try_run = true;
@@ -576,6 +590,11 @@ __global__ __launch_bounds__(64) void k_inflate(InfArgs a) {
         if (st == INF_OK && b.overrun()) st = INF_ERR_TRUNCATED;
         if (st == INF_OK && o.pos > o.cap) st = INF_ERR_ROOM;
     }
+    // a fault met after bits behind the input's end were consumed is the input's end: zlib waits for those bits and
+    // reports a truncated stream, whatever the zeros the reader yields there would have meant.  (Consumed bits only: a
+    // fault the kernel reports before it takes the bits zlib would first wait for -- an invalid code that straddles the
+    // end, code 16 first with its extra bits behind the end -- keeps its own status.)
+    if (st >= INF_ERR_BLOCK && st <= INF_ERR_DISTANCE && b.overrun()) st = INF_ERR_TRUNCATED;
     if (st == INF_OK) {
         __syncthreads();
         while (o.pos - o.flushed >= (uint32_t)INF_FLUSH) inf_flush(&L, o, INF_FLUSH);

@@ -316,18 +316,30 @@ def svbzd_encode(b: DeviceReads):
     return [host[int(offs[r]):int(offs[r]) + int(lens[r])].tobytes() for r in range(n)]
 
 
-def inflate(streams, caps=None, device: Optional[torch.device] = None):
+def inflate_input_offsets(streams, leads=None):
+    """where inflate() puts every stream in its input buffer (whose start is 4-byte aligned) -> (byte offsets, total):
+    at odd offsets on purpose, the kernel aligns its dword reads itself; leads[r] in 0 - 3 (None: any) asks for
+    offset % 4 == leads[r], for streams built for one alignment of their first byte"""
+    in_off = np.zeros(len(streams), dtype=np.uint64)
+    pos = 0
+    for r, s in enumerate(streams):
+        if leads is not None and leads[r] is not None:
+            pos += (int(leads[r]) - pos) & 3
+        in_off[r] = pos
+        pos += len(s) + (r % 3)
+    return in_off, pos
+
+
+def inflate(streams, caps=None, device: Optional[torch.device] = None, with_gaps: bool = False, leads=None):
     """sgk_inflate over a list of zlib streams (bytes) -> (list of inflated bytes as kept: the first caps[r] of each,
-    out_lengths, status) -- the device-side replacement of slow5lib's per-record uncompress()"""
+    out_lengths, status) -- the device-side replacement of slow5lib's per-record uncompress().  with_gaps: a fourth
+    result, the bytes of the (zero-filled) output buffer between caps[r] and the next stream's 16-byte aligned area,
+    which no stream may write; leads: see inflate_input_offsets"""
     L = api.load_library()
     dev = device or torch.device("cuda", 0)
     n = len(streams)
-    in_off = np.zeros(n, dtype=np.uint64)
     in_len = np.asarray([len(s) for s in streams], dtype=np.uint32)
-    pos = 0
-    for r, s in enumerate(streams):
-        in_off[r] = pos
-        pos += len(s) + (r % 3)          # (odd offsets on purpose: the kernel aligns its dword reads itself)
+    in_off, pos = inflate_input_offsets(streams, leads)
     blob = np.zeros((pos + 7) // 4 * 4 + 4, dtype=np.uint8)
     for r, s in enumerate(streams):
         blob[int(in_off[r]):int(in_off[r]) + len(s)] = np.frombuffer(s, dtype=np.uint8)
@@ -337,6 +349,7 @@ def inflate(streams, caps=None, device: Optional[torch.device] = None):
         out_off[1:] = np.cumsum((caps_a[:-1].astype(np.uint64) + 15) // 16 * 16)
     total = int(out_off[-1] + (int(caps_a[-1]) + 15) // 16 * 16) if n else 16
     d_in = torch.from_numpy(blob).to(dev)
+    assert _ptr(d_in) % 4 == 0
     d_ioff = torch.from_numpy(in_off.view(np.int64)).to(dev)
     d_ilen = torch.from_numpy(in_len.view(np.int32)).to(dev)
     d_out = torch.zeros(max(total, 16), dtype=torch.uint8, device=dev)
@@ -351,6 +364,9 @@ def inflate(streams, caps=None, device: Optional[torch.device] = None):
     olen = d_olen.cpu().numpy().view(np.uint32)[:n]
     st = d_st.cpu().numpy()[:n]
     kept = [out[int(out_off[r]):int(out_off[r]) + min(int(olen[r]), int(caps_a[r]))].tobytes() for r in range(n)]
+    if with_gaps:
+        ends = [int(out_off[r + 1]) if r + 1 < n else total for r in range(n)]
+        return kept, olen, st, [out[int(out_off[r]) + int(caps_a[r]):ends[r]].tobytes() for r in range(n)]
     return kept, olen, st
 
 

@@ -225,3 +225,32 @@ def test_a_record_that_does_not_inflate_fails_like_a_read_error(cli, tmp_path, s
     for extra in ([], ["--host-inflate"]):
         p = subprocess.run([cli, "stat", *extra, path], capture_output=True)
         assert p.returncode != 0 and b"slow5_get_next" in p.stderr, (extra, p.stderr[-300:])
+
+
+def test_records_recoded_as_crafted_deflate_streams(cli, tmp_path):
+    """sp1_dna.blow5 with every record's zlib stream replaced by a hand-built encoding of the same bytes
+    (tests/deflate_craft.py: several blocks, literal and distance codes of up to 15 bits, stored blocks in the middle,
+    matches that reach back into them): the records inflated on the GPU, the records inflated by the host's zlib and
+    the reference's goldens agree"""
+    import struct
+    import zlib
+    import deflate_craft
+    data = open(SP1, "rb").read()
+    (hsize,) = struct.unpack_from("<I", data, 64)
+    parts = [data[:68 + hsize]]
+    rng = np.random.RandomState(1950)
+    for rec in blow5.raw_records(SP1):
+        stream = deflate_craft.recode(rng, rec)
+        assert zlib.decompress(stream) == rec
+        parts.append(struct.pack("<Q", len(stream)) + stream)
+    parts.append(data[-5:])                                   # the end-of-file marker
+    path = str(tmp_path / "crafted.blow5")
+    open(path, "wb").write(b"".join(parts))
+    assert blow5.raw_records(path) == blow5.raw_records(SP1)
+    for tool, golden in ((["stat"], "sp1_dna.stat.tsv"), (["event", "-c"], "sp1_dna.event_c.tsv")):
+        got = out(cli, *tool, path)
+        assert got == out(cli, *tool, "--host-inflate", path), tool
+        assert got == gold(golden), tool
+    got = out(cli, "pa", path)
+    assert got == out(cli, "pa", "--host-inflate", path)
+    assert hashlib.sha256(got).hexdigest() == MANIFEST["sp1_dna.pa.tsv.sha256"]
