@@ -327,7 +327,7 @@ static uint64_t check_mean1(uint64_t count) {
                 S += (double)f;
                 Sq += (double)(f * f);
             }
-            const SgkARole a = sgk_arole<W, true>(S, Sq);   // the product's form (event_kernels.hip: LazyPass, fast path)
+            const SgkARole a = sgk_arole<W, true>(S, Sq);   // the product's form (event_detect.h: LazyPass, fast path)
             const float want = (float)(S / (double)(float)W);
             if (f2u(a.mean1) != f2u(want)) bad++;
         }

@@ -21,8 +21,9 @@ LIB = os.path.join(PKG, "libsigtk_gpu.so")
 CLI = os.path.join(PKG, "sigtk-amd")
 CLI_ASAN = os.path.join(PKG, "sigtk-amd-asan")
 
-HIP_SOURCES = ["api.hip", "api_stat.hip", "event_kernels.hip", "stat_launch.hip", "stat_lane.hip", "stat_wave.hip",
-               "stat_long.hip", "misc_kernels.hip", "svb_kernels.hip", "inflate_kernels.hip", "ent_kernels.hip",
+EVENT_SOURCES = ["event_launch.hip", "event_whole.hip", "event_seg.hip", "event_multi.hip", "event_fallback.hip"]
+HIP_SOURCES = ["api.hip", "api_stat.hip", *EVENT_SOURCES, "stat_launch.hip", "stat_lane.hip", "stat_wave.hip", "stat_long.hip",
+               "misc_kernels.hip", "svb_kernels.hip", "inflate_kernels.hip", "ent_kernels.hip",
                "qts_kernels.hip", "text_kernels.hip", "sref_kernels.hip", "job.hip", "shims.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
                "-fhip-fp32-correctly-rounded-divide-sqrt", "-fPIC", "-shared", "-Wall",
@@ -46,8 +47,8 @@ def hipcc() -> str:
 def build_lib(force: bool = False, verbose: bool = False) -> str:
     """One object per .hip source (in parallel, rebuilt only when the source or a header changed), then one link.
     Without -fgpu-rdc every translation unit's device code is self-contained, exactly as when hipcc is handed all the
-    sources at once -- only faster to iterate on (event_kernels.hip and stat_lane.hip, the slowest, take ~45 s each;
-    the other stat units 2 - 12 s)."""
+    sources at once -- only faster to iterate on (stat_lane.hip, the slowest, takes ~45 s; the other stat units 2 - 12 s;
+    the event units 12 - 20 s each: event_whole 14, event_seg 17, event_multi 12, event_fallback 20, event_launch 2)."""
     from concurrent.futures import ThreadPoolExecutor
     srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES if os.path.exists(os.path.join(CSRC, s))]
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
@@ -77,7 +78,7 @@ def build_lib(force: bool = False, verbose: bool = False) -> str:
     return LIB
 
 
-def build_variant(tag: str, defines, sources=("event_kernels.hip", "api.hip"), verbose: bool = False) -> str:
+def build_variant(tag: str, defines, sources=(*EVENT_SOURCES, "api.hip"), verbose: bool = False) -> str:
     """A development variant of the library: `sources` recompiled with the given -D flags, everything else taken from
     the shipped build's objects -> sigtk_amd/_variants/libsigtk_gpu_<tag>.so (select it with SIGTK_AMD_LIB=<path>).
     -DSGK_DEV=1 is the instrumented build of event_args.h (phases switched off per call, per-wave timestamps)."""

@@ -173,7 +173,7 @@ EvSegConfig event_config_for(const EvSegConfig &c0, uint64_t n_samples, int rna)
     return c;
 }
 
-// The tail split (event_kernels.hip: seg_len_of).  A batch of fewer than 8 rounds of waves whose last round is a SMALL
+// The tail split (event_device.h: seg_len_of).  A batch of fewer than 8 rounds of waves whose last round is a SMALL
 // fraction of one: the reads of that round (the last dispatch positions) are cut into segments, as many per read as fill
 // a round (up to 8), never shorter than 16 384 samples.  Not in a batch with packed short reads (they balance by
 // themselves), not for reads under 32 768 samples on average.

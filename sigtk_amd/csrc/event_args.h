@@ -23,9 +23,9 @@ static_assert(sizeof(EvHeader) == 64, "header is one 64-byte block");
 // A read of at least `long_min` samples is cut into segments of `seg_len` samples (a multiple of 1024), one wavefront
 // each: the same speculative scheme that lets the 64 lanes of a wave start in the middle of a read lets a wave do
 // so.  Segment g > 0 starts its first lane `lead` samples early from the fresh state; the state it reaches at the
-// segment's first index must equal the state segment g-1 ended with (k_event_seam checks, and runs a segment whose
-// speculation failed again from the true state).  The builder then runs per segment as well, from the last boundary
-// in front of the segment, at the event rank the segments in front of it determine.
+// segment's first index must equal the state segment g-1 ended with (chain_segment of k_event_seg checks, and runs a
+// segment whose speculation failed again from the true state).  The builder then runs per segment as well, from the last
+// boundary in front of the segment, at the event rank the segments in front of it determine.
 struct LzSnapState {  // detector state at an index, absolute (read-relative) positions: what chunks and segments hand over
     int sp;         // short peak_pos, -1 when not in a peak
     float sv;       // short peak_value
@@ -149,6 +149,15 @@ struct EvWorkspace {
 EvWorkspace event_workspace_layout(const EvSegConfig &c, uint32_t n_reads, uint64_t n_samples, uint32_t max_read_len,
                                    size_t available /* 0 = default sizing */);
 
-int launch_event(const EvArgs &a, int rna, bool float_input, uint32_t n_fb_blocks, hipStream_t st);
+int launch_event(const EvArgs &a, int rna, bool float_input, uint32_t n_fb_blocks, hipStream_t st);  // event_launch.hip
+
+// ---- one launch per kernel, defined in the unit that holds the kernel (without relocatable device code a kernel is
+// launched from its own translation unit); launch_event is made of these.  rna / float_input select the kernel's
+// <W1, T> instance: detector preset (3: DNA, 7: RNA) and sample type (int16_t or float).
+int launch_k_seg_plan(hipStream_t st, const EvArgs &a);                                        // event_seg.hip
+int launch_k_event_seg(int rna, bool float_input, hipStream_t st, const EvArgs &a);            // event_seg.hip
+int launch_k_event(int rna, bool float_input, hipStream_t st, const EvArgs &a);                // event_whole.hip
+int launch_k_event_multi(int rna, bool float_input, hipStream_t st, const EvArgs &a);          // event_multi.hip
+int launch_k_event_fallback(int rna, bool float_input, uint32_t n_fb_blocks, hipStream_t st, const EvArgs &a);  // event_fallback.hip
 
 }  // namespace sgk

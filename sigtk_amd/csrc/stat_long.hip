@@ -57,7 +57,7 @@ struct LcCtx {
 // subtool's output (all of it is written behind a read's LAST barrier: whoever passes that one has seen all LC_PARTS
 // arrive, so what it writes is right even if a late workgroup flagged the read meanwhile), and the redo launch of the
 // wave kernel (StatArgs::long_redo, behind the join) takes the read on one wavefront -- the path of every read before
-// round 4.  The event chain treats a timeout the same way (event_kernels.hip, chain_segment).
+// round 4.  The event chain treats a timeout the same way (event_seg.hip, chain_segment).
 // long_fault (tests only, sgk_stat_options_t::debug_fault): 1 | part << 8 | phase << 16: workgroup `part` never arrives
 // at barrier `phase` (1-based) and the spin bound is 2^12; 2 | bound << 8: that spin bound, nobody withheld.
 __device__ inline bool lc_barrier(LcCtx &cx) {

@@ -178,7 +178,7 @@ SGK_TM void sgk_tstat_try_pair(double A1, double A1q, double B1, double B1q, dou
 #endif
 }
 
-// ================================================================ round-2 forms (event_kernels.hip: LazyPass)
+// ================================================================ round-2 forms (event_detect.h: LazyPass)
 // Measured issue costs on gfx950 (tools/valu_rate.hip, profiles/archive/r02_valu_rate.txt): plain f32 add/sub/mul/fma,
 // logic and int add run at 2.3 cycles per wave64 instruction; everything f64, every conversion, v_cmp, v_cndmask,
 // v_max/min and the packed f32 forms take 4.45; v_rsq_f32 8.5; v_rsq_f64 16.2.  The forms below keep the f64 work to
@@ -250,7 +250,7 @@ SGK_TM SgkARole sgk_arole(double S, double Sq) {
 #define SGK_CV_MIN 8.0779356694631609e-28f /* 2^-90: below it (variance floor included) the exact path runs */
 
 // One t-statistic from the B-side window sums (S, Sq: exact) and the ringed A side.  ok == false: evaluate the
-// reference expression instead.  Preconditions (read-level guard, event_kernels.hip): every non-zero |x| in
+// reference expression instead.  Preconditions (read-level guard, event_device.h): every non-zero |x| in
 // [2^-20, 2^20], so window sums are 0 or >= 2^-43, the f32 constant divisions below never see a non-zero dividend
 // under 2^-100, and a non-zero delta is >= 2^-69.
 template <int W>

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Static instruction table of a gfx950 kernel by loop (VERDICT r04 task 1a).
 
-    hipcc ... --cuda-device-only -S -o event.s sigtk_amd/csrc/event_kernels.hip     (tools/isa_phases.py --build does it)
+    hipcc ... --cuda-device-only -S -o event.s sigtk_amd/csrc/event_whole.hip       (tools/isa_phases.py --build does it;
+                                                  k_event_seg: event_seg.hip, k_event_multi: event_multi.hip, k_event_fallback: event_fallback.hip)
     python tools/isa_phases.py event.s _ZN3sgk7k_eventILi3EsEEvNS_6EvArgsE
 
 Finds the natural loops of the function (backward branches), and prints for every loop and for the straight-line code
@@ -105,7 +106,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("asm", nargs="?")
     ap.add_argument("function", nargs="?")
-    ap.add_argument("--build", metavar="HIP_SOURCE", help="compile this source to <asm> first (device only, the library's flags)")
+    ap.add_argument("--build", metavar="HIP_SOURCE", help="compile this source (one kernel's unit, e.g. sigtk_amd/csrc/event_whole.hip) to <asm> first (device only, the library's flags)")
     ap.add_argument("--define", action="append", default=[], help="-D for --build")
     ap.add_argument("--min", type=int, default=40, help="loops with fewer instructions are folded into their parent")
     ap.add_argument("--name", action="append", default=[], help="HEADER_INSTRUCTION_INDEX=name for a loop")

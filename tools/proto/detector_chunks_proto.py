@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Prototype (CPU, plain Python): the speculative chunk scheme of the event detector as an executable specification,
 checked against the sequential automaton (oracle.peaks = src/events.c:371-443) on the statistics of real and synthetic
-reads.  It pins the RULES the kernels follow (sigtk_amd/csrc/event_kernels.hip), not their arithmetic:
+reads.  It pins the RULES the kernels follow (sigtk_amd/csrc/event_device.h, event_detect.h), not their arithmetic:
 
   * a read is cut into spans (segments), a span into chunks; chunk c > 0 of a span starts `lead` indices early from the
     FRESH state and is accepted iff the state it reached at its first index equals the state chunk c-1 ended with;
