@@ -70,7 +70,8 @@ extern "C" {
  *        kernel redoes it (no result depends on the long path having worked; sgk_long_status_t::n_timeouts counts those
  *        reads); sgk_stat_options_t::debug_fault (was reserved[0]); sgk_job_long_declined; sgk_inflate, SGK_SIGNAL_ZREC / sgk_job_begin_zrec;
  *        the six-argument plan call is sgk_event_plan_opt; sgk_event_plan is the 0.1.0 five-argument form again (deprecated).
- * 0.2.3: SGK_JOB_EVENTS_LENGTHS (additive submit flag). */
+ * 0.2.3: SGK_JOB_EVENTS_LENGTHS (additive submit flag).  Additive to 0.2.3 (no version change): sgk_sigtext_decode;
+ *        SGK_SIGNAL_TEXT for sgk_job_begin. */
 #define SGK_VERSION_STRING "0.2.3"
 
 /* ---- error codes --------------------------------------------------------------- */
@@ -372,6 +373,22 @@ int sgk_svbzd_decode(const uint8_t *blobs, const uint64_t *blob_offsets, const u
                      uint32_t n_reads, int16_t *samples, const uint64_t *offsets, const uint32_t *lengths,
                      uint32_t *status, void *stream);
 
+/* ---- text SLOW5: the raw_signal column parsed on the device ------------------------------------------ */
+/* Turns the raw_signal column of text SLOW5 records (slow5lib/src/slow5.c:2754-2778: decimal int16 tokens separated by
+ * ',') into int16 samples, one wavefront per read.  text: 16-byte aligned device buffer; text + text_offsets[r] holds
+ * text_lengths[r] bytes, exactly the column of record r (no tab, no newline), at any byte alignment.  The kernel loads
+ * aligned 16-byte words and never reads outside [text_offsets[r] rounded down to 16, text_offsets[r] + text_lengths[r]
+ * rounded up to 16): pad the buffer by 16 bytes at both ends.  samples/offsets/lengths as in sgk_batch_t; lengths[r] is
+ * what the record announces and is not trusted: nothing is stored at a sample index >= lengths[r].
+ * Accepted tokens, and nothing else: 0 | -?[1-9][0-9]{0,4} with the value in [-32768, 32767]; an empty text is valid
+ * exactly when lengths[r] == 0.  status[r]: 2 when any token is malformed (empty token, leading zero, "-0", a lone or
+ * interior '-', more than five digits, out of range, any other byte), else 1 when the number of tokens is not
+ * lengths[r], else 0.  With a non-zero status the read's own sample range is undefined; nothing outside it is touched.
+ * (slow5lib's slow5_int_check lets '-' appear anywhere in a token, "1-2" parses as 1 there: no writer produces that.) */
+int sgk_sigtext_decode(const uint8_t *text, const uint64_t *text_offsets, const uint32_t *text_lengths,
+                       uint32_t n_reads, int16_t *samples, const uint64_t *offsets, const uint32_t *lengths,
+                       uint32_t *status, void *stream);
+
 /* ---- zlib record inflate on the device (round 5; SURVEY 8f-1 / 8f-2 taken to the record layer) ------------------ */
 /* BLOW5 files compress every record as one zlib stream (slow5lib/src/slow5.c:2583-2598); the reference inflates them one
  * at a time on its one thread, and a pool of host threads is what bounded the drop-in CLI's rate.  sgk_inflate inflates n
@@ -588,6 +605,9 @@ typedef struct sgk_job sgk_job_t;
 #define SGK_SIGNAL_SVBZD 1 /* caller stages svb-zd blobs; decoded on the GPU (8f-1)      */
 #define SGK_SIGNAL_ZREC 2  /* caller stages whole zlib-compressed BLOW5 records (svb-zd signal): inflated and decoded on the
                             * GPU (sgk_job_begin_zrec) */
+#define SGK_SIGNAL_TEXT 3  /* caller stages the raw_signal column of text SLOW5 records (blob_bytes[r] = its byte length) at
+                            * in.blobs + in.blob_offsets[r]; parsed on the GPU (sgk_sigtext_decode; additive to 0.2.3).
+                            * Every sgk_job_submit kind takes it; sgk_job_submit_qts returns SGK_ERR_ARG */
 
 #define SGK_JOB_EVENTS_COMPACT 1 /* submit flag: only event start/length are copied back (event -c) */
 #define SGK_JOB_EVENTS_LENGTHS 2 /* submit flag (0.2.3): only the event lengths are copied back -- ev_start, ev_mean and
@@ -614,7 +634,7 @@ typedef struct sgk_job_output {
     uint32_t n_reads;
     const uint64_t *offsets;        /* as in sgk_job_input_t */
     const uint32_t *lengths;
-    const uint32_t *decode_status;  /* svb-zd input: per-read status of sgk_svbzd_decode, else NULL */
+    const uint32_t *decode_status;  /* svb-zd / text input: per-read status of sgk_svbzd_decode / sgk_sigtext_decode, else NULL */
     const float *pa;                /* pa: pa[offsets[r] + i] */
     const uint64_t *slots;          /* event / jnn: arena slot of read r's first item (n_reads+1) */
     const uint32_t *counts;         /* event / jnn: items of read r */
@@ -639,7 +659,7 @@ int sgk_job_create(int device, sgk_job_t **out);
 int sgk_job_set_options(sgk_job_t *job, const sgk_event_options_t *event_opt, const sgk_stat_options_t *stat_opt);
 void sgk_job_destroy(sgk_job_t *job);
 int sgk_job_device(const sgk_job_t *job);
-/* lengths[r]: samples of read r; blob_bytes[r] (SGK_SIGNAL_SVBZD only): byte length of its blob */
+/* lengths[r]: samples of read r; blob_bytes[r] (SGK_SIGNAL_SVBZD, SGK_SIGNAL_TEXT): byte length of its blob / text column */
 int sgk_job_begin(sgk_job_t *job, uint32_t n_reads, const uint32_t *lengths, int signal_format,
                   const uint32_t *blob_bytes, sgk_job_input_t *in);
 /* The records as they sit in a BLOW5 file with zlib records and svb-zd signal (0.2.2): the caller stages record r's
@@ -657,7 +677,7 @@ int sgk_job_submit(sgk_job_t *job, int tool, int rna, int pore, int flags);
 /* qts over the staged batch: quantise (bits in [1,15], method SGK_QTS_*), then hand the signal back as svb-zd blobs
  * (out_signal_format SGK_SIGNAL_SVBZD) or int16 samples (SGK_SIGNAL_INT16) */
 int sgk_job_submit_qts(sgk_job_t *job, int bits, int method, int out_signal_format);
-/* SGK_ERR_FORMAT if a blob did not decode, SGK_ERR_CAPACITY on event-slot overflow */
+/* SGK_ERR_FORMAT if a blob (a text column) did not decode, SGK_ERR_CAPACITY on event-slot overflow */
 int sgk_job_wait(sgk_job_t *job);
 /* valid after sgk_job_wait until the job's next sgk_job_begin */
 int sgk_job_output(const sgk_job_t *job, sgk_job_output_t *out);

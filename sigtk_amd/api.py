@@ -21,6 +21,7 @@ LIB_PATH = os.environ.get("SIGTK_AMD_LIB", LIB_PATH)
 SGK_OK = 0
 SGK_ERR_NODEVICE = -3
 SGK_ERR_CAPACITY = -5
+SGK_ERR_FORMAT = -8     # a blob / record / text signal column that does not decode
 
 
 class SigtkGpuError(RuntimeError):
@@ -211,6 +212,7 @@ class JobText(C.Structure):      # sgk_job_text_t
 TOOL_PA, TOOL_EVENT, TOOL_STAT, TOOL_JNN, TOOL_PREFIX, TOOL_ENT, TOOL_QTS = range(7)
 ENT_HIST_BYTES = 4 * (4 + 8192 + 4096 + 512)   # sizeof(sgk_ent_hist_t)
 SIGNAL_INT16, SIGNAL_SVBZD = 0, 1
+SIGNAL_TEXT = 3   # the raw_signal column of text SLOW5 records, parsed on the GPU
 JOB_EVENTS_COMPACT = 1
 JOB_TEXT = 4             # pa / event: the rows are written on the device; wait() returns "text" and "row_offsets"
 TEXT_PA, TEXT_EVENT, TEXT_EVENT_COMPACT = 0, 1, 2
@@ -230,7 +232,7 @@ ABI_SYMBOLS = [
     "sgk_event_workspace_bytes_opt", "sgk_event_opt", "sgk_event_pa_opt", "sgk_event_host_opt",
     "sgk_stat_workspace_bytes", "sgk_stat", "sgk_stat_pa", "sgk_jnn_workspace_bytes", "sgk_jnn",
     "sgk_prefix_workspace_bytes", "sgk_prefix", "sgk_stat_opt", "sgk_stat_long_status", "sgk_stat_plan", "sgk_stat_pa_opt", "sgk_jnn_opt", "sgk_prefix_opt",
-    "sgk_stat_host_opt", "sgk_jnn_host_opt", "sgk_prefix_host_opt", "sgk_job_set_options", "sgk_ent", "sgk_ent_finish", "sgk_svbzd_decode",
+    "sgk_stat_host_opt", "sgk_jnn_host_opt", "sgk_prefix_host_opt", "sgk_job_set_options", "sgk_ent", "sgk_ent_finish", "sgk_svbzd_decode", "sgk_sigtext_decode",
     "sgk_qts", "sgk_svbzd_size", "sgk_svbzd_encode", "sgk_synth_reads", "sgk_synth_reads_host",
     "sgk_profile_enable", "sgk_profile_reset", "sgk_profile_read",
     "sgk_event_host", "sgk_events_host_free", "sgk_pa_host", "sgk_stat_host", "sgk_jnn_host",
@@ -344,6 +346,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.sgk_inflate.argtypes = [C.c_void_p] * 3 + [C.c_uint32] + [C.c_void_p] * 6
     L.sgk_svbzd_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p]
+    L.sgk_sigtext_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]
     L.sgk_synth_reads.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int,
                                                      C.c_void_p]
     L.sgk_synth_reads_host.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint64, C.c_uint64, C.c_int]
@@ -652,8 +656,9 @@ def profile_read():
 class Job:
     """A pipelined host job (sgk_job_*): pinned staging + device buffers + stream for one batch at a time.
 
-    `signals` is a list of int16 arrays (SIGNAL_INT16) or of svb-zd blobs as bytes (SIGNAL_SVBZD, with
-    `counts` = samples per read); results come back as numpy copies."""
+    `signals` is a list of int16 arrays (SIGNAL_INT16), of svb-zd blobs as bytes (SIGNAL_SVBZD, with
+    `counts` = samples per read) or of SLOW5 raw_signal text columns as bytes (SIGNAL_TEXT: `counts` and text=True);
+    results come back as numpy copies."""
 
     def __init__(self, device: int = 0):
         self.L = load_library()
@@ -686,10 +691,10 @@ class Job:
         blob = b"".join(raw)
         check(self.L.sgk_job_set_ids(self.h, blob if blob else None, offs.ctypes.data), "sgk_job_set_ids")
 
-    def stage(self, signals, dig, off, rng, counts=None, ids=None):
-        """sgk_job_begin + fill the pinned staging (int16 arrays, or svb-zd blobs when `counts` is given); `ids`: the
-        read ids, for submits with JOB_TEXT"""
-        self._stage(signals, dig, off, rng, counts)
+    def stage(self, signals, dig, off, rng, counts=None, ids=None, text=False):
+        """sgk_job_begin + fill the pinned staging (int16 arrays, or svb-zd blobs when `counts` is given -- with
+        text=True the blobs are SLOW5 raw_signal text columns); `ids`: the read ids, for submits with JOB_TEXT"""
+        self._stage(signals, dig, off, rng, counts, text)
         if ids is not None:
             self.set_ids(ids)
 
@@ -709,14 +714,15 @@ class Job:
         if ids is not None:
             self.set_ids(ids)
 
-    def _stage(self, signals, dig, off, rng, counts=None):
+    def _stage(self, signals, dig, off, rng, counts=None, text=False):
         n = len(signals)
         svb = counts is not None
         lengths = np.asarray(counts if svb else [len(x) for x in signals], dtype=np.uint32)
         blens = np.asarray([len(b) for b in signals], dtype=np.uint32) if svb else None
         jin = JobInput()
-        check(self.L.sgk_job_begin(self.h, n, lengths.ctypes.data, SIGNAL_SVBZD if svb else SIGNAL_INT16,
-                                   blens.ctypes.data if svb else None, C.byref(jin)), "sgk_job_begin")
+        fmt = (SIGNAL_TEXT if text else SIGNAL_SVBZD) if svb else SIGNAL_INT16
+        check(self.L.sgk_job_begin(self.h, n, lengths.ctypes.data, fmt, blens.ctypes.data if svb else None, C.byref(jin)),
+              "sgk_job_begin")
         for r in range(n):
             jin.digitisation[r] = float(dig[r]); jin.offset[r] = float(off[r]); jin.range[r] = float(rng[r])
             if svb:
@@ -738,9 +744,19 @@ class Job:
         check(self.L.sgk_job_submit_qts(self.h, bits, method, SIGNAL_SVBZD if out_svb else SIGNAL_INT16),
               "sgk_job_submit_qts")
 
-    def submit(self, tool: int, signals, dig, off, rng, rna: int = 0, pore: int = 0, flags: int = 0, counts=None, ids=None):
-        self.stage(signals, dig, off, rng, counts, ids)
+    def submit(self, tool: int, signals, dig, off, rng, rna: int = 0, pore: int = 0, flags: int = 0, counts=None, ids=None,
+               text=False):
+        self.stage(signals, dig, off, rng, counts, ids, text)
         self.launch(tool, rna, pore, flags)
+
+    def wait_rc(self):
+        """sgk_job_wait without raising -> (return code, decode_status as a numpy copy or None): for batches that may
+        hold a blob or a text column that does not decode (SGK_ERR_FORMAT; the job stays usable)"""
+        rc = int(self.L.sgk_job_wait(self.h))
+        o = JobOutput()
+        check(self.L.sgk_job_output(self.h, C.byref(o)), "sgk_job_output")
+        ds = _np_from(o.decode_status, o.n_reads, np.uint32).copy() if o.decode_status else None
+        return rc, ds
 
     def wait(self):
         """-> dict of numpy results (per read lists for the variable-length outputs)"""

@@ -1,4 +1,4 @@
-"""Minimal BLOW5 reader/writer (pure Python + numpy + zlib).
+"""Minimal BLOW5 / text SLOW5 reader/writer (pure Python + numpy + zlib).
 
 Convenience for tests, golden generation and bench tooling; the product's host
 reader is the C implementation in ``sigtk_amd/host/blow5.c``.  Both were written
@@ -190,6 +190,77 @@ def write_blow5(path: str, reads: Sequence[Read], attrs: Dict[str, str] | None =
             fh.write(struct.pack("<Q", len(rec)))
             fh.write(rec)
         fh.write(EOF_MARK)
+
+
+# --------------------------------------------------------------------------- text SLOW5
+
+_S5_NAMES = _NAMES.rstrip("\n").split("\t")
+
+
+def _plain_double(x: float) -> str:
+    """plain decimal with the fewest fraction digits that round-trip: slow5lib's reader takes digits, '.' and '-' only
+    (slow5_float_check), so neither repr's exponents nor inf / nan can be written"""
+    x = float(x)
+    if x != x or x in (float("inf"), float("-inf")):
+        raise ValueError("text SLOW5 cannot hold %r" % x)
+    for prec in range(0, 1100):
+        s = "%.*f" % (prec, x)
+        if float(s) == x:
+            return s
+    raise ValueError("no plain decimal form of %r" % x)
+
+
+def slow5_signal_text(raw) -> bytes:
+    """the raw_signal column of a text record: decimal samples separated by ','"""
+    return ",".join(map(str, np.asarray(raw, dtype=np.int16).tolist())).encode("ascii")
+
+
+def write_slow5(path: str, reads: Sequence[Read], attrs: Dict[str, str] | None = None) -> None:
+    """Write a single-read-group text SLOW5 (version 0.2.0) the reference CLI can open."""
+    attrs = dict(attrs or {})
+    with open(path, "wb") as fh:
+        fh.write(b"#slow5_version\t0.2.0\n#num_read_groups\t1\n")
+        fh.write(("".join("@%s\t%s\n" % (k, attrs[k]) for k in sorted(attrs)) + _TYPES + _NAMES).encode("ascii"))
+        for r in reads:
+            raw = np.asarray(r.raw, dtype=np.int16)
+            head = "\t".join([r.read_id, str(int(r.read_group)), _plain_double(r.digitisation), _plain_double(r.offset),
+                              _plain_double(r.range), _plain_double(r.sampling_rate), str(raw.size)])
+            fh.write(head.encode("ascii") + b"\t" + slow5_signal_text(raw) + b"\n")
+
+
+def read_slow5(path: str) -> Blow5:
+    """Read a text SLOW5 file (auxiliary columns are ignored)."""
+    with open(path, "rb") as fh:
+        lines = fh.read().decode("ascii").split("\n")
+    if lines[-1] != "":
+        raise ValueError("text SLOW5: the last line has no newline")
+    lines.pop()
+    if len(lines) < 4 or not lines[0].startswith("#slow5_version\t") or not lines[1].startswith("#num_read_groups\t"):
+        raise ValueError("not a text SLOW5 file")
+    version = tuple(int(x) for x in lines[0].split("\t")[1].split("."))
+    out = Blow5(version, 0, 0, int(lines[1].split("\t")[1]))
+    k = 2
+    while k < len(lines) and lines[k][:1] in "@#":
+        line = lines[k]
+        k += 1
+        if line.startswith("@"):
+            parts = line[1:].split("\t")
+            out.attrs[parts[0]] = parts[1:]
+        elif line.startswith("#read_id"):
+            if line.split("\t")[:8] != _S5_NAMES:
+                raise ValueError("text SLOW5: the eight main columns are not in order")
+            break
+    else:
+        raise ValueError("text SLOW5: no column names line")
+    for line in lines[k:]:
+        c = line.split("\t")
+        if len(c) < 8:
+            raise ValueError("text SLOW5: record with fewer than eight columns")
+        raw = np.array([int(t) for t in c[7].split(",")] if c[7] else [], dtype=np.int64)
+        if raw.size != int(c[6]) or (raw.size and (raw.min() < -32768 or raw.max() > 32767)):
+            raise ValueError("text SLOW5: bad signal in record %s" % c[0])
+        out.reads.append(Read(c[0], int(c[1]), float(c[2]), float(c[3]), float(c[4]), float(c[5]), raw.astype(np.int16)))
+    return out
 
 
 def read_signal_blobs(path: str):

@@ -1,7 +1,7 @@
 // job.hip -- pipelined host jobs (sgk_job_*): the host-side runtime the CLI drives.
 //
 // A job owns everything one batch needs on its way through a GPU: pinned host staging for the
-// signal (raw int16 or svb-zd blobs exactly as they sit in the BLOW5 records), the device
+// signal (raw int16, svb-zd blobs exactly as they sit in the BLOW5 records, or the raw_signal text of SLOW5 records), the device
 // buffers, a private HIP stream, and pinned host buffers for the results.  All buffers only ever
 // grow, so a job that is recycled batch after batch stops allocating after the first few batches.
 //
@@ -177,7 +177,7 @@ static int job_begin(sgk_job_t *j, uint32_t n_reads, const uint32_t *lengths, in
 
 int sgk_job_begin(sgk_job_t *j, uint32_t n_reads, const uint32_t *lengths, int signal_format,
                   const uint32_t *blob_bytes, sgk_job_input_t *in) {
-    if (signal_format != SGK_SIGNAL_INT16 && signal_format != SGK_SIGNAL_SVBZD) return SGK_ERR_ARG;
+    if (signal_format != SGK_SIGNAL_INT16 && signal_format != SGK_SIGNAL_SVBZD && signal_format != SGK_SIGNAL_TEXT) return SGK_ERR_ARG;
     return job_begin(j, n_reads, lengths, signal_format, blob_bytes, nullptr, nullptr, nullptr, in);
 }
 
@@ -220,7 +220,7 @@ static int job_begin(sgk_job_t *j, uint32_t n_reads, const uint32_t *lengths, in
     j->fmt = signal_format;
     j->blob_bytes = 0;
     memset(in, 0, sizeof *in);
-    if (signal_format == SGK_SIGNAL_SVBZD || signal_format == SGK_SIGNAL_ZREC) {
+    if (signal_format == SGK_SIGNAL_SVBZD || signal_format == SGK_SIGNAL_ZREC || signal_format == SGK_SIGNAL_TEXT) {
         if ((rc = j->h_boffs.ensure(nr1 * 8)) != SGK_OK) return rc;
         if ((rc = j->h_blens.ensure(nr1 * 4)) != SGK_OK) return rc;
         uint64_t *bo = j->h_boffs.as<uint64_t>();
@@ -229,9 +229,9 @@ static int job_begin(sgk_job_t *j, uint32_t n_reads, const uint32_t *lengths, in
         for (size_t r = 0; r < nr; ++r) {
             bo[r] = b;
             bl[r] = blob_bytes[r];
-            b += round_up(blob_bytes[r], 8);
+            b += round_up(blob_bytes[r], signal_format == SGK_SIGNAL_TEXT ? 16 : 8);  // (text: 16-byte words, no lead-in)
         }
-        j->blob_bytes = b + 16;  // the decoder reads whole aligned dwords
+        j->blob_bytes = b + 16;  // the decoders read whole aligned words
         if ((rc = j->h_blobs.ensure(j->blob_bytes)) != SGK_OK) return rc;
         in->blobs = j->h_blobs.as<uint8_t>();
         in->blob_offsets = bo;
@@ -336,15 +336,20 @@ static int job_upload(sgk_job_t *j, sgk_batch_t *view) {
         if (rc != SGK_OK) return rc;
         if ((rc = d2h(j->h_dstat, j->d_dstat, nr * 4, st)) != SGK_OK) return rc;
         if ((rc = d2h(j->h_istat, j->d_istat, nr * 4, st)) != SGK_OK) return rc;
-    } else if (j->fmt == SGK_SIGNAL_SVBZD) {
+    } else if (j->fmt == SGK_SIGNAL_SVBZD || j->fmt == SGK_SIGNAL_TEXT) {
         if ((rc = j->d_samples.ensure(j->n_samples * sizeof(int16_t))) != SGK_OK) return rc;
         if ((rc = h2d(j->d_blobs, j->h_blobs, j->blob_bytes, st)) != SGK_OK) return rc;
         if ((rc = h2d(j->d_boffs, j->h_boffs, nr * 8, st)) != SGK_OK) return rc;
         if ((rc = h2d(j->d_blens, j->h_blens, nr * 4, st)) != SGK_OK) return rc;
         if ((rc = j->d_dstat.ensure(nr * 4)) != SGK_OK) return rc;
-        rc = sgk_svbzd_decode(j->d_blobs.as<uint8_t>(), j->d_boffs.as<uint64_t>(), j->d_blens.as<uint32_t>(),
-                              j->n_reads, j->d_samples.as<int16_t>(), j->d_offsets.as<uint64_t>(),
-                              j->d_lengths.as<uint32_t>(), j->d_dstat.as<uint32_t>(), st);
+        if (j->fmt == SGK_SIGNAL_TEXT)  // (d_blobs is 16-byte aligned and blob_bytes holds 16 bytes behind the last column)
+            rc = sgk_sigtext_decode(j->d_blobs.as<uint8_t>(), j->d_boffs.as<uint64_t>(), j->d_blens.as<uint32_t>(),
+                                    j->n_reads, j->d_samples.as<int16_t>(), j->d_offsets.as<uint64_t>(),
+                                    j->d_lengths.as<uint32_t>(), j->d_dstat.as<uint32_t>(), st);
+        else
+            rc = sgk_svbzd_decode(j->d_blobs.as<uint8_t>(), j->d_boffs.as<uint64_t>(), j->d_blens.as<uint32_t>(),
+                                  j->n_reads, j->d_samples.as<int16_t>(), j->d_offsets.as<uint64_t>(),
+                                  j->d_lengths.as<uint32_t>(), j->d_dstat.as<uint32_t>(), st);
         if (rc != SGK_OK) return rc;
         if ((rc = d2h(j->h_dstat, j->d_dstat, nr * 4, st)) != SGK_OK) return rc;
     } else {
@@ -627,6 +632,7 @@ int sgk_job_submit(sgk_job_t *j, int tool, int rna, int pore, int flags) {
 int sgk_job_submit_qts(sgk_job_t *j, int bits, int method, int out_fmt) {
     if (!j || !j->begun || j->submitted) return SGK_ERR_ARG;
     if (out_fmt != SGK_SIGNAL_INT16 && out_fmt != SGK_SIGNAL_SVBZD) return SGK_ERR_ARG;
+    if (j->fmt == SGK_SIGNAL_TEXT) return SGK_ERR_ARG;  // rewriting text records is not part of qts here
     if (bits < 1 || bits > 15 || method < SGK_QTS_FLOOR || method > SGK_QTS_FILL_ONES) return SGK_ERR_ARG;
     SGK_HIP_TRY(hipSetDevice(j->device));
     j->tool = SGK_TOOL_QTS;
@@ -692,7 +698,7 @@ int sgk_job_wait(sgk_job_t *j) {
         }
         if (bad) return SGK_ERR_FORMAT;
     }
-    if (j->fmt == SGK_SIGNAL_SVBZD) {
+    if (j->fmt == SGK_SIGNAL_SVBZD || j->fmt == SGK_SIGNAL_TEXT) {
         const uint32_t *ds = j->h_dstat.as<uint32_t>();
         for (uint32_t r = 0; r < j->n_reads; ++r)
             if (ds[r] != 0) return SGK_ERR_FORMAT;
@@ -751,7 +757,7 @@ int sgk_job_output(const sgk_job_t *j, sgk_job_output_t *out) {
     out->n_reads = j->n_reads;
     out->offsets = j->h_offsets.as<uint64_t>();
     out->lengths = j->h_lengths.as<uint32_t>();
-    out->decode_status = (j->fmt == SGK_SIGNAL_SVBZD || j->fmt == SGK_SIGNAL_ZREC) ? j->h_dstat.as<uint32_t>() : nullptr;
+    out->decode_status = (j->fmt == SGK_SIGNAL_SVBZD || j->fmt == SGK_SIGNAL_ZREC || j->fmt == SGK_SIGNAL_TEXT) ? j->h_dstat.as<uint32_t>() : nullptr;
     if ((j->flags & SGK_JOB_TEXT) && (j->tool == SGK_TOOL_PA || j->tool == SGK_TOOL_EVENT)) {
         out->event_status = j->ev_status;  // the results are the rows: sgk_job_text
         return SGK_OK;

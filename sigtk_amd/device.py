@@ -286,6 +286,35 @@ def svbzd_decode(blobs, counts, device: torch.device):
     return reads, status
 
 
+# ---------------------------------------------------------------------- text SLOW5 signal parse (device API)
+
+def sigtext_decode(texts, counts, device: torch.device):
+    """Parse SLOW5 raw_signal text columns (bytes objects) on the device; counts[r] = the samples read r announces.
+    Every column starts 16-byte aligned; the arena has 16 bytes of padding at both ends.
+    -> (DeviceReads with the parsed samples and zeroed scaling, status tensor [n_reads] int32)"""
+    L = api.load_library()
+    n = len(texts)
+    tlens = np.array([len(t) for t in texts], dtype=np.uint32)
+    toffs = np.zeros(n, dtype=np.int64)
+    pos = 16
+    for i in range(n):
+        pos = (pos + 15) // 16 * 16
+        toffs[i] = pos
+        pos += int(tlens[i])
+    host = np.zeros((pos + 15) // 16 * 16 + 16, dtype=np.uint8)
+    for i, t in enumerate(texts):
+        host[int(toffs[i]):int(toffs[i]) + len(t)] = np.frombuffer(t, dtype=np.uint8)
+    d_text = torch.from_numpy(host).to(device)
+    d_toffs = torch.from_numpy(toffs).to(device)
+    d_tlens = torch.from_numpy(tlens.astype(np.int32)).to(device)
+    reads = alloc_reads(np.asarray(counts, dtype=np.int64), device)
+    status = torch.full((max(n, 1),), -1, dtype=torch.int32, device=device)
+    api.check(L.sgk_sigtext_decode(_ptr(d_text), _ptr(d_toffs), _ptr(d_tlens), n, _ptr(reads.samples),
+                                   _ptr(reads.offsets), _ptr(reads.lengths), _ptr(status), _stream_ptr()),
+              "sgk_sigtext_decode")
+    return reads, status
+
+
 # ---------------------------------------------------------------------- qts + svb-zd encode (device API)
 
 def qts(b: DeviceReads, bits: int, method: int) -> None:

@@ -24,10 +24,174 @@ static int grow(uint8_t **p, uint64_t *cap, uint64_t need) {
     return 0;
 }
 
+/* ------------------------------------------------------------------ text SLOW5 (slow5lib/src/slow5.c:794-881 header,
+ * :2660-2790 record): "#slow5_version\tX.Y.Z", "#num_read_groups\tN", the "@attr" lines, the types line and the names
+ * line -- the last three exactly what a BLOW5 keeps in its header block -- then one record per line, columns separated
+ * by tabs, the signal as decimal numbers separated by commas. */
+
+static const char S5_VERSION_KEY[] = "#slow5_version\t";
+static const char S5_GROUPS_KEY[] = "#num_read_groups\t";
+static const char S5_NAMES[] = "#read_id\tread_group\tdigitisation\toffset\trange\tsampling_rate\tlen_raw_signal\traw_signal";
+
+/* slow5_uint_check (slow5_misc.c:103-120) + strtoull: digits only, no leading zero, no overflow */
+static int s5_uint(const char *p, size_t n, uint64_t *out) {
+    if (n == 0 || n > 20 || (n > 1 && p[0] == '0')) return -1;
+    uint64_t v = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (p[i] < '0' || p[i] > '9') return -1;
+        const uint64_t d = (uint64_t)(p[i] - '0');
+        if (v > (UINT64_MAX - d) / 10) return -1;
+        v = v * 10 + d;
+    }
+    *out = v;
+    return 0;
+}
+
+/* slow5_float_check (slow5_misc.c:141-156) + strtod: digits, '.' and '-' only (no exponent, no inf / nan) */
+static int s5_double(const char *p, size_t n, double *out) {
+    char tmp[64];
+    if (n == 0 || n >= sizeof tmp) return -1;
+    for (size_t i = 0; i < n; i++)
+        if (!((p[i] >= '0' && p[i] <= '9') || p[i] == '.' || p[i] == '-')) return -1;
+    memcpy(tmp, p, n);
+    tmp[n] = '\0';
+    char *end = NULL;
+    *out = strtod(tmp, &end);
+    return end == tmp ? -1 : 0;
+}
+
+int b5_sigtext_decode(const uint8_t *text, uint64_t nbytes, int16_t *dst, uint32_t count) {
+    if (nbytes == 0) return count == 0 ? 0 : B5_ERR_PRESS;
+    uint64_t k = 0, i = 0;
+    for (;;) {  /* one token per round: 0 | -?[1-9][0-9]{0,4}, then ',' or the end */
+        const int neg = i < nbytes && text[i] == '-';
+        if (neg) i++;
+        uint32_t v = 0;
+        int nd = 0;
+        const uint64_t first = i;
+        while (i < nbytes && text[i] >= '0' && text[i] <= '9' && nd < 6) {
+            v = v * 10 + (uint32_t)(text[i] - '0');
+            nd++;
+            i++;
+        }
+        if (nd == 0 || nd > 5) return B5_ERR_PRESS;
+        if (text[first] == '0' && (nd > 1 || neg)) return B5_ERR_PRESS;
+        if (v > 32767u + (uint32_t)neg) return B5_ERR_PRESS;
+        if (i < nbytes && text[i] != ',') return B5_ERR_PRESS;
+        if (k < count) dst[k] = (int16_t)(neg ? -(int32_t)v : (int32_t)v);
+        k++;
+        if (i == nbytes) break;
+        i++;  /* the comma: another token must follow */
+    }
+    return k == count ? 0 : B5_ERR_PRESS;
+}
+
+/* the line at p (n bytes, with or without its newline) -> view.  id_only: the id alone */
+static int s5_parse_line(const uint8_t *p, uint64_t n, b5_view_t *out, int id_only) {
+    if (n && p[n - 1] == '\n') n--;
+    const char *c = (const char *)p, *end = c + n;
+    const char *col[8];
+    size_t len[8];
+    for (int k = 0; k < 8; k++) {
+        const char *t = (const char *)memchr(c, '\t', (size_t)(end - c));
+        if (!t && k < 7) return B5_ERR_FORMAT;  /* fewer than eight columns */
+        col[k] = c;
+        len[k] = t ? (size_t)(t - c) : (size_t)(end - c);  /* (auxiliary columns behind raw_signal are skipped) */
+        if (k == 0) {
+            if (len[0] == 0 || len[0] > 0xffff) return B5_ERR_FORMAT;
+            out->read_id = c;
+            out->id_len = (uint16_t)len[0];
+            if (id_only) return 0;
+        }
+        if (t) c = t + 1;
+    }
+    uint64_t rg, ln;
+    if (s5_uint(col[1], len[1], &rg) || rg > 0xffffffffull) return B5_ERR_FORMAT;
+    if (s5_double(col[2], len[2], &out->digitisation) || s5_double(col[3], len[3], &out->offset) ||
+        s5_double(col[4], len[4], &out->range) || s5_double(col[5], len[5], &out->sampling_rate))
+        return B5_ERR_FORMAT;
+    if (s5_uint(col[6], len[6], &ln) || ln > 0xffffffffull) return B5_ERR_FORMAT;
+    /* a sample takes a digit and all but the last a comma: a short column cannot announce a huge signal.  The announced
+     * length sizes the buffers; whether it is the number of tokens is for the decoder to say, so one more passes. */
+    if (ln > ((uint64_t)len[7] + 1) / 2 + 1) return B5_ERR_FORMAT;
+    out->read_group = (uint32_t)rg;
+    out->rec = p;
+    out->rec_len = n;
+    out->signal = (const uint8_t *)col[7];
+    out->signal_bytes = len[7];
+    out->n_samples = (uint32_t)ln;
+    out->signal_offset = (uint32_t)(col[7] - (const char *)p);
+    return 0;
+}
+
+static int has_ext(const char *path, const char *ext) {
+    const size_t n = strlen(path), e = strlen(ext);
+    return n >= e && strcmp(path + n - e, ext) == 0;
+}
+
+/* the header of a text file, read from the start of fp */
+static b5_file_t *s5_open_text(FILE *fp, const char *path) {
+    b5_file_t *f = (b5_file_t *)calloc(1, sizeof *f);
+    if (!f) { fclose(fp); return NULL; }
+    f->fp = fp;
+    f->path = strdup(path);
+    f->text = 1;
+    rewind(fp);
+    char *line = NULL;
+    size_t cap = 0;
+    ssize_t n;
+    uint64_t hcap = 0, hlen = 0;
+    int lineno = 0, done = 0;
+    while (!done && (n = getline(&line, &cap, fp)) > 0) {
+        if (line[n - 1] != '\n') break;
+        if (lineno == 0) {
+            unsigned a, b, c;
+            char tail;
+            if (strncmp(line, S5_VERSION_KEY, sizeof S5_VERSION_KEY - 1) != 0 ||
+                sscanf(line + sizeof S5_VERSION_KEY - 1, "%u.%u.%u%c", &a, &b, &c, &tail) != 4 || tail != '\n' || a > 255 || b > 255 || c > 255)
+                break;
+            f->version[0] = (uint8_t)a; f->version[1] = (uint8_t)b; f->version[2] = (uint8_t)c;
+        } else if (lineno == 1) {
+            uint64_t g;
+            if (strncmp(line, S5_GROUPS_KEY, sizeof S5_GROUPS_KEY - 1) != 0 ||
+                s5_uint(line + sizeof S5_GROUPS_KEY - 1, (size_t)n - sizeof S5_GROUPS_KEY, &g) || g == 0 || g > 0xffffffffull)
+                break;
+            f->num_read_groups = (uint32_t)g;
+        } else {
+            if (line[0] != '@' && line[0] != '#') break;
+            if (hlen + (uint64_t)n > 0x7fffffffull || grow((uint8_t **)&f->hdr_text, &hcap, hlen + (uint64_t)n + 1)) break;
+            memcpy(f->hdr_text + hlen, line, (size_t)n);
+            hlen += (uint64_t)n;
+            f->hdr_text[hlen] = '\0';
+            if (strncmp(line, "#read_id", 8) == 0) {
+                /* the eight main columns in order; what follows them are auxiliary columns */
+                const size_t k = sizeof S5_NAMES - 1;
+                if ((size_t)n <= k || strncmp(line, S5_NAMES, k) != 0 || (line[k] != '\n' && line[k] != '\t')) break;
+                done = 1;
+            }
+        }
+        lineno++;
+    }
+    free(line);
+    if (!done) { b5_close(f); return NULL; }
+    f->hdr_size = (uint32_t)hlen;
+    f->first_rec = (uint64_t)ftell(fp);
+    return f;
+}
+
 b5_file_t *b5_open(const char *path) {
     FILE *fp = fopen(path, "rb");
     if (!fp) return NULL;
+    /* the format from the extension, as slow5_open does (slow5.c:483-492); any other name: from the first bytes */
+    const int want_text = has_ext(path, ".slow5"), want_bin = has_ext(path, ".blow5");
     uint8_t head[68];
+    const size_t got = fread(head, 1, sizeof S5_VERSION_KEY - 1, fp);
+    const int is_text = got == sizeof S5_VERSION_KEY - 1 && memcmp(head, S5_VERSION_KEY, got) == 0;
+    if (want_text || (is_text && !want_bin)) {
+        if (!is_text) { fclose(fp); return NULL; }
+        return s5_open_text(fp, path);
+    }
+    rewind(fp);
     if (fread(head, 1, 68, fp) != 68 || memcmp(head, B5_MAGIC, 6) != 0) {
         fclose(fp);
         return NULL;
@@ -60,6 +224,7 @@ void b5_close(b5_file_t *f) {
     for (uint64_t i = 0; i < f->n_idx; i++) free(f->idx[i].id);
     free(f->idx);
     free(f->hdr_text);
+    free(f->line);
     free(f->path);
     free(f);
 }
@@ -160,7 +325,36 @@ static int parse_record(const b5_file_t *f, const uint8_t *p, uint64_t n, b5_rec
 }
 
 /* reads the record at the current file position; id_only skips signal decoding when possible */
+static int read_raw_here(b5_file_t *f, uint8_t **buf, uint64_t *len, uint64_t *cap, uint64_t *size);
+
 static int read_record(b5_file_t *f, b5_rec_t *rec, int id_only) {
+    if (f->text) {
+        uint64_t len = 0, size = 0;
+        int rc = read_raw_here(f, &rec->buf, &len, &rec->cap_buf, &size);
+        if (rc) return rc;
+        b5_view_t v;
+        if ((rc = s5_parse_line(rec->buf, size, &v, id_only)) != 0) return rc;
+        char *id = (char *)realloc(rec->read_id, (size_t)v.id_len + 1);
+        if (!id) return B5_ERR_MEM;
+        memcpy(id, v.read_id, v.id_len);
+        id[v.id_len] = '\0';
+        rec->read_id = id;
+        if (id_only) return 0;
+        rec->read_group = v.read_group;
+        rec->digitisation = v.digitisation;
+        rec->offset = v.offset;
+        rec->range = v.range;
+        rec->sampling_rate = v.sampling_rate;
+        if (rec->cap_signal < v.n_samples) {
+            int16_t *q = (int16_t *)realloc(rec->raw_signal, sizeof(int16_t) * ((uint64_t)v.n_samples + 1));
+            if (!q) return B5_ERR_MEM;
+            rec->raw_signal = q;
+            rec->cap_signal = v.n_samples;
+        }
+        if ((rc = b5_sigtext_decode(v.signal, v.signal_bytes, rec->raw_signal, v.n_samples)) != 0) return rc;
+        rec->len_raw_signal = v.n_samples;
+        return 0;
+    }
     uint8_t szb[8];
     const size_t got = fread(szb, 1, 8, f->fp);
     if (got >= 5 && memcmp(szb, B5_EOF_MARK, 5) == 0) {
@@ -404,6 +598,21 @@ void b5_rec_free(b5_rec_t *rec) {
 /* ------------------------------------------------------------------ split API (pipelined reader) */
 
 static int read_raw_here(b5_file_t *f, uint8_t **buf, uint64_t *len, uint64_t *cap, uint64_t *size) {
+    if (f->text) {
+        /* one line, its newline included; a last line without one is a truncated record */
+        size_t lcap = (size_t)f->line_cap;
+        const ssize_t n = getline(&f->line, &lcap, f->fp);
+        f->line_cap = lcap;
+        if (n <= 0) return ferror(f->fp) ? B5_ERR_IO : B5_EOF;
+        if (f->line[n - 1] != '\n' || (uint64_t)n > (1ull << 36)) return B5_ERR_FORMAT;
+        const uint64_t got = (uint64_t)n;
+        const int rc = grow(buf, cap, *len + got);
+        if (rc) return rc;
+        memcpy(*buf + *len, f->line, (size_t)n);
+        *len += got;
+        *size = got;
+        return 0;
+    }
     uint8_t szb[8];
     const size_t got = fread(szb, 1, 8, f->fp);
     if (got >= 5 && memcmp(szb, B5_EOF_MARK, 5) == 0) return got == 5 ? B5_EOF : B5_ERR_FORMAT;
@@ -442,8 +651,12 @@ int b5_get_raw(b5_file_t *f, const char *read_id, uint8_t **buf, uint64_t *len, 
         const uint64_t esize = e->size, len0 = *len;
         if (fseek(f->fp, (long)e->offset, SEEK_SET) != 0) return B5_ERR_IO;
         const int rc = read_raw_here(f, buf, len, cap, size);
-        int fits = rc == 0 && *size + 8 == esize;
-        if (fits && f->record_press == 0) {
+        int fits = rc == 0 && *size + (f->text ? 0 : 8) == esize;
+        if (fits && f->text) {
+            const uint8_t *r = *buf + len0;
+            const size_t idl = strlen(read_id);
+            fits = *size > idl && memcmp(r, read_id, idl) == 0 && r[idl] == '\t';
+        } else if (fits && f->record_press == 0) {
             const uint8_t *r = *buf + len0;
             const size_t idl = strlen(read_id);
             uint16_t have;
@@ -472,6 +685,7 @@ int b5_get_raw(b5_file_t *f, const char *read_id, uint8_t **buf, uint64_t *len, 
 
 int b5_parse_raw(const b5_file_t *f, const uint8_t *raw, uint64_t size, uint8_t **scratch, uint64_t *scratch_cap,
                  b5_view_t *out) {
+    if (f->text) return s5_parse_line(raw, size, out, 0);
     const uint8_t *p = raw;
     uint64_t n = size;
     if (f->record_press == 1) {
@@ -658,6 +872,15 @@ int b5_next_ref(b5_file_t *f, const uint8_t **ptr, uint64_t *size) {
     if (!f->map) return B5_ERR_IO;
     const uint64_t left = f->map_len > f->map_pos ? f->map_len - f->map_pos : 0;
     const uint8_t *p = f->map + f->map_pos;
+    if (f->text) {
+        if (left == 0) return B5_EOF;
+        const uint8_t *nl = (const uint8_t *)memchr(p, '\n', (size_t)left);
+        if (!nl) return B5_ERR_FORMAT;
+        *ptr = p;
+        *size = (uint64_t)(nl - p) + 1;
+        f->map_pos += *size;
+        return 0;
+    }
     if (left >= 5 && memcmp(p, B5_EOF_MARK, 5) == 0) return left == 5 ? B5_EOF : B5_ERR_FORMAT;
     if (left < 8) return B5_ERR_IO;
     uint64_t sz;

@@ -1,9 +1,12 @@
-/* blow5.h -- minimal BLOW5 reader of the sigtk-amd host CLI.
+/* blow5.h -- minimal BLOW5 / text SLOW5 reader of the sigtk-amd host CLI.
  *
  * Written from the on-disk layout; the reference reads the same files
  * through slow5lib (slow5_open / slow5_get_next / slow5_get, slow5lib/include/slow5/slow5.h:345-454).
- * Supports record compression none/zlib and signal compression none/svb-zd; zstd files are
- * rejected (the reference build here has no zstd either).  Auxiliary fields are skipped. */
+ * Binary BLOW5: record compression none/zlib and signal compression none/svb-zd; zstd files are
+ * rejected (the reference build here has no zstd either).  Text SLOW5 (b5_file_t::text; taken from the
+ * ".slow5" extension or the first bytes): one record per line, the eight main columns in order, the
+ * signal column handed on as text (b5_view_t::signal) for the GPU parser or b5_sigtext_decode.
+ * Auxiliary fields are skipped in both. */
 #ifndef SGK_BLOW5_H
 #define SGK_BLOW5_H
 
@@ -25,8 +28,8 @@ typedef struct {
 
 typedef struct {
     char *id;
-    uint64_t offset; /* file offset of the u64 record size */
-    uint64_t size;   /* 8 + record bytes (what the reference's .idx stores) */
+    uint64_t offset; /* file offset of the u64 record size (text: of the line) */
+    uint64_t size;   /* 8 + record bytes (what the reference's .idx stores; text: the line with its newline) */
 } b5_idx_entry_t;
 
 typedef struct {
@@ -44,6 +47,9 @@ typedef struct {
     int idx_from_disk;    /* the index was loaded from "<file>.idx" (checked against what it points at) */
     const uint8_t *map;   /* the whole file mapped read-only (b5_map), or NULL */
     uint64_t map_len, map_pos;
+    char *line;           /* text: the line read last (b5_next / b5_next_raw / b5_get*) */
+    uint64_t line_cap;
+    int text;             /* a text SLOW5 file: hdr_text holds its @attr, types and names lines, a record is a line */
 } b5_file_t;
 
 #define B5_EOF (-1)
@@ -77,14 +83,14 @@ typedef struct {
     double digitisation, offset, range, sampling_rate;
     const uint8_t *rec;    /* the whole (inflated) record and its length: qts rewrites the signal and keeps the rest */
     uint64_t rec_len;
-    const uint8_t *signal; /* svb-zd blob (signal_press 1) or little-endian int16 samples */
+    const uint8_t *signal; /* svb-zd blob (signal_press 1), little-endian int16 samples, or (text) the raw_signal column */
     uint64_t signal_bytes;
-    uint32_t n_samples;    /* from the blob's count word, or signal_bytes / 2 */
+    uint32_t n_samples;    /* from the blob's count word, or signal_bytes / 2; text: len_raw_signal as the record announces it */
     uint32_t signal_offset; /* of the signal inside the inflated record (b5_parse_head: `rec` / `signal` are NULL there) */
 } b5_view_t;
 
-/* appends the next record's on-disk bytes (without the u64 size) to *buf at *len (realloc'd as needed);
- * *size receives their length.  0 ok, B5_EOF, or an error. */
+/* appends the next record's on-disk bytes (without the u64 size; text: the line with its newline) to *buf at *len
+ * (realloc'd as needed); *size receives their length.  0 ok, B5_EOF, or an error. */
 int b5_next_raw(b5_file_t *f, uint8_t **buf, uint64_t *len, uint64_t *cap, uint64_t *size);
 int b5_get_raw(b5_file_t *f, const char *read_id, uint8_t **buf, uint64_t *len, uint64_t *cap, uint64_t *size);
 /* Zero-copy variant of b5_next_raw: maps the file once (b5_map; returns non-zero if that is not possible, the
@@ -107,5 +113,10 @@ int b5_parse_head(const b5_file_t *f, const uint8_t *raw, uint64_t size, uint8_t
 int64_t b5_aux_fixed_bytes(const b5_file_t *f);
 /* scalar streamvbyte + zigzag-delta decode of one blob into dst[count] (host-decode fallback path) */
 int b5_svb_zd_decode(const uint8_t *blob, uint64_t nbytes, int16_t *dst, uint32_t count);
+/* scalar parse of a text SLOW5 raw_signal column (nbytes of text, no tab or newline) into dst[count]: the grammar of
+ * the GPU parser (sgk_sigtext_decode) -- tokens 0 | -?[1-9][0-9]{0,4} in [-32768, 32767] separated by ',', an empty
+ * text exactly when count is 0.  0, or B5_ERR_PRESS for a malformed token or a token count other than `count`;
+ * nothing is written behind dst[count - 1]. */
+int b5_sigtext_decode(const uint8_t *text, uint64_t nbytes, int16_t *dst, uint32_t count);
 
 #endif

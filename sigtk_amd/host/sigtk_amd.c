@@ -12,6 +12,8 @@
  * decoded there.  Several batches are in flight (one per GPU plus two), a writer thread formats the
  * rows of finished batches on a pool of threads (exact fast number formatting, fmt.h) and emits them
  * in file order.  Whole batches are the multi-GPU sharding unit: no collective.
+ * Text SLOW5 files (.slow5) go the same way: a record is a line, its signal column is handed to the GPU as text and
+ * parsed there (k_sigtext_decode), or by the pool with --host-decode.
  * Extra options: --gpus N, --batch-samples M, -t/--threads T, --host-decode.
  */
 #include <getopt.h>
@@ -312,6 +314,7 @@ typedef struct batch {
     uint32_t *lengths, *blob_bytes;
     uint32_t *sig_off, *sig_len, *room; /* zrec: where the signal sits in the inflated record, its bytes, the record's inflated size */
     int svb;        /* signal staged as svb-zd blobs (GPU decode) */
+    int sigtext;    /* signal staged as the raw_signal column of text SLOW5 records (GPU parse) */
     int zrec;       /* whole zlib records staged: inflated and decoded on the GPU */
     int last;       /* sentinel: no more batches */
     uint8_t *id_blob;   /* --gpu-text: the batch's read ids back to back, id r at id_offs[r] .. id_offs[r + 1] */
@@ -438,8 +441,10 @@ static void load_stage(void *ctx_, uint32_t i, int tid) {
     b->in.range[i] = r->v.range;
     if (b->zrec) {
         memcpy(b->in.blobs + b->in.blob_offsets[i], r->raw_ptr ? r->raw_ptr : b->raw + r->raw_off, r->raw_size);
-    } else if (b->svb) {
+    } else if (b->svb || b->sigtext) {
         memcpy(b->in.blobs + b->in.blob_offsets[i], r->v.signal, r->v.signal_bytes);
+    } else if (c->P->f->text) {
+        r->err = b5_sigtext_decode(r->v.signal, r->v.signal_bytes, b->in.samples + b->in.offsets[i], r->v.n_samples);
     } else if (c->P->f->signal_press == 1) {
         r->err = b5_svb_zd_decode(r->v.signal, r->v.signal_bytes, b->in.samples + b->in.offsets[i], r->v.n_samples);
     } else {
@@ -457,6 +462,10 @@ static void batch_launch(pipe_t *P, batch_t *b) {
             fprintf(stderr, "Error in slow5_get_next. Error code %d\n", b->recs[i].err);
             die_now();
         }
+        if (P->f->text && (b->recs[i].v.signal_bytes > 0xffffffffull || b->recs[i].v.n_samples > 0x7fffffffu)) {
+            fprintf(stderr, "Error in slow5_get_next. Error code %d\n", B5_ERR_FORMAT);
+            die_now();
+        }
         b->lengths[i] = b->recs[i].v.n_samples;
         b->blob_bytes[i] = P->zrec ? (uint32_t)b->recs[i].raw_size : (uint32_t)b->recs[i].v.signal_bytes;
         if (P->zrec) {
@@ -470,10 +479,11 @@ static void batch_launch(pipe_t *P, batch_t *b) {
     double t1 = realtime();
     P->t_parse += t1 - t0;
     b->svb = P->f->signal_press == 1 && !P->host_decode;
+    b->sigtext = P->f->text && !P->host_decode;
     b->zrec = P->zrec;
     int rc;
     if (b->zrec) rc = sgk_job_begin_zrec(b->job, b->n, b->lengths, b->blob_bytes, b->sig_off, b->sig_len, b->room, &b->in);
-    else rc = sgk_job_begin(b->job, b->n, b->lengths, b->svb ? SGK_SIGNAL_SVBZD : SGK_SIGNAL_INT16, b->blob_bytes, &b->in);
+    else rc = sgk_job_begin(b->job, b->n, b->lengths, b->sigtext ? SGK_SIGNAL_TEXT : (b->svb ? SGK_SIGNAL_SVBZD : SGK_SIGNAL_INT16), b->blob_bytes, &b->in);
     if (rc != SGK_OK) gpu_fail("sgk_job_begin", rc);
     pfor(P->load_pool, b->n, load_stage, &c);
     for (uint32_t i = 0; i < b->n; i++) {
@@ -793,8 +803,9 @@ static void *writer_main(void *arg) {
         if (b->last) break;
         double t0 = realtime();
         int rc = sgk_job_wait(b->job);
-        if (rc == SGK_ERR_FORMAT && b->zrec) {
-            /* a record that does not inflate (or not to what its head announced), or a blob that does not decode: what the
+        if (rc == SGK_ERR_FORMAT && (b->zrec || b->sigtext)) {
+            /* a record that does not inflate (or not to what its head announced), a blob that does not decode, or a text
+             * signal column with a malformed token or another number of tokens than the record announces: what the
              * reference reports for it (slow5_get_next's negative return, src/cmain.c:121-124) */
             fprintf(stderr, "Error in slow5_get_next. Error code %d\n", B5_ERR_PRESS);
             die_now();
@@ -1100,7 +1111,7 @@ static int cmain(int argc, char *argv[], const char *mode_s) {
         fprintf(fp_help, "   --gpus INT                 number of GPUs; whole batches go round-robin [1]\n");
         fprintf(fp_help, "   --batch-samples INT        approximate raw samples per batch [134217728; with --host-inflate 16777216, jnn / prefix 67108864]\n");
         fprintf(fp_help, "   -t, --threads INT          host threads for inflating records / formatting rows [auto]\n");
-        fprintf(fp_help, "   --host-decode              decode svb-zd signals on the host instead of the GPU\n");
+        fprintf(fp_help, "   --host-decode              decode svb-zd signals (parse text SLOW5 signals) on the host instead of the GPU\n");
         fprintf(fp_help, "   --host-inflate             inflate zlib records on the host threads instead of the GPU\n");
         fprintf(fp_help, "   --gpu-text                 pa / event, whole-file mode: format the rows on the GPU and fetch them as text\n");
         exit(fp_help == stdout ? EXIT_SUCCESS : EXIT_FAILURE);
@@ -1169,14 +1180,15 @@ static int cmain(int argc, char *argv[], const char *mode_s) {
      * auxiliary fields have a fixed size (the inflated length of a record then follows from its head); everything else
      * -- and --host-inflate / --host-decode -- is inflated by the host threads as before. */
     P.aux_bytes = b5_aux_fixed_bytes(f);
-    P.zrec = !host_inflate && !host_decode && f->record_press == 1 && f->signal_press == 1 && P.aux_bytes >= 0;
+    P.zrec = !f->text && !host_inflate && !host_decode && f->record_press == 1 && f->signal_press == 1 && P.aux_bytes >= 0;
     /* ... in batches of 128 M samples: the inflate kernel is a wavefront per record and takes ~35 ms however many records
      * it has (up to the ~4 800 the GPU holds at once), so a batch should bring a thousand of them (1e10 samples of `stat`:
      * 5.2 s with the 16 M-sample batches of the host path, 1.7 s with 128 M, profiles/r05_cli_steady.json) */
     if (P.zrec && !batch_set) batch_samples = 128ull << 20;
     P.opt = opt;
     P.out_fp = stdout;
-    P.limit_bytes = batch_samples;
+    /* (the limit counts on-disk bytes: about one per sample in a BLOW5, four to five in a text file) */
+    P.limit_bytes = f->text ? batch_samples * 4 : batch_samples;
     P.ids = argv + optind + 1;
     P.n_ids = argc - optind - 1;
     /* rows as text from the GPU: the three large-output grammars, when the whole file is read in order (with read ids
@@ -1254,9 +1266,20 @@ static int qtsmain(int argc, char *argv[]) {
         fprintf(stderr, "Unknown method for -m. Available options are floor,round,fill-ones.\n");
         die_now();
     }
+    {   /* records are rewritten byte for byte around the new signal: text records (their auxiliary columns) are not */
+        const size_t ni = strlen(argv[optind]), no = strlen(out_fn);
+        if ((ni >= 6 && strcmp(argv[optind] + ni - 6, ".slow5") == 0) || (no >= 6 && strcmp(out_fn + no - 6, ".slow5") == 0)) {
+            fprintf(stderr, "Error: qts on text SLOW5 files is not supported: use BLOW5 for the input and the output\n");
+            die_now();
+        }
+    }
     b5_file_t *f = b5_open(argv[optind]);
     if (!f) {
         fprintf(stderr, "Error in opening file\n");
+        die_now();
+    }
+    if (f->text) {
+        fprintf(stderr, "Error: qts on text SLOW5 files is not supported: use BLOW5 for the input and the output\n");
         die_now();
     }
     FILE *out = fopen(out_fn, "wb");
@@ -1340,6 +1363,7 @@ static int dumpmain(int argc, char *argv[]) {
         if (ret == 0) {
             int16_t *sig = (int16_t *)malloc(sizeof(int16_t) * (v.n_samples ? v.n_samples : 1));
             if (!sig) ret = -1;
+            else if (f->text) ret = b5_sigtext_decode(v.signal, v.signal_bytes, sig, v.n_samples);
             else if (f->signal_press == 1) ret = b5_svb_zd_decode(v.signal, v.signal_bytes, sig, v.n_samples);
             else if (v.signal_bytes != 2 * (uint64_t)v.n_samples) ret = -1;  /* (a malformed record: the copy would overrun) */
             else memcpy(sig, v.signal, v.signal_bytes);
@@ -1384,7 +1408,10 @@ static int dumpmain(int argc, char *argv[]) {
                 if (!sig) die_mem();
                 sig_cap = v.n_samples;
             }
-            if (f->signal_press == 1) {
+            if (f->text) {
+                ret = b5_sigtext_decode(v.signal, v.signal_bytes, sig, v.n_samples);
+                if (ret < 0) break;
+            } else if (f->signal_press == 1) {
                 ret = b5_svb_zd_decode(v.signal, v.signal_bytes, sig, v.n_samples);
                 if (ret < 0) break;
             } else if (v.n_samples) {
