@@ -71,7 +71,7 @@ extern "C" {
  *        reads); sgk_stat_options_t::debug_fault (was reserved[0]); sgk_job_long_declined; sgk_inflate, SGK_SIGNAL_ZREC / sgk_job_begin_zrec;
  *        the six-argument plan call is sgk_event_plan_opt; sgk_event_plan is the 0.1.0 five-argument form again (deprecated).
  * 0.2.3: SGK_JOB_EVENTS_LENGTHS (additive submit flag).  Additive to 0.2.3 (no version change): sgk_sigtext_decode;
- *        SGK_SIGNAL_TEXT for sgk_job_begin. */
+ *        SGK_SIGNAL_TEXT for sgk_job_begin; sgk_ss_* (`ss paf2tsv`: decode, text, host pipe). */
 #define SGK_VERSION_STRING "0.2.3"
 
 /* ---- error codes --------------------------------------------------------------- */
@@ -521,6 +521,91 @@ int sgk_sref_pipe_begin(sgk_sref_pipe_t *pipe, int slot, uint64_t n_bases, uint3
                         uint64_t name_bytes, sgk_sref_stage_t *out);
 int sgk_sref_pipe_submit(sgk_sref_pipe_t *pipe, int slot);
 int sgk_sref_pipe_wait(sgk_sref_pipe_t *pipe, int slot, const uint8_t **text, uint64_t *n_bytes);
+
+/* ---- ss: signal-alignment strings to k-mer rows (csrc/ss_kernels.hip) --------------------------------- */
+/* `sigtk ss paf2tsv` (src/ss.c:124-197).  A record is one PAF line: its ss:Z: string and the columns start_raw, end_raw,
+ * start_kmer, end_kmer and tlen.  st_k = min(start_kmer, end_kmer), end_k = max, rna = start_kmer > end_kmer.
+ * Grammar: tokens <digits><op>, op one of ',' 'I' 'D'.  With i_k = st_k and i_raw = start_raw at the start,
+ *   nI: i_raw += n     nD: i_k += n     n,: k-mer i_k gets the pair (i_raw, i_raw + n); i_raw += n; i_k += 1
+ * Leading zeros are allowed, "0," is an empty mapping, digits behind the last op are ignored.
+ * status, the first that applies:
+ *   1  an op with no digit in front of it          }  of these two the one at the lower byte position
+ *   2  a byte that is neither a digit nor an op    }
+ *   5  a run of more than 10 digits in front of an op, a number above INT32_MAX, or i_raw / i_k above INT32_MAX
+ *      (undefined in the reference: buff[11] and int overflow)
+ *   3  i_raw != end_raw at the end
+ *   4  i_k != end_k at the end
+ *   0  ok
+ * ends: the final (i_raw, i_k), or (-1, -1) with status 1, 2 or 5.
+ * The unit of work is a span: k-mers st_k + first .. st_k + first + count of one record; one wavefront parses the
+ * record's whole string for every span of it (a record may expand 8 bytes into 10^6 rows, so rows are budgeted by span,
+ * never by what a line claims).  A span's pairs go to pairs[2 * (out_offsets[s] + j)], j < count, (start, end) of k-mer
+ * st_k + first + j; the caller fills the table with -1 beforehand and a k-mer no ',' reached keeps (-1, -1).  A pair is
+ * stored only at j < count, whatever the string says.  With a non-zero status the span's own table range is undefined;
+ * nothing outside it is touched.  status and ends are indexed by SPAN (status[s], ends[2 s], ends[2 s + 1]); with
+ * spans == NULL every record is one span of count 0 (n_spans is ignored): validation, nothing is stored.
+ * start_raw and st_k must not be negative (a pair of -1 reads as "not mapped"); the kernel is memory-safe regardless.
+ * ss: 16-byte aligned device buffer, readable up to n_ss_bytes rounded up to a multiple of 16.  A record's string is
+ * ss[ss_offset .. ss_offset + ss_len), at any byte alignment, without the "ss:Z:" prefix.  The kernel loads aligned
+ * 16-byte words below round_up(n_ss_bytes, 16) only; bytes of a string that lie behind n_ss_bytes read as invalid
+ * bytes (status 2).  ss_len < 2^32 - 16.
+ * Rows of a span's text: "id \t idx \t start \t end \n" per k-mer i, ascending, idx = rna ? tlen - i - 1 : i (computed in
+ * 64 bits, may be negative), start and end "." for a k-mer that is not mapped; id = ids[record.id].  Text is made from
+ * the pair table; measure / write / sgk_text_status work as for sgk_sref_text_* (n_rows_capacity: the sum of the spans'
+ * counts or more).  Only spans of records whose status is 0 may be given to the text calls. */
+typedef struct sgk_ss_record {
+    uint64_t ss_offset;
+    uint32_t ss_len;
+    int32_t start_raw, end_raw;
+    int32_t st_k, end_k; /* st_k <= end_k */
+    int32_t tlen;
+    uint32_t rna; /* 0 / 1 */
+    uint32_t id;  /* index into the ids */
+} sgk_ss_record_t;
+typedef struct sgk_ss_span {
+    uint32_t record;
+    uint32_t first, count; /* k-mers st_k + first .. st_k + first + count */
+    uint32_t reserved;
+} sgk_ss_span_t;
+typedef struct sgk_ss_batch {
+    const uint8_t *ss; /* device */
+    uint64_t n_ss_bytes;
+    const sgk_ss_record_t *records; /* device */
+    const sgk_ss_span_t *spans;     /* device; NULL (decode only): one span of count 0 per record */
+    uint32_t n_records, n_spans;
+} sgk_ss_batch_t;
+int sgk_ss_decode(const sgk_ss_batch_t *batch, const uint64_t *out_offsets /* n_spans, in pairs */, int32_t *pairs,
+                  uint32_t *status, int32_t *ends, void *stream);
+size_t sgk_ss_text_workspace_bytes(uint32_t n_spans, uint64_t n_rows_capacity);
+int sgk_ss_text_measure(const sgk_ss_batch_t *batch, const uint64_t *out_offsets, const int32_t *pairs,
+                        const sgk_text_ids_t *ids, uint64_t *row_offsets /* n_spans + 1 */, void *workspace,
+                        size_t workspace_bytes, void *stream);
+int sgk_ss_text_write(const sgk_ss_batch_t *batch, const uint64_t *out_offsets, const int32_t *pairs,
+                      const sgk_text_ids_t *ids, uint8_t *text, uint64_t text_capacity, void *workspace,
+                      size_t workspace_bytes, void *stream);
+/* Host pipe for the CLI, in the manner of sgk_sref_pipe_*: two slots, begin -> (fill the pinned staging) -> submit ->
+ * wait.  The caller cuts the records into spans of at most its row budget per batch; a record larger than the budget is
+ * given again, with its next span, in the next batch.  submit uploads, validates every record (status), keeps the spans
+ * in front of the first record whose status is not 0, and only then sizes the pair table and the text for them: device
+ * memory follows the caller's budget and the strings' verdict, not the columns of a line.  It then decodes, measures,
+ * writes and starts the download.  wait returns the text of the kept spans (pinned, valid until the slot's next begin)
+ * and the first bad record of the batch with its status (bad_record = UINT32_MAX: none).
+ * id i is id_bytes[id_offsets[i] .. id_offsets[i + 1]); records[r].ss_offset is relative to `ss`. */
+typedef struct sgk_ss_pipe sgk_ss_pipe_t;
+typedef struct sgk_ss_stage {
+    uint8_t *ss;              /* n_ss_bytes */
+    sgk_ss_record_t *records; /* n_records */
+    sgk_ss_span_t *spans;     /* n_spans, ascending record */
+    uint8_t *id_bytes;
+    uint32_t *id_offsets; /* n_ids + 1 */
+} sgk_ss_stage_t;
+int sgk_ss_pipe_create(int device, sgk_ss_pipe_t **out);
+void sgk_ss_pipe_destroy(sgk_ss_pipe_t *pipe);
+int sgk_ss_pipe_begin(sgk_ss_pipe_t *pipe, int slot, uint64_t n_ss_bytes, uint32_t n_records, uint32_t n_spans,
+                      uint32_t n_ids, uint64_t id_bytes, sgk_ss_stage_t *out);
+int sgk_ss_pipe_submit(sgk_ss_pipe_t *pipe, int slot);
+int sgk_ss_pipe_wait(sgk_ss_pipe_t *pipe, int slot, const uint8_t **text, uint64_t *n_bytes, uint32_t *bad_record,
+                     uint32_t *bad_status);
 
 /* ---- synthetic reads (BASELINE configs 2-5) ---------------------------- */
 /* Deterministic counter-based generator, identical on host and device (integer only).

@@ -20,6 +20,7 @@ LIB_PATH = os.environ.get("SIGTK_AMD_LIB", LIB_PATH)
 
 SGK_OK = 0
 SGK_ERR_NODEVICE = -3
+SGK_ERR_WORKSPACE = -4
 SGK_ERR_CAPACITY = -5
 SGK_ERR_FORMAT = -8     # a blob / record / text signal column that does not decode
 
@@ -205,6 +206,31 @@ class SrefStage(C.Structure):    # sgk_sref_stage_t (pinned host pointers)
     _fields_ = [("bases", C.c_void_p), ("spans", C.c_void_p), ("name_bytes", C.c_void_p), ("name_offsets", C.c_void_p)]
 
 
+class SsRecord(C.Structure):     # sgk_ss_record_t
+    _fields_ = [("ss_offset", C.c_uint64), ("ss_len", C.c_uint32), ("start_raw", C.c_int32), ("end_raw", C.c_int32),
+                ("st_k", C.c_int32), ("end_k", C.c_int32), ("tlen", C.c_int32), ("rna", C.c_uint32), ("id", C.c_uint32)]
+
+
+class SsSpan(C.Structure):       # sgk_ss_span_t
+    _fields_ = [("record", C.c_uint32), ("first", C.c_uint32), ("count", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+#: sgk_ss_record_t (40 bytes) and sgk_ss_span_t (16 bytes) as numpy records
+SS_RECORD_DTYPE = np.dtype([("ss_offset", "<u8"), ("ss_len", "<u4"), ("start_raw", "<i4"), ("end_raw", "<i4"), ("st_k", "<i4"),
+                            ("end_k", "<i4"), ("tlen", "<i4"), ("rna", "<u4"), ("id", "<u4")])
+SS_SPAN_DTYPE = np.dtype([("record", "<u4"), ("first", "<u4"), ("count", "<u4"), ("reserved", "<u4")])
+
+
+class SsBatch(C.Structure):      # sgk_ss_batch_t (device pointers)
+    _fields_ = [("ss", C.c_void_p), ("n_ss_bytes", C.c_uint64), ("records", C.c_void_p), ("spans", C.c_void_p),
+                ("n_records", C.c_uint32), ("n_spans", C.c_uint32)]
+
+
+class SsStage(C.Structure):      # sgk_ss_stage_t (pinned host pointers)
+    _fields_ = [("ss", C.c_void_p), ("records", C.c_void_p), ("spans", C.c_void_p), ("id_bytes", C.c_void_p),
+                ("id_offsets", C.c_void_p)]
+
+
 class JobText(C.Structure):      # sgk_job_text_t
     _fields_ = [("text", C.c_void_p), ("row_offsets", C.POINTER(C.c_uint64)), ("n_bytes", C.c_uint64)]
 
@@ -246,6 +272,9 @@ ABI_SYMBOLS = [
     # sref: the synthetic reference signal as floats and as rows (csrc/sref_kernels.hip)
     "sgk_sref_levels", "sgk_sref_text_workspace_bytes", "sgk_sref_text_measure", "sgk_sref_text_write",
     "sgk_sref_pipe_create", "sgk_sref_pipe_destroy", "sgk_sref_pipe_begin", "sgk_sref_pipe_submit", "sgk_sref_pipe_wait",
+    # ss paf2tsv: signal-alignment strings to k-mer rows (csrc/ss_kernels.hip)
+    "sgk_ss_decode", "sgk_ss_text_workspace_bytes", "sgk_ss_text_measure", "sgk_ss_text_write",
+    "sgk_ss_pipe_create", "sgk_ss_pipe_destroy", "sgk_ss_pipe_begin", "sgk_ss_pipe_submit", "sgk_ss_pipe_wait",
     # per-read shims with the reference's signatures (csrc/shims.hip)
     "sgk_jnn_raw", "sgk_jnn_pa", "sgk_jnnv2", "sgk_find_adaptor", "sgk_find_polya",
     "sgk_meanf", "sgk_meani16", "sgk_stdvf", "sgk_stdvi16", "sgk_medianf", "sgk_mediani16", "sgk_shim_status",
@@ -278,6 +307,23 @@ def sref_spans(seq_lens, k: int, rna: bool = False, max_span: Optional[int] = No
                 recs.append((int(starts[i]), 0, l, lo, hi - lo, i, strand, (0,) * 7))
                 rows.append(row)
     return np.array(recs, dtype=SREF_SPAN_DTYPE), np.asarray(rows, dtype=np.int64)
+
+
+def ss_spans(rows, max_span: Optional[int] = None, cuts=None):
+    """The spans (SS_SPAN_DTYPE) of records with the given row counts (end_k - st_k): every record's k-mer range cut at
+    every multiple of max_span and at every position of `cuts` that falls inside it; a record without rows is one span of
+    count 0.  Spans are in record order."""
+    recs = []
+    for r, n in enumerate(int(x) for x in rows):
+        b = {0, n}
+        if max_span and n > 0:
+            b.update(range(max_span, n, max_span))
+        if cuts is not None:
+            b.update(int(c) for c in cuts if 0 < int(c) < n)
+        bounds = sorted(b) if n > 0 else [0, 0]
+        for lo, hi in zip(bounds[:-1], bounds[1:]):
+            recs.append((r, lo, hi - lo, 0))
+    return np.array(recs, dtype=SS_SPAN_DTYPE)
 
 
 def event_slots_for(n):
@@ -393,6 +439,21 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.sgk_sref_pipe_begin.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(SrefStage)]
     L.sgk_sref_pipe_submit.argtypes = [C.c_void_p, C.c_int]
     L.sgk_sref_pipe_wait.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.sgk_ss_decode.argtypes = [C.POINTER(SsBatch)] + [C.c_void_p] * 5
+    L.sgk_ss_text_workspace_bytes.restype = C.c_size_t
+    L.sgk_ss_text_workspace_bytes.argtypes = [C.c_uint32, C.c_uint64]
+    L.sgk_ss_text_measure.argtypes = [C.POINTER(SsBatch), C.c_void_p, C.c_void_p, C.POINTER(TextIds), C.c_void_p, C.c_void_p,
+                                      C.c_size_t, C.c_void_p]
+    L.sgk_ss_text_write.argtypes = [C.POINTER(SsBatch), C.c_void_p, C.c_void_p, C.POINTER(TextIds), C.c_void_p, C.c_uint64,
+                                    C.c_void_p, C.c_size_t, C.c_void_p]
+    L.sgk_ss_pipe_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+    L.sgk_ss_pipe_destroy.argtypes = [C.c_void_p]
+    L.sgk_ss_pipe_destroy.restype = None
+    L.sgk_ss_pipe_begin.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                    C.POINTER(SsStage)]
+    L.sgk_ss_pipe_submit.argtypes = [C.c_void_p, C.c_int]
+    L.sgk_ss_pipe_wait.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+                                   C.POINTER(C.c_uint32)]
     L.sgk_event_host.argtypes = [C.POINTER(HostBatch), C.c_int, C.POINTER(EventsHost)]
     L.sgk_event_host_opt.argtypes = L.sgk_event_host.argtypes + [OE]
     L.sgk_events_host_free.argtypes = [C.POINTER(EventsHost)]

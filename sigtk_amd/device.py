@@ -563,6 +563,149 @@ class SrefText(SrefBatch):
         return text[:total].cpu().numpy().tobytes()
 
 
+# ---------------------------------------------------------------------- ss paf2tsv (sgk_ss_*)
+
+SS_CANARY = 0x5a5a5a5a
+
+
+class SsBatch:
+    """Records of `ss paf2tsv` on the device.  A record is any object with the attributes rid, ss (bytes), start_raw,
+    end_raw, st_k, end_k, tlen and rna (tests/ss_model.py: Record).  Its k-mer range is cut into spans by api.ss_spans
+    (max_span / cuts), or `spans` gives them.  aligns[r] in 0..15: the byte alignment of string r in the buffer (default
+    r % 16); the bytes between strings are digits, so a read outside a string would show.  gap: pair-table entries left
+    between the spans' ranges and at both ends, filled with SS_CANARY; the ranges themselves are filled with -1."""
+
+    def __init__(self, records, max_span: Optional[int] = None, cuts=None, spans=None, aligns=None, gap: int = 0,
+                 device: Optional[torch.device] = None):
+        dev = device or torch.device("cuda", torch.cuda.current_device())
+        self.device, self.records = dev, list(records)
+        n = len(self.records)
+        rec = np.zeros(n, dtype=api.SS_RECORD_DTYPE)
+        pos, chunks = 16, [b"7" * 16]
+        for r, x in enumerate(self.records):
+            al = int(aligns[r]) if aligns is not None else r % 16
+            pad = (-pos) % 16 + al
+            chunks.append(b"7" * pad)
+            pos += pad
+            rec[r] = (pos, len(x.ss), x.start_raw, x.end_raw, x.st_k, x.end_k, x.tlen, x.rna, r)
+            chunks.append(bytes(x.ss))
+            pos += len(x.ss)
+        chunks.append(b"7" * ((-pos) % 16 + 16))
+        blob = np.frombuffer(b"".join(chunks), dtype=np.uint8).copy()
+        self.n_ss_bytes = blob.size - 16
+        self.records_host = rec
+        self.spans_host = np.asarray(spans, dtype=api.SS_SPAN_DTYPE) if spans is not None else \
+            api.ss_spans([x.end_k - x.st_k for x in self.records], max_span, cuts)
+        self.n_records, self.n_spans = n, int(self.spans_host.size)
+        counts = self.spans_host["count"].astype(np.int64) if self.n_spans else np.zeros(0, dtype=np.int64)
+        self.n_rows = int(counts.sum())
+        self.offsets_host = np.zeros(self.n_spans, dtype=np.int64)
+        pos = gap
+        table = np.full((gap + self.n_rows + (self.n_spans + 1) * gap + 2, 2), SS_CANARY, dtype=np.int32)
+        for s in range(self.n_spans):
+            self.offsets_host[s] = pos
+            table[pos:pos + int(counts[s])] = -1
+            pos += int(counts[s]) + gap
+        self.table_filled = table.copy()
+        self.ss = torch.from_numpy(blob).to(dev)
+        assert _ptr(self.ss) % 16 == 0
+        self.recs = torch.from_numpy(np.frombuffer(rec.tobytes() + b"\0" * 40, dtype=np.uint8).copy()).to(dev)
+        self.spans = torch.from_numpy(np.frombuffer(self.spans_host.tobytes() + b"\0" * 16, dtype=np.uint8).copy()).to(dev)
+        self.offsets = torch.from_numpy(np.concatenate([self.offsets_host, [0]])).to(dev)
+        self.pairs = torch.from_numpy(table).to(dev)
+        self.status = torch.full((max(self.n_spans, 1),), -1, dtype=torch.int32, device=dev)
+        self.ends = torch.full((max(self.n_spans, 1), 2), -7, dtype=torch.int32, device=dev)
+        raw = [bytes(x.rid) for x in self.records]
+        offs = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum([len(i) for i in raw], out=offs[1:])
+        self.id_bytes = torch.from_numpy(np.frombuffer(b"".join(raw) + b"\0" * 16, dtype=np.uint8).copy()).to(dev)
+        self.id_offs = torch.from_numpy(offs.astype(np.int32)).to(dev)
+        self.ids = api.TextIds(_ptr(self.id_bytes), _ptr(self.id_offs))
+
+    def view(self) -> api.SsBatch:
+        return api.SsBatch(_ptr(self.ss), self.n_ss_bytes, _ptr(self.recs), _ptr(self.spans), self.n_records, self.n_spans)
+
+    def decode(self) -> None:
+        """sgk_ss_decode over the spans (enqueued, not synchronised)"""
+        view = self.view()
+        api.check(api.load_library().sgk_ss_decode(C.byref(view), _ptr(self.offsets), _ptr(self.pairs), _ptr(self.status),
+                                                   _ptr(self.ends), _stream_ptr()), "sgk_ss_decode")
+
+
+def ss_decode(records, max_span: Optional[int] = None, cuts=None, spans=None, aligns=None, gap: int = 0,
+              device: Optional[torch.device] = None, validate: bool = False):
+    """sgk_ss_decode -> (pairs: one int32 array [count, 2] per span, status [n_spans] uint32, ends [n_spans, 2] int32,
+    the SsBatch: .table_filled is the pair table as it was before the call, .table_after as it is now, .offsets_host where
+    each span's range starts).  validate=True: the spans == NULL form, one result per record and nothing stored."""
+    b = SsBatch(records, max_span, cuts, spans, aligns, gap, device)
+    if validate:
+        b.status = torch.full((max(b.n_records, 1),), -1, dtype=torch.int32, device=b.device)
+        b.ends = torch.full((max(b.n_records, 1), 2), -7, dtype=torch.int32, device=b.device)
+        view = api.SsBatch(_ptr(b.ss), b.n_ss_bytes, _ptr(b.recs), None, b.n_records, 0)
+        api.check(api.load_library().sgk_ss_decode(C.byref(view), None, None, _ptr(b.status), _ptr(b.ends), _stream_ptr()),
+                  "sgk_ss_decode")
+        n_out = b.n_records
+    else:
+        b.decode()
+        n_out = b.n_spans
+    torch.cuda.synchronize()
+    b.table_after = b.pairs.cpu().numpy()
+    pairs = [b.table_after[int(o):int(o) + int(c)].copy() for o, c in zip(b.offsets_host, b.spans_host["count"])] \
+        if b.n_spans else []
+    return pairs, b.status.cpu().numpy().view(np.uint32)[:n_out], b.ends.cpu().numpy()[:n_out], b
+
+
+class SsText(SsBatch):
+    """sgk_ss_decode, then sgk_ss_text_measure + sgk_ss_text_write over one resident batch of spans, in the manner of
+    SrefText: row_offsets has n_spans + 1 entries.  rows_capacity: what the workspace is sized for (default: the rows)."""
+
+    def __init__(self, *args, rows_capacity: Optional[int] = None, **kw):
+        super().__init__(*args, **kw)
+        L = api.load_library()
+        self.ws_bytes = int(L.sgk_ss_text_workspace_bytes(self.n_spans, self.n_rows if rows_capacity is None else rows_capacity))
+        self.ws = torch.zeros(self.ws_bytes, dtype=torch.uint8, device=self.device)
+        self.row_offsets = torch.zeros(self.n_spans + 1, dtype=torch.int64, device=self.device)
+        self.decode()
+
+    def measure(self) -> None:
+        view = self.view()
+        api.check(api.load_library().sgk_ss_text_measure(C.byref(view), _ptr(self.offsets), _ptr(self.pairs), C.byref(self.ids),
+                                                         _ptr(self.row_offsets), _ptr(self.ws), self.ws_bytes, _stream_ptr()),
+                  "sgk_ss_text_measure")
+
+    def write(self, text: torch.Tensor, capacity: Optional[int] = None) -> None:
+        view = self.view()
+        api.check(api.load_library().sgk_ss_text_write(C.byref(view), _ptr(self.offsets), _ptr(self.pairs), C.byref(self.ids),
+                                                       _ptr(text), int(text.numel() if capacity is None else capacity),
+                                                       _ptr(self.ws), self.ws_bytes, _stream_ptr()), "sgk_ss_text_write")
+
+    def status_text(self):
+        """-> (return code of sgk_text_status: 0, api.SGK_ERR_CAPACITY or api.SGK_ERR_WORKSPACE; api.TextStatus); synchronises"""
+        torch.cuda.synchronize()
+        st = api.TextStatus()
+        return api.load_library().sgk_text_status(_ptr(self.ws), C.byref(st)), st
+
+    def run(self) -> bytes:
+        """measure, allocate exactly, write -> the rows as bytes (and self.row_offsets_host)"""
+        self.measure()
+        torch.cuda.synchronize()
+        self.row_offsets_host = self.row_offsets.cpu().numpy().astype(np.uint64)
+        total = int(self.row_offsets_host[-1])
+        text = torch.zeros(max(total, 1), dtype=torch.uint8, device=self.device)
+        self.write(text, total)
+        rc, _ = self.status_text()
+        api.check(rc, "sgk_ss_text_write")
+        return text[:total].cpu().numpy().tobytes()
+
+
+def ss_text(records, max_span: Optional[int] = None, cuts=None, spans=None, aligns=None,
+            device: Optional[torch.device] = None):
+    """the rows of the spans written on the device -> (bytes, row_offsets [n_spans + 1] uint64)"""
+    t = SsText(records, max_span, cuts, spans, aligns, device=device)
+    text = t.run()
+    return text, t.row_offsets_host
+
+
 def text_numbers(values: np.ndarray):
     """sgk_text_numbers_f32 / _i64 (by dtype): printf("%f") / "%ld" of every value, made on the device
     -> (uint8 array [n, 48] of the slots, filled with '#' beforehand; uint8 array [n] of the byte counts)"""

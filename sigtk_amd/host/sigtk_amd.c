@@ -32,6 +32,7 @@
 #include "blow5.h"
 #include "fmt.h"
 #include "sref.h"
+#include "ss.h"
 #include "version.h"
 #include "../csrc/text_format.h"
 #include "sigtk_gpu.h"
@@ -1562,7 +1563,8 @@ static void print_usage(FILE *fp) {
     fprintf(fp, "         ent       calculate entropies\n");
     fprintf(fp, "         qts       quantise the raw signal in a S/BLOW5 files\n");
     fprintf(fp, "         sref      print synthetic reference signal (needs --kmer-model FILE)\n");
-    fprintf(fp, "\n(sigtk-amd: the raw-signal subtools and sref on MI355X; ss is not part of it)\n");
+    fprintf(fp, "         ss        ss string conversion\n");
+    fprintf(fp, "\n(sigtk-amd: every command of sigtk on MI355X; gzipped PAF input for ss is not part of it)\n");
     exit(fp == stdout ? EXIT_SUCCESS : EXIT_FAILURE);
 }
 
@@ -1580,6 +1582,8 @@ int main(int argc, char *argv[]) {
         ret = qtsmain(argc - 1, argv + 1);
     } else if (strcmp(argv[1], "sref") == 0) {
         ret = srefmain(argc - 1, argv + 1);
+    } else if (strcmp(argv[1], "ss") == 0) {
+        ret = ssmain(argc - 1, argv + 1);
     } else if (strcmp(argv[1], "_fadump") == 0) {
         return fadumpmain(argc - 1, argv + 1);
     } else if (strcmp(argv[1], "_modelcheck") == 0) {
