@@ -53,6 +53,15 @@ class _JnnParam(C.Structure):
                 ("top", C.c_float), ("bot", C.c_float)]
 
 
+class _JnnPair(C.Structure):      # jnn_pair_t, src/jnn.h:13-16
+    _fields_ = [("x", C.c_int64), ("y", C.c_int64)]
+
+
+class _Jnnv2Param(C.Structure):   # jnnv2_param_t, src/jnn.h:74-81
+    _fields_ = [("std_scale", C.c_float), ("seg_dist", C.c_int), ("window", C.c_int), ("stall_len", C.c_float),
+                ("hi_thresh", C.c_int), ("lo_thresh", C.c_int)]
+
+
 class Oracle:
     def __init__(self, path: str = ORACLE_SO):
         if not os.path.exists(path):
@@ -196,6 +205,14 @@ class Oracle:
         self.lib.orc_find_adaptor(_p(raw, C.c_int16), C.c_int64(raw.size), C.c_int(pore), _p(xy, C.c_int64))
         return int(xy[0]), int(xy[1])
 
+    def jnnv2(self, raw, std_scale, seg_dist, hi, lo):
+        """jnnv2 (src/jnn.c:99-179) with window 2000"""
+        raw = np.ascontiguousarray(raw, dtype=np.int16)
+        xy = np.zeros(2, dtype=np.int64)
+        self.lib.orc_jnnv2(_p(raw, C.c_int16), C.c_int64(raw.size), C.c_float(std_scale), C.c_int(seg_dist), C.c_int(hi),
+                           C.c_int(lo), _p(xy, C.c_int64))
+        return int(xy[0]), int(xy[1])
+
     def find_polya(self, pa, top, bot, pore):
         pa = np.ascontiguousarray(pa, dtype=np.float32)
         xy = np.zeros(2, dtype=np.int64)
@@ -290,6 +307,15 @@ class RefLib:
         xy = np.zeros(2, dtype=np.int64)
         self.lib.ref_find_adaptor(_p(raw, C.c_int16), C.c_int64(raw.size), C.c_int(pore), _p(xy, C.c_int64))
         return int(xy[0]), int(xy[1])
+
+    def jnnv2(self, raw, std_scale, seg_dist, hi, lo):
+        """the reference's own jnnv2 (src/jnn.c:99), called as it is exported: parameters by value, window 2000"""
+        raw = np.ascontiguousarray(raw, dtype=np.int16)
+        f = self.lib.jnnv2
+        f.restype = _JnnPair
+        f.argtypes = [C.POINTER(C.c_int16), C.c_int64, _Jnnv2Param]
+        p = f(_p(raw, C.c_int16), raw.size, _Jnnv2Param(std_scale, seg_dist, 2000, 0.0, hi, lo))
+        return int(p.x), int(p.y)
 
     def find_polya(self, pa, top, bot, pore):
         pa = np.ascontiguousarray(pa, dtype=np.float32)

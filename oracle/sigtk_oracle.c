@@ -430,9 +430,12 @@ int64_t orc_jnn_pa(const float *pa, int64_t n, orc_jnn_param_t p, int64_t *x, in
 /* src/jnn.c:99-188.  Presets src/jnn.h:84-98: R9 {0.5,1500,2000,hi 200000,lo 2000},
  * RNA004 {0.7,1500,2000,200000,500}. */
 void orc_find_adaptor(const int16_t *raw, int64_t n, int pore, int64_t *xy) {
-    const float std_scale = (pore == 2) ? 0.7f : 0.5f;
-    const int seg_dist = 1500, window = 2000, hi = 200000;
-    const int lo = (pore == 2) ? 500 : 2000;
+    orc_jnnv2(raw, n, (pore == 2) ? 0.7f : 0.5f, 1500, 200000, (pore == 2) ? 500 : 2000, xy);
+}
+
+/* jnnv2 with any std_scale / seg_dist / hi_thresh / lo_thresh; the window stays 2000 (exactness of the running total) */
+void orc_jnnv2(const int16_t *raw, int64_t n, float std_scale, int seg_dist, int hi, int lo, int64_t *xy) {
+    const int window = 2000;
     if (n <= window) { xy[0] = -1; xy[1] = -1; return; }
     const int64_t m = n - window;
     float *t = (float *)malloc(sizeof(float) * (size_t)m);

@@ -20,6 +20,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from sigtk_amd import api  # noqa: E402
+import prefix_cases  # noqa: E402  (tests/ is on the path: conftest.py lies there)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 VECTORS = os.path.join(GOLDEN, "ref_vectors.json")
@@ -96,9 +97,33 @@ def observe_soak_fixtures(lib):
     return out
 
 
+def observe_prefix_catalogue(lib):
+    """tests/prefix_cases.py: find_adaptor on every read with either pore; find_polya on pA[adapt_y:] with the thresholds
+    cfunc.c:191 forms from the mean of pA[adapt_x:adapt_y] (their bits are recorded too); jnnv2 with the small hi / lo /
+    seg_dist sets of the shim cases; find_polya on the direct pA arrays"""
+    out = {}
+    with np.errstate(all="ignore"):
+        for k in prefix_cases.catalogue():
+            pa = lib.pa(k.raw, k.dig, k.off, k.rng)
+            for pore in (0, 2):
+                ax, ay = lib.find_adaptor(k.raw, pore)
+                out["%s.adaptor%d" % (k.name, pore)] = [ax, ay]
+                if ay > 0:
+                    mid = np.float32(lib.statf(pa[ax:ay])[0]) + np.float32(30)
+                    top, bot = mid + np.float32(20), mid - np.float32(20)
+                    out["%s.polya%d" % (k.name, pore)] = [_bits(top), _bits(bot)] + list(lib.find_polya(pa[ay:], top, bot, pore))
+        for k in prefix_cases.shim_cases():
+            out["jnnv2:" + k.name] = list(lib.jnnv2(k.raw, k.p.std_scale, k.p.seg_dist, k.p.hi, k.p.lo))
+        for k in prefix_cases.pa_cases():
+            for pore in (0, 2):
+                out["pa:%s.polya%d" % (k.name, pore)] = list(lib.find_polya(k.pa, k.top, k.bot, pore))
+    return out
+
+
 OBSERVATIONS = {"pa_event_stat_seed%d" % s: (observe_pa_event_stat, (s,)) for s in (1, 2, 3)}
 OBSERVATIONS.update({"jnn_adaptor_polya_seed%d" % s: (observe_jnn_adaptor_polya, (s,)) for s in (4, 5)})
 OBSERVATIONS["soak_fixtures"] = (observe_soak_fixtures, ())
+OBSERVATIONS["prefix_catalogue"] = (observe_prefix_catalogue, ())
 
 
 def _check(name, oracle, reflib):
@@ -126,6 +151,12 @@ def test_soak_regression_fixtures_are_pinned(oracle, reflib):
     """the reads the round-2 soaks found GPU bugs on (tests/golden/soak_*.npz): what the GPU tests compare against --
     the oracle -- equals the real reference on them (event, stat and jnn)."""
     _check("soak_fixtures", oracle, reflib)
+
+
+def test_prefix_catalogue(oracle, reflib):
+    """every branch of the adaptor and polyA finders (tests/prefix_cases.py): the oracle the GPU tests compare against
+    equals the real reference on the whole catalogue"""
+    _check("prefix_catalogue", oracle, reflib)
 
 
 if __name__ == "__main__":
