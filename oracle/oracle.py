@@ -22,11 +22,40 @@ REF_SO = os.path.join(HERE, "_ref", "libsigtk_ref.so")
 REF_BIN = os.path.join(HERE, "_ref", "sigtk_ref")
 
 
+def _ref_sources_present() -> bool:
+    return os.path.exists("/root/reference/src/events.c")
+
+
+def ref_shim_symbols():
+    """the entry points oracle/ref_shim.c defines"""
+    import re
+    with open(os.path.join(HERE, "ref_shim.c")) as fh:
+        return sorted(set(re.findall(r"^[A-Za-z_][\w \*]*?\b(ref_\w+)\(", fh.read(), flags=re.M)))
+
+
+def ref_is_current() -> bool:
+    """oracle/_ref/libsigtk_ref.so holds every entry point of this tree's ref_shim.c.  (make goes by time stamps: a
+    library left by a build of another revision of the shim can be newer than the file a checkout wrote.)"""
+    if not os.path.exists(REF_SO):
+        return False
+    with open(REF_SO, "rb") as fh:
+        blob = fh.read()
+    return all(s.encode() + b"\0" in blob for s in ref_shim_symbols())
+
+
+def build_ref() -> None:
+    subprocess.check_call(["make", "-s", "-C", HERE, "ref"])
+    if not ref_is_current():
+        subprocess.check_call(["make", "-s", "-C", HERE, "-W", "ref_shim.c", "ref"])
+    if not ref_is_current():
+        raise RuntimeError("%s misses entry points of oracle/ref_shim.c after a rebuild" % REF_SO)
+
+
 def build(ref: bool = True) -> None:
     """Compile liboracle.so and, if /root/reference is present, oracle/_ref."""
     subprocess.check_call(["make", "-s", "-C", HERE, "oracle"])
-    if ref and os.path.exists("/root/reference/src/events.c"):
-        subprocess.check_call(["make", "-s", "-C", HERE, "ref"])
+    if ref and _ref_sources_present():
+        build_ref()
 
 
 class Events(NamedTuple):
@@ -189,6 +218,11 @@ class Oracle:
                                   C.c_int64(cap))
         return x[:k].copy(), y[:k].copy()
 
+    def jnn_raw_param(self, raw, p: "_JnnParam"):
+        """jnn_raw (src/jnn.c:282-293) with any jnn_param_t: rm_outlier then jnn_core"""
+        raw = np.ascontiguousarray(raw, dtype=np.int16)
+        return self.jnn_core(np.clip(raw, 0, 1200).astype(np.float32), p)
+
     def jnn_pa(self, pa, p: "_JnnParam"):
         """jnn_pa (src/jnn.c:295-306): rm_outlierf then jnn_core"""
         pa = np.ascontiguousarray(pa, dtype=np.float32)
@@ -239,6 +273,8 @@ class RefLib:
     """The real reference (oracle/_ref/libsigtk_ref.so), if built."""
 
     def __init__(self, path: str = REF_SO):
+        if path == REF_SO and not ref_is_current() and _ref_sources_present():
+            build_ref()   # (built from another revision of ref_shim.c: see ref_is_current)
         self.lib = C.CDLL(path)
         L = self.lib
         L.ref_getevents.restype = C.c_int64
@@ -301,6 +337,26 @@ class RefLib:
         k = self.lib.ref_jnn_raw(_p(raw, C.c_int16), C.c_int64(raw.size), C.c_int(rna), _p(x, C.c_int64),
                                  _p(y, C.c_int64), C.c_int(cap))
         return x[:k].copy(), y[:k].copy()
+
+    def jnn_param(self, **kw) -> "_JnnParam":
+        return Oracle.jnn_param(self, **kw)
+
+    def _jnn_param_call(self, fn, a, ctype, p):
+        cap = a.size // 2 + 16
+        x = np.empty(cap, dtype=np.int64)
+        y = np.empty(cap, dtype=np.int64)
+        fn.restype = C.c_int
+        fn.argtypes = [C.POINTER(ctype), C.c_int64, _JnnParam, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]
+        k = fn(_p(a, ctype), a.size, p, _p(x, C.c_int64), _p(y, C.c_int64), cap)
+        return x[:k].copy(), y[:k].copy()
+
+    def jnn_raw_param(self, raw, p: "_JnnParam"):
+        """the reference's jnn_raw (src/jnn.c:282) with any jnn_param_t"""
+        return self._jnn_param_call(self.lib.ref_jnn_raw_param, np.ascontiguousarray(raw, dtype=np.int16), C.c_int16, p)
+
+    def jnn_pa(self, pa, p: "_JnnParam"):
+        """the reference's jnn_pa (src/jnn.c:295) with any jnn_param_t"""
+        return self._jnn_param_call(self.lib.ref_jnn_pa_param, np.ascontiguousarray(pa, dtype=np.float32), C.c_float, p)
 
     def find_adaptor(self, raw, pore):
         raw = np.ascontiguousarray(raw, dtype=np.int16)

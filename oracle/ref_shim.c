@@ -137,6 +137,29 @@ int ref_jnn_raw(const int16_t *raw, int64_t n, int rna, int64_t *x, int64_t *y, 
     return nseg;
 }
 
+static int shim_segments(jnn_pair_t *segs, int nseg, int64_t *x, int64_t *y, int cap) {
+    for (int i = 0; i < nseg && i < cap; i++) {
+        x[i] = segs[i].x;
+        y[i] = segs[i].y;
+    }
+    free(segs);
+    return nseg;
+}
+
+/* jnn_raw (src/jnn.c:282) with the caller's jnn_param_t */
+int ref_jnn_raw_param(const int16_t *raw, int64_t n, jnn_param_t param, int64_t *x, int64_t *y, int cap) {
+    int nseg = 0;
+    jnn_pair_t *segs = jnn_raw(raw, n, param, &nseg);
+    return shim_segments(segs, nseg, x, y, cap);
+}
+
+/* jnn_pa (src/jnn.c:295) with the caller's jnn_param_t */
+int ref_jnn_pa_param(const float *pa, int64_t n, jnn_param_t param, int64_t *x, int64_t *y, int cap) {
+    int nseg = 0;
+    jnn_pair_t *segs = jnn_pa(pa, n, param, &nseg);
+    return shim_segments(segs, nseg, x, y, cap);
+}
+
 /* find_adaptor (src/jnn.c:181) */
 void ref_find_adaptor(const int16_t *raw, int64_t n, int pore, int64_t *xy) {
     slow5_rec_t rec = shim_rec(raw, n, 8192.0, 0.0, 1400.0);

@@ -20,6 +20,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from sigtk_amd import api  # noqa: E402
+import jnn_cases  # noqa: E402
 import prefix_cases  # noqa: E402  (tests/ is on the path: conftest.py lies there)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -120,10 +121,31 @@ def observe_prefix_catalogue(lib):
     return out
 
 
+def observe_jnn_catalogue(lib):
+    """tests/jnn_cases.py: jnn_raw on every read with the parameters it is run with (both presets, or its own: the err--
+    correction, fixed thresholds on the clamp's edges, error 0 / 31 / 32 ...) and jnn_pa on the pA arrays; the preset
+    entry point must agree with the presets passed as parameters"""
+    out = {}
+    with np.errstate(all="ignore"):
+        for k in jnn_cases.catalogue():
+            for label, p in jnn_cases.case_runs(k):
+                x, y = lib.jnn_raw_param(k.raw, lib.jnn_param(**p._asdict()))
+                out[label] = [int(x.size), _h(x, np.int64), _h(y, np.int64)]
+            if k.params is None:
+                for rna in (0, 1):
+                    x, y = lib.jnn_raw(k.raw, rna)
+                    assert out["%s/rna%d" % (k.name, rna)] == [int(x.size), _h(x, np.int64), _h(y, np.int64)], (k.name, rna)
+        for k in jnn_cases.pa_cases():
+            x, y = lib.jnn_pa(k.pa, lib.jnn_param(**k.params._asdict()))
+            out["pa:" + k.name] = [int(x.size), _h(x, np.int64), _h(y, np.int64)]
+    return out
+
+
 OBSERVATIONS = {"pa_event_stat_seed%d" % s: (observe_pa_event_stat, (s,)) for s in (1, 2, 3)}
 OBSERVATIONS.update({"jnn_adaptor_polya_seed%d" % s: (observe_jnn_adaptor_polya, (s,)) for s in (4, 5)})
 OBSERVATIONS["soak_fixtures"] = (observe_soak_fixtures, ())
 OBSERVATIONS["prefix_catalogue"] = (observe_prefix_catalogue, ())
+OBSERVATIONS["jnn_catalogue"] = (observe_jnn_catalogue, ())
 
 
 def _check(name, oracle, reflib):
@@ -157,6 +179,12 @@ def test_prefix_catalogue(oracle, reflib):
     """every branch of the adaptor and polyA finders (tests/prefix_cases.py): the oracle the GPU tests compare against
     equals the real reference on the whole catalogue"""
     _check("prefix_catalogue", oracle, reflib)
+
+
+def test_jnn_catalogue(oracle, reflib):
+    """every branch of the segmenter, the err-- correction among them (tests/jnn_cases.py): the oracle the GPU tests compare
+    against equals the real reference on the whole catalogue"""
+    _check("jnn_catalogue", oracle, reflib)
 
 
 if __name__ == "__main__":
