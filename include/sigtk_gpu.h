@@ -71,7 +71,8 @@ extern "C" {
  *        reads); sgk_stat_options_t::debug_fault (was reserved[0]); sgk_job_long_declined; sgk_inflate, SGK_SIGNAL_ZREC / sgk_job_begin_zrec;
  *        the six-argument plan call is sgk_event_plan_opt; sgk_event_plan is the 0.1.0 five-argument form again (deprecated).
  * 0.2.3: SGK_JOB_EVENTS_LENGTHS (additive submit flag).  Additive to 0.2.3 (no version change): sgk_sigtext_decode;
- *        SGK_SIGNAL_TEXT for sgk_job_begin; sgk_ss_* (`ss paf2tsv`: decode, text, host pipe). */
+ *        SGK_SIGNAL_TEXT for sgk_job_begin; sgk_ss_* (`ss paf2tsv`: decode, text, host pipe); sgk_zstd_decompress,
+ *        SGK_RECORD_ZLIB / SGK_RECORD_ZSTD and sgk_job_begin_zrec_format (BLOW5 files with zstd records). */
 #define SGK_VERSION_STRING "0.2.3"
 
 /* ---- error codes --------------------------------------------------------------- */
@@ -403,6 +404,26 @@ int sgk_sigtext_decode(const uint8_t *text, const uint64_t *text_offsets, const 
 int sgk_inflate(const uint8_t *in, const uint64_t *in_offsets, const uint32_t *in_lengths, uint32_t n, uint8_t *out,
                 const uint64_t *out_offsets, const uint32_t *out_caps, uint32_t *out_lengths, uint32_t *status,
                 void *stream);
+
+/* ---- zstd record decompression on the device (additive to 0.2.3) -------------------------------------------------- */
+/* BLOW5 files written with record compression 2 hold one zstd frame (RFC 8878) per record, as ZSTD_compress makes it
+ * (slow5lib/src/slow5_press.c:1156-1200).  sgk_zstd_decompress decodes n frames, one wavefront per frame, with the buffer
+ * contract of sgk_inflate: in readable up to its size rounded up to a multiple of 4 bytes, out 16-byte aligned, frame r's
+ * bytes at out + out_offsets[r] (multiples of 16) with room for out_caps[r] bytes; out_lengths[r]: the bytes written.
+ * Taken: every frame header layout that declares the content size, Raw / RLE / Compressed blocks, all literals types and
+ * sequence modes, the content checksum (verified when present).  Refused: no content size, a dictionary id other than 0,
+ * skippable frames, anything behind the frame.  status[r]:
+ *   0 ok                          1 frame header refused (magic, reserved bit, dictionary, skippable, no content size,
+ *   2 bad block header              bytes behind the frame)
+ *   3 bad table description       4 bad literals or sequences section
+ *   5 offset 0 or in front of the frame                              6 truncated input
+ *   7 checksum mismatch           8 size differs from the declaration or exceeds out_caps[r]
+ * (1 - 8: the bytes are undefined; nothing is written at or behind out_caps[r]).  The library keeps the literals scratch
+ * (128 KB per resident wavefront, at most ten per compute unit) per device and stream: a job's is freed by
+ * sgk_job_destroy, that of a stream the caller owns stays allocated until the process ends. */
+int sgk_zstd_decompress(const uint8_t *in, const uint64_t *in_offsets, const uint32_t *in_lengths, uint32_t n, uint8_t *out,
+                        const uint64_t *out_offsets, const uint32_t *out_caps, uint32_t *out_lengths, uint32_t *status,
+                        void *stream);
 
 /* ---- qts: quantise the raw signal (src/qts.c:27-43, :126-142) and re-encode it ------ */
 #define SGK_QTS_FLOOR 0     /* (raw >> b) << b                                       */
@@ -757,6 +778,14 @@ int sgk_job_begin(sgk_job_t *job, uint32_t n_reads, const uint32_t *lengths, int
 int sgk_job_begin_zrec(sgk_job_t *job, uint32_t n_reads, const uint32_t *lengths, const uint32_t *rec_bytes,
                        const uint32_t *sig_offset, const uint32_t *sig_bytes, const uint32_t *rec_room,
                        sgk_job_input_t *in);
+/* The same for either record compression of a BLOW5 file (additive to 0.2.3): SGK_RECORD_ZLIB is sgk_job_begin_zrec,
+ * SGK_RECORD_ZSTD decodes the records with sgk_zstd_decompress -- rec_room[r] is then at least the content size the
+ * frame declares, and decode_status[r] of a record that did not decode is 0x200 | sgk_zstd_decompress's status. */
+#define SGK_RECORD_ZLIB 1
+#define SGK_RECORD_ZSTD 2
+int sgk_job_begin_zrec_format(sgk_job_t *job, uint32_t n_reads, int record_format, const uint32_t *lengths,
+                              const uint32_t *rec_bytes, const uint32_t *sig_offset, const uint32_t *sig_bytes,
+                              const uint32_t *rec_room, sgk_job_input_t *in);
 /* may be called again after sgk_job_wait to run another tool over the same staged batch */
 int sgk_job_submit(sgk_job_t *job, int tool, int rna, int pore, int flags);
 /* qts over the staged batch: quantise (bits in [1,15], method SGK_QTS_*), then hand the signal back as svb-zd blobs

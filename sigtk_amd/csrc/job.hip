@@ -24,6 +24,7 @@
 #include "stat_args.h"
 
 namespace sgk {
+void zstd_release_scratch(int device, hipStream_t st);   // zstd_kernels.hip
 
 struct GrowDev {
     void *p = nullptr;
@@ -92,6 +93,7 @@ struct sgk_job {
     GrowPin h_ioffs, h_icaps, h_istat, h_soffs, h_slens;
     GrowDev d_inflated, d_ioffs, d_icaps, d_ilens, d_istat, d_soffs, d_slens;
     uint64_t inflated_bytes = 0;
+    int rec_fmt = SGK_RECORD_ZLIB;   // SGK_SIGNAL_ZREC: what the records are compressed with
     bool long_fetched = false;        // stat / jnn / prefix: the long-read header of the call is on its way to h_long
     uint32_t long_declined = 0;       // ... long reads the long path declined (n_timeouts of sgk_long_status_t), after wait
     int n_dense = 0;                  // arrays to fetch in sgk_job_wait once the dense total is known
@@ -165,6 +167,7 @@ void sgk_job_destroy(sgk_job_t *j) {
     (void)hipSetDevice(j->device);
     if (j->st) {
         (void)hipStreamSynchronize(j->st);
+        sgk::zstd_release_scratch(j->device, j->st);
         (void)hipStreamDestroy(j->st);
     }
     delete j;
@@ -184,8 +187,17 @@ int sgk_job_begin(sgk_job_t *j, uint32_t n_reads, const uint32_t *lengths, int s
 int sgk_job_begin_zrec(sgk_job_t *j, uint32_t n_reads, const uint32_t *lengths, const uint32_t *rec_bytes,
                        const uint32_t *sig_offset, const uint32_t *sig_bytes, const uint32_t *rec_room,
                        sgk_job_input_t *in) {
+    return sgk_job_begin_zrec_format(j, n_reads, SGK_RECORD_ZLIB, lengths, rec_bytes, sig_offset, sig_bytes, rec_room, in);
+}
+
+int sgk_job_begin_zrec_format(sgk_job_t *j, uint32_t n_reads, int record_format, const uint32_t *lengths,
+                              const uint32_t *rec_bytes, const uint32_t *sig_offset, const uint32_t *sig_bytes,
+                              const uint32_t *rec_room, sgk_job_input_t *in) {
+    if (record_format != SGK_RECORD_ZLIB && record_format != SGK_RECORD_ZSTD) return SGK_ERR_ARG;
     if (n_reads && (!rec_bytes || !sig_offset || !sig_bytes || !rec_room)) return SGK_ERR_ARG;
-    return job_begin(j, n_reads, lengths, SGK_SIGNAL_ZREC, rec_bytes, sig_offset, sig_bytes, rec_room, in);
+    const int rc = job_begin(j, n_reads, lengths, SGK_SIGNAL_ZREC, rec_bytes, sig_offset, sig_bytes, rec_room, in);
+    if (rc == SGK_OK) j->rec_fmt = record_format;
+    return rc;
 }
 
 static int job_begin(sgk_job_t *j, uint32_t n_reads, const uint32_t *lengths, int signal_format, const uint32_t *blob_bytes,
@@ -324,9 +336,10 @@ static int job_upload(sgk_job_t *j, sgk_batch_t *view) {
         if ((rc = j->d_ilens.ensure(nr * 4)) != SGK_OK) return rc;
         if ((rc = j->d_istat.ensure(nr * 4)) != SGK_OK) return rc;
         if ((rc = j->d_dstat.ensure(nr * 4)) != SGK_OK) return rc;
-        rc = sgk_inflate(j->d_blobs.as<uint8_t>(), j->d_boffs.as<uint64_t>(), j->d_blens.as<uint32_t>(), j->n_reads,
-                         j->d_inflated.as<uint8_t>(), j->d_ioffs.as<uint64_t>(), j->d_icaps.as<uint32_t>(),
-                         j->d_ilens.as<uint32_t>(), j->d_istat.as<uint32_t>(), st);
+        rc = (j->rec_fmt == SGK_RECORD_ZSTD ? sgk_zstd_decompress : sgk_inflate)(
+            j->d_blobs.as<uint8_t>(), j->d_boffs.as<uint64_t>(), j->d_blens.as<uint32_t>(), j->n_reads,
+            j->d_inflated.as<uint8_t>(), j->d_ioffs.as<uint64_t>(), j->d_icaps.as<uint32_t>(), j->d_ilens.as<uint32_t>(),
+            j->d_istat.as<uint32_t>(), st);
         if (rc != SGK_OK) return rc;
         // (a record that did not inflate leaves whatever it leaves: its blob then fails the decoder's own checks or
         // decodes to garbage nobody reads -- sgk_job_wait refuses the batch on the inflate status)
@@ -688,12 +701,13 @@ int sgk_job_wait(sgk_job_t *j) {
     }
     if (j->fmt == SGK_SIGNAL_ZREC) {
         // a record that did not inflate (malformed stream, check value, more bytes than its head announced): as the
-        // reference's slow5_get_next error.  decode_status carries 0x100 | the inflate status for such a read.
+        // reference's slow5_get_next error.  decode_status carries 0x100 | the inflate status for such a read (zstd
+        // records: 0x200 | sgk_zstd_decompress's status).
         uint32_t *ds = j->h_dstat.as<uint32_t>();
         const uint32_t *is = j->h_istat.as<uint32_t>();
         bool bad = false;
         for (uint32_t r = 0; r < j->n_reads; ++r) {
-            if (is[r] != 0) ds[r] = 0x100u | is[r];
+            if (is[r] != 0) ds[r] = (j->rec_fmt == SGK_RECORD_ZSTD ? 0x200u : 0x100u) | is[r];
             bad = bad || ds[r] != 0;
         }
         if (bad) return SGK_ERR_FORMAT;

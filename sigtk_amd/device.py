@@ -399,6 +399,48 @@ def inflate(streams, caps=None, device: Optional[torch.device] = None, with_gaps
     return kept, olen, st
 
 
+def zstd_decompress(frames, caps=None, device: Optional[torch.device] = None, with_gaps: bool = False, leads=None,
+                    fill: int = 0, guard: int = 0):
+    """sgk_zstd_decompress over a list of zstd frames (bytes) -> (list of decoded bytes as kept, out_lengths, status) --
+    the device-side replacement of slow5lib's per-record ZSTD_decompress().  caps, with_gaps and leads as inflate().
+    The output buffer starts out as `fill` bytes, and `guard` more bytes (a multiple of 16) lie between a frame's room and
+    the next frame's: with_gaps returns what is there after the launch, for tests that look for stray writes."""
+    L = api.load_library()
+    dev = device or torch.device("cuda", 0)
+    n = len(frames)
+    in_len = np.asarray([len(s) for s in frames], dtype=np.uint32)
+    in_off, pos = inflate_input_offsets(frames, leads)
+    blob = np.zeros((pos + 7) // 4 * 4 + 4, dtype=np.uint8)
+    for r, s in enumerate(frames):
+        blob[int(in_off[r]):int(in_off[r]) + len(s)] = np.frombuffer(s, dtype=np.uint8)
+    caps_a = np.asarray(caps if caps is not None else [1 << 20] * n, dtype=np.uint32)
+    assert guard % 16 == 0
+    out_off = np.zeros(n, dtype=np.uint64)
+    if n > 1:
+        out_off[1:] = np.cumsum((caps_a[:-1].astype(np.uint64) + 15) // 16 * 16 + np.uint64(guard))
+    total = int(out_off[-1]) + (int(caps_a[-1]) + 15) // 16 * 16 + guard if n else 16
+    d_in = torch.from_numpy(blob).to(dev)
+    assert _ptr(d_in) % 4 == 0
+    d_ioff = torch.from_numpy(in_off.view(np.int64)).to(dev)
+    d_ilen = torch.from_numpy(in_len.view(np.int32)).to(dev)
+    d_out = torch.full((max(total, 16),), fill, dtype=torch.uint8, device=dev)
+    d_ooff = torch.from_numpy(out_off.view(np.int64)).to(dev)
+    d_caps = torch.from_numpy(caps_a.view(np.int32)).to(dev)
+    d_olen = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    d_st = torch.full((max(n, 1),), -1, dtype=torch.int32, device=dev)
+    api.check(L.sgk_zstd_decompress(_ptr(d_in), _ptr(d_ioff), _ptr(d_ilen), n, _ptr(d_out), _ptr(d_ooff), _ptr(d_caps),
+                                    _ptr(d_olen), _ptr(d_st), _stream_ptr()), "sgk_zstd_decompress")
+    torch.cuda.synchronize()
+    out = d_out.cpu().numpy()
+    olen = d_olen.cpu().numpy().view(np.uint32)[:n]
+    st = d_st.cpu().numpy()[:n]
+    kept = [out[int(out_off[r]):int(out_off[r]) + min(int(olen[r]), int(caps_a[r]))].tobytes() for r in range(n)]
+    if with_gaps:
+        ends = [int(out_off[r + 1]) if r + 1 < n else total for r in range(n)]
+        return kept, olen, st, [out[int(out_off[r]) + int(caps_a[r]):ends[r]].tobytes() for r in range(n)]
+    return kept, olen, st
+
+
 # ---------------------------------------------------------------------- TSV rows written on the device (sgk_text_*)
 
 class TextWriter:

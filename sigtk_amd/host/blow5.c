@@ -7,6 +7,8 @@
 #include <sys/stat.h>
 #include <zlib.h>
 
+#include "zstd_dec.h"
+
 /* an inflated record larger than this is refused (a 2^31-sample record is 4 GiB of signal) */
 #define B5_MAX_INFLATED (1ull << 33)
 
@@ -21,6 +23,22 @@ static int grow(uint8_t **p, uint64_t *cap, uint64_t need) {
     if (!q) return B5_ERR_MEM;
     *p = q;
     *cap = c;
+    return 0;
+}
+
+/* a zstd record (record compression 2; slow5lib/src/slow5_press.c:1177-1200): one frame that declares its content size */
+static int depress_zstd(const uint8_t *raw, uint64_t size, uint8_t **buf, uint64_t *cap, uint64_t *n) {
+    uint64_t want;
+    if (zsd_content_size(raw, (size_t)size, &want) != ZSD_OK || want > B5_MAX_INFLATED) return B5_ERR_PRESS;
+    /* A block yields at most 128 KB and takes at least its 3 header bytes, so a frame of `size` bytes cannot hold more
+     * than this: a small record that declares gigabytes is refused before anything is allocated for it. */
+    if (want > (size / 3 + 1) * (128u << 10)) return B5_ERR_PRESS;
+    const int rc = grow(buf, cap, want ? want : 1);
+    if (rc) return rc;
+    size_t got = 0;
+    const int st = zsd_decode(raw, (size_t)size, *buf, (size_t)want, &got);
+    if (st != ZSD_OK) return st == ZSD_ERR_MEM ? B5_ERR_MEM : B5_ERR_PRESS;
+    *n = got;
     return 0;
 }
 
@@ -213,7 +231,7 @@ b5_file_t *b5_open(const char *path) {
     f->hdr_text[hsize] = '\0';
     f->hdr_size = hsize;
     f->first_rec = 68 + (uint64_t)hsize;
-    if (f->record_press > 1 || f->signal_press > 1) { b5_close(f); return NULL; }
+    if (f->record_press > 2 || f->signal_press > 1) { b5_close(f); return NULL; }
     return f;
 }
 
@@ -383,6 +401,9 @@ static int read_record(b5_file_t *f, b5_rec_t *rec, int id_only) {
             if (rec->cap_zbuf >= B5_MAX_INFLATED) return B5_ERR_PRESS; /* zip bomb / truncated stream */
             cap = rec->cap_zbuf * 2;
         }
+        p = rec->zbuf;
+    } else if (f->record_press == 2) {
+        if ((rc = depress_zstd(rec->buf, size, &rec->zbuf, &rec->cap_zbuf, &n)) != 0) return rc;
         p = rec->zbuf;
     }
     return parse_record(f, p, n, rec, id_only);
@@ -701,6 +722,10 @@ int b5_parse_raw(const b5_file_t *f, const uint8_t *raw, uint64_t size, uint8_t 
             want = *scratch_cap * 2;
         }
         p = *scratch;
+    } else if (f->record_press == 2) {
+        const int rc = depress_zstd(raw, size, scratch, scratch_cap, &n);
+        if (rc) return rc;
+        p = *scratch;
     }
     if (n < 2) return B5_ERR_FORMAT;
     uint16_t idl;
@@ -738,24 +763,40 @@ int b5_parse_raw(const b5_file_t *f, const uint8_t *raw, uint64_t size, uint8_t 
 
 int b5_parse_head(const b5_file_t *f, const uint8_t *raw, uint64_t size, uint8_t **scratch, uint64_t *scratch_cap,
                   b5_view_t *out) {
-    if (f->record_press != 1) return B5_ERR_FORMAT;
+    if (f->record_press != 1 && f->record_press != 2) return B5_ERR_FORMAT;
+    uint64_t z_room = 0;   /* zstd: the frame's declared content size */
+    if (f->record_press == 2 && (zsd_content_size(raw, (size_t)size, &z_room) != ZSD_OK || z_room > B5_MAX_INFLATED)) return B5_ERR_PRESS;
     /* u16 id_len, id, 44 bytes of fields, and the blob's count word: 512 bytes hold an id of up to 462 characters;
      * a longer one (never seen: ids are UUIDs) goes round again with the room it needs */
     uint64_t want = *scratch_cap >= 512 ? *scratch_cap : 512;
+    uint64_t ask = 512;    /* zstd: the bytes asked of the decoder, whose work grows with them (not the scratch's size) */
     for (;;) {
         const int rc = grow(scratch, scratch_cap, want);
         if (rc) return rc;
-        z_stream z;
-        memset(&z, 0, sizeof z);
-        if (inflateInit(&z) != Z_OK) return B5_ERR_MEM;
-        z.next_in = (Bytef *)raw;
-        z.avail_in = size > 0xffffffffull ? 0xffffffffu : (uInt)size;
-        z.next_out = *scratch;
-        z.avail_out = (uInt)(*scratch_cap > 0x7fffffffull ? 0x7fffffffull : *scratch_cap);
-        const int zr = inflate(&z, Z_SYNC_FLUSH);
-        const uint64_t got = z.total_out;
-        inflateEnd(&z);
-        if (zr != Z_OK && zr != Z_STREAM_END && zr != Z_BUF_ERROR) return B5_ERR_PRESS;
+        int zr;
+        uint64_t got, room = *scratch_cap;
+        if (f->record_press == 2) {
+            /* the head of the frame: the decoder stops once the bytes asked for exist, and of the first block's
+             * Huffman-coded literals it decodes no more than that many */
+            size_t have = 0;
+            room = ask;
+            const int st = zsd_decode_head(raw, (size_t)size, *scratch, (size_t)ask, &have);
+            if (st != ZSD_OK) return st == ZSD_ERR_MEM ? B5_ERR_MEM : B5_ERR_PRESS;
+            got = have;
+            zr = got >= z_room ? Z_STREAM_END : Z_OK;
+        } else {
+            z_stream z;
+            memset(&z, 0, sizeof z);
+            if (inflateInit(&z) != Z_OK) return B5_ERR_MEM;
+            z.next_in = (Bytef *)raw;
+            z.avail_in = size > 0xffffffffull ? 0xffffffffu : (uInt)size;
+            z.next_out = *scratch;
+            z.avail_out = (uInt)(*scratch_cap > 0x7fffffffull ? 0x7fffffffull : *scratch_cap);
+            zr = inflate(&z, Z_SYNC_FLUSH);
+            got = z.total_out;
+            inflateEnd(&z);
+            if (zr != Z_OK && zr != Z_STREAM_END && zr != Z_BUF_ERROR) return B5_ERR_PRESS;
+        }
         if (got < 2) return B5_ERR_FORMAT;
         const uint8_t *p = *scratch;
         uint16_t idl;
@@ -763,8 +804,9 @@ int b5_parse_head(const b5_file_t *f, const uint8_t *raw, uint64_t size, uint8_t
         const uint64_t need = 2 + (uint64_t)idl + 44 + (f->signal_press == 1 ? 4 : 0);
         if (got < need) {
             if (zr == Z_STREAM_END) return B5_ERR_FORMAT;   /* the record ends inside its own head */
-            if (*scratch_cap >= need) return B5_ERR_PRESS;    /* (room was not the problem) */
-            want = need;
+            if (room >= need) return B5_ERR_PRESS;    /* (room was not the problem) */
+            want = *scratch_cap >= need ? *scratch_cap : need;
+            ask = need;
             continue;
         }
         out->rec = NULL;

@@ -2,8 +2,8 @@
  *
  * Written from the on-disk layout; the reference reads the same files
  * through slow5lib (slow5_open / slow5_get_next / slow5_get, slow5lib/include/slow5/slow5.h:345-454).
- * Binary BLOW5: record compression none/zlib and signal compression none/svb-zd; zstd files are
- * rejected (the reference build here has no zstd either).  Text SLOW5 (b5_file_t::text; taken from the
+ * Binary BLOW5: record compression none/zlib/zstd (the zstd frames are decoded by zstd_dec.c, written from
+ * the format: no libzstd) and signal compression none/svb-zd.  Text SLOW5 (b5_file_t::text; taken from the
  * ".slow5" extension or the first bytes): one record per line, the eight main columns in order, the
  * signal column handed on as text (b5_view_t::signal) for the GPU parser or b5_sigtext_decode.
  * Auxiliary fields are skipped in both. */
@@ -36,7 +36,7 @@ typedef struct {
     FILE *fp;
     char *path;
     uint8_t version[3];
-    uint8_t record_press; /* 0 none, 1 zlib */
+    uint8_t record_press; /* 0 none, 1 zlib, 2 zstd */
     uint8_t signal_press; /* 0 none, 1 svb-zd */
     uint32_t num_read_groups;
     char *hdr_text;       /* header text block */
@@ -102,10 +102,12 @@ int b5_next_ref(b5_file_t *f, const uint8_t **ptr, uint64_t *size);
  * into *scratch or into raw.  Re-entrant: touches no state of f besides its compression settings. */
 int b5_parse_raw(const b5_file_t *f, const uint8_t *raw, uint64_t size, uint8_t **scratch, uint64_t *scratch_cap,
                  b5_view_t *out);
-/* The HEAD of a zlib-compressed record only: inflates just far enough (into *scratch) for the id, the scaling, the signal's
+/* The HEAD of a zlib- or zstd-compressed record only: inflates just far enough (into *scratch) for the id, the scaling, the signal's
  * byte length and -- svb-zd -- its sample count; the view's read_id points into *scratch, rec / signal are NULL,
- * signal_offset tells where the signal starts in the inflated record.  A few microseconds per record instead of the
- * whole inflate: the record itself is inflated on the GPU (sgk_job_begin_zrec).  Files with zlib records only. */
+ * signal_offset tells where the signal starts in the inflated record.  A small part of the whole inflate: the record
+ * itself is inflated on the GPU (sgk_job_begin_zrec).  For a zstd record that part is the first block's Huffman and FSE
+ * tables, the first 512 literals and the first sequences (zsd_decode_head): some 16 us against 1 ms for the whole record
+ * of a 100 000-sample read.  Files with compressed records only; rec_len is 0. */
 int b5_parse_head(const b5_file_t *f, const uint8_t *raw, uint64_t size, uint8_t **scratch, uint64_t *scratch_cap,
                   b5_view_t *out);
 /* bytes of a record's auxiliary fields when all of them are primitive (fixed size), else -1 (an array field, an unknown

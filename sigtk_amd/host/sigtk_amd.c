@@ -30,6 +30,7 @@
 #include <zlib.h>
 
 #include "blow5.h"
+#include "zstd_dec.h"
 #include "fmt.h"
 #include "sref.h"
 #include "ss.h"
@@ -483,7 +484,7 @@ static void batch_launch(pipe_t *P, batch_t *b) {
     b->sigtext = P->f->text && !P->host_decode;
     b->zrec = P->zrec;
     int rc;
-    if (b->zrec) rc = sgk_job_begin_zrec(b->job, b->n, b->lengths, b->blob_bytes, b->sig_off, b->sig_len, b->room, &b->in);
+    if (b->zrec) rc = sgk_job_begin_zrec_format(b->job, b->n, P->f->record_press == 2 ? SGK_RECORD_ZSTD : SGK_RECORD_ZLIB, b->lengths, b->blob_bytes, b->sig_off, b->sig_len, b->room, &b->in);
     else rc = sgk_job_begin(b->job, b->n, b->lengths, b->sigtext ? SGK_SIGNAL_TEXT : (b->svb ? SGK_SIGNAL_SVBZD : SGK_SIGNAL_INT16), b->blob_bytes, &b->in);
     if (rc != SGK_OK) gpu_fail("sgk_job_begin", rc);
     pfor(P->load_pool, b->n, load_stage, &c);
@@ -711,7 +712,9 @@ static void row_ent(sbuf_t *o, const batch_t *b, const sgk_job_output_t *out, ui
 
 /* qts (src/qts.c:118-150): the record as it was read, with the signal replaced by the quantised one (and
  * len_raw_signal with it); everything else -- id, read group, scaling, auxiliary fields -- is kept byte for byte.
- * Emitted as the file stores it: u64 size, then the record (one zlib stream when the file compresses records). */
+ * Emitted as the file stores it: u64 size, then the record (one zlib stream when the file compresses records -- a file
+ * of zstd records too: the output is written with zlib records, as slow5_open(out, "w") makes it in the reference,
+ * slow5lib/src/slow5.c:421-423; qtsmain sets the header byte). */
 static __thread uint8_t *qts_tmp;
 static __thread size_t qts_tmp_cap;
 static void row_qts(sbuf_t *o, const batch_t *b, const sgk_job_output_t *out, uint32_t r, const b5_file_t *f) {
@@ -731,7 +734,7 @@ static void row_qts(sbuf_t *o, const batch_t *b, const sgk_job_output_t *out, ui
         len_field = b->lengths[r];
     }
     const size_t n = head + 8 + (size_t)sig_bytes + tail_len;
-    if (f->record_press == 1) {
+    if (f->record_press != 0) {
         if (qts_tmp_cap < n) {
             qts_tmp = (uint8_t *)realloc(qts_tmp, n + n / 4 + 64);
             if (!qts_tmp) die_mem();
@@ -1113,7 +1116,7 @@ static int cmain(int argc, char *argv[], const char *mode_s) {
         fprintf(fp_help, "   --batch-samples INT        approximate raw samples per batch [134217728; with --host-inflate 16777216, jnn / prefix 67108864]\n");
         fprintf(fp_help, "   -t, --threads INT          host threads for inflating records / formatting rows [auto]\n");
         fprintf(fp_help, "   --host-decode              decode svb-zd signals (parse text SLOW5 signals) on the host instead of the GPU\n");
-        fprintf(fp_help, "   --host-inflate             inflate zlib records on the host threads instead of the GPU\n");
+        fprintf(fp_help, "   --host-inflate             decompress zlib / zstd records on the host threads instead of the GPU\n");
         fprintf(fp_help, "   --gpu-text                 pa / event, whole-file mode: format the rows on the GPU and fetch them as text\n");
         exit(fp_help == stdout ? EXIT_SUCCESS : EXIT_FAILURE);
     }
@@ -1177,11 +1180,11 @@ static int cmain(int argc, char *argv[], const char *mode_s) {
     P.mode = mode;
     P.nthreads = nthreads;
     P.host_decode = host_decode;
-    /* Records go to the GPU as they sit in the file when they are zlib streams around an svb-zd signal and their
+    /* Records go to the GPU as they sit in the file when they are zlib streams or zstd frames around an svb-zd signal and their
      * auxiliary fields have a fixed size (the inflated length of a record then follows from its head); everything else
      * -- and --host-inflate / --host-decode -- is inflated by the host threads as before. */
     P.aux_bytes = b5_aux_fixed_bytes(f);
-    P.zrec = !f->text && !host_inflate && !host_decode && f->record_press == 1 && f->signal_press == 1 && P.aux_bytes >= 0;
+    P.zrec = !f->text && !host_inflate && !host_decode && (f->record_press == 1 || f->record_press == 2) && f->signal_press == 1 && P.aux_bytes >= 0;
     /* ... in batches of 128 M samples: the inflate kernel is a wavefront per record and takes ~35 ms however many records
      * it has (up to the ~4 800 the GPU holds at once), so a batch should bring a thousand of them (1e10 samples of `stat`:
      * 5.2 s with the 16 M-sample batches of the host path, 1.7 s with 128 M, profiles/r05_cli_steady.json) */
@@ -1293,7 +1296,9 @@ static int qtsmain(int argc, char *argv[]) {
         const size_t hb = 68 + (size_t)f->hdr_size;
         uint8_t *h = (uint8_t *)malloc(hb);
         if (!h) die_mem();
-        if (fseek(f->fp, 0, SEEK_SET) != 0 || fread(h, 1, hb, f->fp) != hb || fwrite(h, 1, hb, out) != hb ||
+        int ok = fseek(f->fp, 0, SEEK_SET) == 0 && fread(h, 1, hb, f->fp) == hb;
+        if (ok && h[9] == 2) h[9] = 1;   /* zstd records in, zlib records out (row_qts) */
+        if (!ok || fwrite(h, 1, hb, out) != hb ||
             fseek(f->fp, (long)f->first_rec, SEEK_SET) != 0) {
             fprintf(stderr, "Error writing header!\n");
             die_now();
@@ -1432,6 +1437,59 @@ static int dumpmain(int argc, char *argv[]) {
     }
     b5_close(f);
     return ret == B5_EOF ? 0 : 1;
+}
+
+/* hidden helper for tests: _zstd FILE decodes the zstd frame in FILE with the host decoder (zstd_dec.c) and writes the
+ * content to stdout; a frame that is refused: exit 1, "zstd status N: ..." on stderr.  With --head N: the frame's first
+ * N bytes as zsd_decode_head gives them (what b5_parse_head uses).  No GPU. */
+static int zstdmain(int argc, char *argv[]) {
+    long head = -1;
+    if (argc == 4 && strcmp(argv[1], "--head") == 0) {
+        head = atol(argv[2]);
+        argv += 2;
+        argc -= 2;
+    }
+    if (argc != 2 || head < -1 || head > (1l << 30)) {
+        fprintf(stderr, "Usage: sigtk-amd _zstd [--head N] FILE\n");
+        return 1;
+    }
+    FILE *fp = fopen(argv[1], "rb");
+    if (!fp) {
+        fprintf(stderr, "Error in opening file\n");
+        return 1;
+    }
+    uint8_t *in = NULL;
+    size_t n = 0, cap = 0;
+    for (;;) {
+        if (n == cap) {
+            cap = cap ? cap * 2 : 1 << 16;
+            in = (uint8_t *)realloc(in, cap);
+            if (!in) die_mem();
+        }
+        const size_t got = fread(in + n, 1, cap - n, fp);
+        if (got == 0) break;
+        n += got;
+    }
+    fclose(fp);
+    uint64_t size = 0;
+    int st = zsd_content_size(in, n, &size);
+    if (st == ZSD_OK && size > (1ull << 31)) st = ZSD_ERR_SIZE;
+    uint8_t *out = NULL;
+    size_t got = 0;
+    if (st == ZSD_OK) {
+        const size_t room = head >= 0 ? (size_t)head : (size_t)size;
+        out = (uint8_t *)malloc(room ? room : 1);
+        if (!out) die_mem();
+        st = head >= 0 ? zsd_decode_head(in, n, out, room, &got) : zsd_decode(in, n, out, room, &got);
+    }
+    int ret = 0;
+    if (st != ZSD_OK) {
+        fprintf(stderr, "zstd status %d: %s\n", st, zsd_status_name(st));
+        ret = 1;
+    } else if (fwrite(out, 1, got, stdout) != got) ret = 1;
+    free(in);
+    free(out);
+    return ret;
 }
 
 /* hidden helper for tests: fmt_f6 / fmt_i64 against snprintf on every stride-th float bit pattern */
@@ -1590,6 +1648,8 @@ int main(int argc, char *argv[]) {
         return modelcheckmain(argc - 1, argv + 1);
     } else if (strcmp(argv[1], "_dump") == 0) {
         return dumpmain(argc - 1, argv + 1);
+    } else if (strcmp(argv[1], "_zstd") == 0) {
+        return zstdmain(argc - 1, argv + 1);
     } else if (strcmp(argv[1], "_fmtcheck") == 0) {
         return fmtcheckmain(argc - 1, argv + 1);
     } else if (strcmp(argv[1], "_textcheck") == 0) {
