@@ -72,7 +72,8 @@ extern "C" {
  *        the six-argument plan call is sgk_event_plan_opt; sgk_event_plan is the 0.1.0 five-argument form again (deprecated).
  * 0.2.3: SGK_JOB_EVENTS_LENGTHS (additive submit flag).  Additive to 0.2.3 (no version change): sgk_sigtext_decode;
  *        SGK_SIGNAL_TEXT for sgk_job_begin; sgk_ss_* (`ss paf2tsv`: decode, text, host pipe); sgk_zstd_decompress,
- *        SGK_RECORD_ZLIB / SGK_RECORD_ZSTD and sgk_job_begin_zrec_format (BLOW5 files with zstd records). */
+ *        SGK_RECORD_ZLIB / SGK_RECORD_ZSTD and sgk_job_begin_zrec_format (BLOW5 files with zstd records);
+ *        sgk_aux_field_t, sgk_zrec_tail_check and sgk_job_begin_zrec_aux (records with variable-length auxiliary fields). */
 #define SGK_VERSION_STRING "0.2.3"
 
 /* ---- error codes --------------------------------------------------------------- */
@@ -424,6 +425,30 @@ int sgk_inflate(const uint8_t *in, const uint64_t *in_offsets, const uint32_t *i
 int sgk_zstd_decompress(const uint8_t *in, const uint64_t *in_offsets, const uint32_t *in_lengths, uint32_t n, uint8_t *out,
                         const uint64_t *out_offsets, const uint32_t *out_caps, uint32_t *out_lengths, uint32_t *status,
                         void *stream);
+
+/* ---- the auxiliary fields of an inflated BLOW5 record, checked on the device (additive to 0.2.3) ----------------------- */
+/* Behind its signal a record carries one field per auxiliary column of the file's header, in header order: a primitive
+ * column elem_bytes bytes, an array column (`char*`, `double*`, `enum{..}*`) a u64 element count and then count x
+ * elem_bytes bytes (slow5lib/src/slow5.c:3088-3165).  With an array column the inflated length of a record does not
+ * follow from its head; sgk_zrec_tail_check walks the fields of n records, one lane per record, and tells whether they
+ * fill the record exactly.  inflated: device buffer, record r's rec_lengths[r] bytes at inflated + rec_offsets[r] (any
+ * byte alignment); tail_offsets[r]: where the record's signal ends, relative to the record.  fields is a HOST table of
+ * n_fields columns (elem_bytes 1, 2, 4 or 8; any number of columns -- up to 256 the table travels with the launch and the
+ * call only enqueues work, with more it goes through a temporary device buffer and the call waits for the stream).
+ * Nothing at or behind rec_offsets[r] + rec_lengths[r] is read; only status is written.  status[r]:
+ *   0 ok (with n_fields == 0: the record ends exactly at its signal)
+ *   1 the record is shorter than tail_offsets[r]: it ended inside or in front of its signal
+ *   2 a field is missing or cut: no byte left where a field must start, or a count word or data that would end behind
+ *     the record (where the reference reads past its buffer)
+ *   3 bytes are left behind the last field (with n_fields == 0: any byte behind the signal)
+ *   4 an array's count x elem_bytes does not fit in 32 bits */
+typedef struct sgk_aux_field {
+    uint8_t elem_bytes;
+    uint8_t is_array;
+} sgk_aux_field_t;
+int sgk_zrec_tail_check(const uint8_t *inflated, const uint64_t *rec_offsets, const uint32_t *rec_lengths,
+                        const uint32_t *tail_offsets, uint32_t n, const sgk_aux_field_t *fields /* host */,
+                        uint32_t n_fields, uint32_t *status, void *stream);
 
 /* ---- qts: quantise the raw signal (src/qts.c:27-43, :126-142) and re-encode it ------ */
 #define SGK_QTS_FLOOR 0     /* (raw >> b) << b                                       */
@@ -786,6 +811,16 @@ int sgk_job_begin_zrec(sgk_job_t *job, uint32_t n_reads, const uint32_t *lengths
 int sgk_job_begin_zrec_format(sgk_job_t *job, uint32_t n_reads, int record_format, const uint32_t *lengths,
                               const uint32_t *rec_bytes, const uint32_t *sig_offset, const uint32_t *sig_bytes,
                               const uint32_t *rec_room, sgk_job_input_t *in);
+/* sgk_job_begin_zrec_format for a file whose records carry auxiliary fields of the given columns (host table, copied;
+ * n_fields 0: none), arrays included (additive to 0.2.3).  rec_room[r] is then an upper bound -- for zstd records the
+ * content size the frame declares, for zlib records head + signal + the fixed fields + room for every array -- and what a
+ * record inflated to is checked with sgk_zrec_tail_check against the end of its signal (sig_offset[r] + sig_bytes[r]).
+ * decode_status[r] of a record that inflated but whose fields do not fill it exactly is 0x400 | that status; the inflate
+ * statuses (0x100 |, 0x200 |) come first, as before.  A zlib record that inflates to more than its room reports 0x108:
+ * with an array column that may be a sound record with a long array, which the caller can inflate on the host instead. */
+int sgk_job_begin_zrec_aux(sgk_job_t *job, uint32_t n_reads, int record_format, const uint32_t *lengths,
+                           const uint32_t *rec_bytes, const uint32_t *sig_offset, const uint32_t *sig_bytes,
+                           const uint32_t *rec_room, const sgk_aux_field_t *fields, uint32_t n_fields, sgk_job_input_t *in);
 /* may be called again after sgk_job_wait to run another tool over the same staged batch */
 int sgk_job_submit(sgk_job_t *job, int tool, int rna, int pore, int flags);
 /* qts over the staged batch: quantise (bits in [1,15], method SGK_QTS_*), then hand the signal back as svb-zd blobs

@@ -240,6 +240,18 @@ ENT_HIST_BYTES = 4 * (4 + 8192 + 4096 + 512)   # sizeof(sgk_ent_hist_t)
 SIGNAL_INT16, SIGNAL_SVBZD = 0, 1
 SIGNAL_TEXT = 3   # the raw_signal column of text SLOW5 records, parsed on the GPU
 RECORD_ZLIB, RECORD_ZSTD = 1, 2   # SGK_RECORD_*: what the records of Job.stage_zrec are compressed with
+
+
+class AuxField(C.Structure):   # sgk_aux_field_t: one auxiliary column of a BLOW5 header
+    _fields_ = [("elem_bytes", C.c_uint8), ("is_array", C.c_uint8)]
+
+
+def aux_table(fields):
+    """(elem_bytes, is_array) pairs or AuxField objects -> a ctypes array of sgk_aux_field_t"""
+    tab = (AuxField * max(len(fields), 1))()
+    for k, f in enumerate(fields):
+        tab[k] = f if isinstance(f, AuxField) else AuxField(int(f[0]), int(bool(f[1])))
+    return tab
 JOB_EVENTS_COMPACT = 1
 JOB_TEXT = 4             # pa / event: the rows are written on the device; wait() returns "text" and "row_offsets"
 TEXT_PA, TEXT_EVENT, TEXT_EVENT_COMPACT = 0, 1, 2
@@ -255,7 +267,7 @@ PREFIX_DTYPE = np.dtype([("adapt_x", "<i4"), ("adapt_y", "<i4"), ("polya_x", "<i
 #: every symbol include/sigtk_gpu.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "sgk_strerror", "sgk_version", "sgk_last_hip_error", "sgk_device_count", "sgk_set_device",
-    "sgk_pa", "sgk_event_workspace_bytes", "sgk_event", "sgk_event_pa", "sgk_event_status", "sgk_event_plan", "sgk_event_plan_opt", "sgk_job_long_declined", "sgk_inflate", "sgk_job_begin_zrec", "sgk_zstd_decompress", "sgk_job_begin_zrec_format", "sgk_pipeline", "sgk_stat_lane_rules",
+    "sgk_pa", "sgk_event_workspace_bytes", "sgk_event", "sgk_event_pa", "sgk_event_status", "sgk_event_plan", "sgk_event_plan_opt", "sgk_job_long_declined", "sgk_inflate", "sgk_job_begin_zrec", "sgk_zstd_decompress", "sgk_job_begin_zrec_format", "sgk_zrec_tail_check", "sgk_job_begin_zrec_aux", "sgk_pipeline", "sgk_stat_lane_rules",
     "sgk_event_workspace_bytes_opt", "sgk_event_opt", "sgk_event_pa_opt", "sgk_event_host_opt",
     "sgk_stat_workspace_bytes", "sgk_stat", "sgk_stat_pa", "sgk_jnn_workspace_bytes", "sgk_jnn",
     "sgk_prefix_workspace_bytes", "sgk_prefix", "sgk_stat_opt", "sgk_stat_long_status", "sgk_stat_plan", "sgk_stat_pa_opt", "sgk_jnn_opt", "sgk_prefix_opt",
@@ -421,6 +433,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.sgk_job_set_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.sgk_job_begin_zrec.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 5 + [C.POINTER(JobInput)]
     L.sgk_job_begin_zrec_format.argtypes = [C.c_void_p, C.c_uint32, C.c_int] + [C.c_void_p] * 5 + [C.POINTER(JobInput)]
+    L.sgk_job_begin_zrec_aux.argtypes = [C.c_void_p, C.c_uint32, C.c_int] + [C.c_void_p] * 5 + \
+        [C.POINTER(AuxField), C.c_uint32, C.POINTER(JobInput)]
+    L.sgk_zrec_tail_check.argtypes = [C.c_void_p] * 4 + [C.c_uint32, C.POINTER(AuxField), C.c_uint32, C.c_void_p, C.c_void_p]
     L.sgk_job_text.argtypes = [C.c_void_p, C.POINTER(JobText)]
     L.sgk_text_workspace_bytes.restype = C.c_size_t
     L.sgk_text_workspace_bytes.argtypes = [C.c_int, C.c_uint32, C.c_uint64]
@@ -762,18 +777,26 @@ class Job:
         if ids is not None:
             self.set_ids(ids)
 
-    def stage_zrec(self, records, lengths, sig_offset, sig_bytes, rec_room, dig, off, rng, ids=None, record_format=RECORD_ZLIB):
+    def stage_zrec(self, records, lengths, sig_offset, sig_bytes, rec_room, dig, off, rng, ids=None, record_format=RECORD_ZLIB,
+                   aux=None):
         """sgk_job_begin_zrec_format: `records` are compressed BLOW5 records (bytes; record_format RECORD_ZLIB: zlib
         streams, RECORD_ZSTD: zstd frames) with an svb-zd signal blob at sig_offset[r] (sig_bytes[r] long) of the
-        decompressed record, which is rec_room[r] bytes at most"""
+        decompressed record, which is rec_room[r] bytes at most.  With aux (the file's auxiliary columns: AuxField
+        objects or (elem_bytes, is_array) pairs, [] for none) sgk_job_begin_zrec_aux: rec_room is an upper bound and
+        the fields behind the signal must fill what the record inflated to exactly (decode_status 0x400 | status)"""
         n = len(records)
         u32 = lambda x: np.ascontiguousarray(x, dtype=np.uint32)
         lengths, sig_offset, sig_bytes, rec_room = u32(lengths), u32(sig_offset), u32(sig_bytes), u32(rec_room)
         rbytes = u32([len(b) for b in records])
         jin = JobInput()
-        check(self.L.sgk_job_begin_zrec_format(self.h, n, int(record_format), lengths.ctypes.data, rbytes.ctypes.data,
-                                               sig_offset.ctypes.data, sig_bytes.ctypes.data, rec_room.ctypes.data,
-                                               C.byref(jin)), "sgk_job_begin_zrec_format")
+        if aux is not None:
+            check(self.L.sgk_job_begin_zrec_aux(self.h, n, int(record_format), lengths.ctypes.data, rbytes.ctypes.data,
+                                                sig_offset.ctypes.data, sig_bytes.ctypes.data, rec_room.ctypes.data,
+                                                aux_table(aux), len(aux), C.byref(jin)), "sgk_job_begin_zrec_aux")
+        else:
+            check(self.L.sgk_job_begin_zrec_format(self.h, n, int(record_format), lengths.ctypes.data, rbytes.ctypes.data,
+                                                   sig_offset.ctypes.data, sig_bytes.ctypes.data, rec_room.ctypes.data,
+                                                   C.byref(jin)), "sgk_job_begin_zrec_format")
         for r in range(n):
             jin.digitisation[r] = float(dig[r]); jin.offset[r] = float(off[r]); jin.range[r] = float(rng[r])
             C.memmove(jin.blobs + jin.blob_offsets[r], records[r], len(records[r]))

@@ -20,7 +20,7 @@ from __future__ import annotations
 import struct
 import zlib
 from dataclasses import dataclass, field
-from typing import Dict, Iterator, List, Sequence
+from typing import Dict, Iterator, List, Optional, Sequence
 
 import numpy as np
 
@@ -37,6 +37,7 @@ class Read:
     range: float
     sampling_rate: float
     raw: np.ndarray  # int16
+    aux: Optional[tuple] = None  # write_blow5(aux_types=...): one value per auxiliary column (bytes / str or a sequence for arrays)
 
 
 @dataclass
@@ -158,11 +159,37 @@ _TYPES = "#char*\tuint32_t\tdouble\tdouble\tdouble\tdouble\tuint64_t\tint16_t*\n
 _NAMES = "#read_id\tread_group\tdigitisation\toffset\trange\tsampling_rate\tlen_raw_signal\traw_signal\n"
 
 
+_AUX_PACK = {"int8_t": "b", "uint8_t": "B", "char": "c", "int16_t": "h", "uint16_t": "H", "int32_t": "i", "uint32_t": "I",
+             "float": "f", "int64_t": "q", "uint64_t": "Q", "double": "d"}
+
+
+def aux_field_bytes(type_str: str, value) -> bytes:
+    """one auxiliary field as a binary record stores it (slow5lib/src/slow5.c:3088-3165): a primitive as its bytes, an
+    enum as uint8, an array (`type*`) as a u64 element count and the elements; `char*` takes bytes or str"""
+    arr = type_str.endswith("*")
+    base = type_str[:-1] if arr else type_str
+    code = "B" if base.startswith("enum{") and base.endswith("}") else _AUX_PACK[base]
+    if not arr:
+        if code == "c":
+            value = value.encode("ascii") if isinstance(value, str) else bytes(value)
+        return struct.pack("<" + code, value)
+    if code == "c":
+        data = value.encode("ascii") if isinstance(value, str) else bytes(value)
+        return struct.pack("<Q", len(data)) + data
+    vals = list(value)
+    return struct.pack("<Q%d%s" % (len(vals), code), len(vals), *vals)
+
+
 def write_blow5(path: str, reads: Sequence[Read], attrs: Dict[str, str] | None = None,
-                record_press: int = 1, signal_press: int = 1) -> None:
-    """Write a single-read-group BLOW5 (version 0.2.0) the reference CLI can open."""
+                record_press: int = 1, signal_press: int = 1, aux_types=None) -> None:
+    """Write a single-read-group BLOW5 (version 0.2.0) the reference CLI can open.  aux_types: a list of (name, type
+    string) -- auxiliary columns appended to the type and name lines; every read then carries its values in Read.aux."""
     attrs = dict(attrs or {})
-    text = "".join("@%s\t%s\n" % (k, attrs[k]) for k in sorted(attrs)) + _TYPES + _NAMES
+    types, names = _TYPES, _NAMES
+    if aux_types:
+        types = types[:-1] + "".join("\t" + t for _, t in aux_types) + "\n"
+        names = names[:-1] + "".join("\t" + n for n, _ in aux_types) + "\n"
+    text = "".join("@%s\t%s\n" % (k, attrs[k]) for k in sorted(attrs)) + types + names
     tb = text.encode("ascii")
     head = bytearray(64)
     head[0:6] = MAGIC
@@ -185,6 +212,10 @@ def write_blow5(path: str, reads: Sequence[Read], attrs: Dict[str, str] | None =
             rid = r.read_id.encode("ascii")
             rec = struct.pack("<H", len(rid)) + rid + struct.pack(
                 "<IddddQ", r.read_group, r.digitisation, r.offset, r.range, r.sampling_rate, ln) + sig
+            if aux_types:
+                if r.aux is None or len(r.aux) != len(aux_types):
+                    raise ValueError("read %s: one aux value per column of aux_types is needed" % r.read_id)
+                rec += b"".join(aux_field_bytes(t, v) for (_, t), v in zip(aux_types, r.aux))
             if record_press == 1:
                 rec = zlib.compress(rec)
             fh.write(struct.pack("<Q", len(rec)))

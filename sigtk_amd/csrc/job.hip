@@ -25,6 +25,9 @@
 
 namespace sgk {
 void zstd_release_scratch(int device, hipStream_t st);   // zstd_kernels.hip
+int zrec_tail_check(const uint8_t *inflated, const uint64_t *rec_offsets, const uint32_t *rec_lengths,
+                    const uint32_t *tail_offsets, const uint32_t *gate, uint32_t n, const sgk_aux_field_t *fields,
+                    uint32_t n_fields, uint32_t *status, hipStream_t st);   // zrec_kernels.hip
 
 struct GrowDev {
     void *p = nullptr;
@@ -94,6 +97,14 @@ struct sgk_job {
     GrowDev d_inflated, d_ioffs, d_icaps, d_ilens, d_istat, d_soffs, d_slens;
     uint64_t inflated_bytes = 0;
     int rec_fmt = SGK_RECORD_ZLIB;   // SGK_SIGNAL_ZREC: what the records are compressed with
+    // sgk_job_begin_zrec_aux: the file's auxiliary columns; what every record inflated to (d_ilens) is then checked against
+    // them from the end of its signal (h_toffs, relative to the record) by k_zrec_tail
+    bool aux = false;
+    sgk_aux_field_t *aux_fields = nullptr;
+    uint32_t n_aux = 0, aux_cap = 0;
+    GrowPin h_toffs, h_tstat;
+    GrowDev d_toffs, d_tstat;
+    ~sgk_job() { free(aux_fields); }
     bool long_fetched = false;        // stat / jnn / prefix: the long-read header of the call is on its way to h_long
     uint32_t long_declined = 0;       // ... long reads the long path declined (n_timeouts of sgk_long_status_t), after wait
     int n_dense = 0;                  // arrays to fetch in sgk_job_wait once the dense total is known
@@ -200,6 +211,32 @@ int sgk_job_begin_zrec_format(sgk_job_t *j, uint32_t n_reads, int record_format,
     return rc;
 }
 
+int sgk_job_begin_zrec_aux(sgk_job_t *j, uint32_t n_reads, int record_format, const uint32_t *lengths,
+                           const uint32_t *rec_bytes, const uint32_t *sig_offset, const uint32_t *sig_bytes,
+                           const uint32_t *rec_room, const sgk_aux_field_t *fields, uint32_t n_fields, sgk_job_input_t *in) {
+    if (!j || (n_fields && !fields)) return SGK_ERR_ARG;
+    for (uint32_t c = 0; c < n_fields; ++c) {
+        const uint32_t eb = fields[c].elem_bytes;
+        if ((eb != 1 && eb != 2 && eb != 4 && eb != 8) || fields[c].is_array > 1) return SGK_ERR_ARG;
+    }
+    int rc = sgk_job_begin_zrec_format(j, n_reads, record_format, lengths, rec_bytes, sig_offset, sig_bytes, rec_room, in);
+    if (rc != SGK_OK) return rc;
+    if (n_fields > j->aux_cap) {
+        sgk_aux_field_t *p = static_cast<sgk_aux_field_t *>(realloc(j->aux_fields, sizeof(sgk_aux_field_t) * n_fields));
+        if (!p) return SGK_ERR_NOMEM;
+        j->aux_fields = p;
+        j->aux_cap = n_fields;
+    }
+    if (n_fields) memcpy(j->aux_fields, fields, sizeof(sgk_aux_field_t) * n_fields);
+    j->n_aux = n_fields;
+    const size_t nr1 = n_reads ? n_reads : 1;
+    if ((rc = j->h_toffs.ensure(nr1 * 4)) != SGK_OK) return rc;
+    uint32_t *to = j->h_toffs.as<uint32_t>();
+    for (size_t r = 0; r < n_reads; ++r) to[r] = sig_offset[r] + sig_bytes[r];   // <= rec_room[r]: job_begin checked
+    j->aux = true;
+    return SGK_OK;
+}
+
 static int job_begin(sgk_job_t *j, uint32_t n_reads, const uint32_t *lengths, int signal_format, const uint32_t *blob_bytes,
                      const uint32_t *sig_offset, const uint32_t *sig_bytes, const uint32_t *rec_room, sgk_job_input_t *in) {
     if (!j || !in || (n_reads && !lengths)) return SGK_ERR_ARG;
@@ -230,6 +267,7 @@ static int job_begin(sgk_job_t *j, uint32_t n_reads, const uint32_t *lengths, in
     j->max_len = mx;
     j->n_samples = o + 64;
     j->fmt = signal_format;
+    j->aux = false;
     j->blob_bytes = 0;
     memset(in, 0, sizeof *in);
     if (signal_format == SGK_SIGNAL_SVBZD || signal_format == SGK_SIGNAL_ZREC || signal_format == SGK_SIGNAL_TEXT) {
@@ -349,6 +387,17 @@ static int job_upload(sgk_job_t *j, sgk_batch_t *view) {
         if (rc != SGK_OK) return rc;
         if ((rc = d2h(j->h_dstat, j->d_dstat, nr * 4, st)) != SGK_OK) return rc;
         if ((rc = d2h(j->h_istat, j->d_istat, nr * 4, st)) != SGK_OK) return rc;
+        if (j->aux) {
+            // what every record inflated to against the file's columns (a record that did not inflate is not looked at:
+            // its length word may lie behind its room)
+            if ((rc = h2d(j->d_toffs, j->h_toffs, nr * 4, st)) != SGK_OK) return rc;
+            if ((rc = j->d_tstat.ensure(nr * 4)) != SGK_OK) return rc;
+            rc = zrec_tail_check(j->d_inflated.as<uint8_t>(), j->d_ioffs.as<uint64_t>(), j->d_ilens.as<uint32_t>(),
+                                 j->d_toffs.as<uint32_t>(), j->d_istat.as<uint32_t>(), j->n_reads, j->aux_fields, j->n_aux,
+                                 j->d_tstat.as<uint32_t>(), st);
+            if (rc != SGK_OK) return rc;
+            if ((rc = d2h(j->h_tstat, j->d_tstat, nr * 4, st)) != SGK_OK) return rc;
+        }
     } else if (j->fmt == SGK_SIGNAL_SVBZD || j->fmt == SGK_SIGNAL_TEXT) {
         if ((rc = j->d_samples.ensure(j->n_samples * sizeof(int16_t))) != SGK_OK) return rc;
         if ((rc = h2d(j->d_blobs, j->h_blobs, j->blob_bytes, st)) != SGK_OK) return rc;
@@ -705,9 +754,11 @@ int sgk_job_wait(sgk_job_t *j) {
         // records: 0x200 | sgk_zstd_decompress's status).
         uint32_t *ds = j->h_dstat.as<uint32_t>();
         const uint32_t *is = j->h_istat.as<uint32_t>();
+        const uint32_t *ts = j->aux ? j->h_tstat.as<uint32_t>() : nullptr;   // (sgk_job_begin_zrec_aux: 0x400 | k_zrec_tail's)
         bool bad = false;
         for (uint32_t r = 0; r < j->n_reads; ++r) {
             if (is[r] != 0) ds[r] = (j->rec_fmt == SGK_RECORD_ZSTD ? 0x200u : 0x100u) | is[r];
+            else if (ts && ts[r] != 0) ds[r] = 0x400u | ts[r];
             bad = bad || ds[r] != 0;
         }
         if (bad) return SGK_ERR_FORMAT;

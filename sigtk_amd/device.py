@@ -441,6 +441,24 @@ def zstd_decompress(frames, caps=None, device: Optional[torch.device] = None, wi
     return kept, olen, st
 
 
+def zrec_tail_check(inflated: torch.Tensor, rec_offsets: torch.Tensor, rec_lengths: torch.Tensor,
+                    tail_offsets: torch.Tensor, fields, status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sgk_zrec_tail_check over torch buffers on one device: inflated uint8; rec_offsets int64 (uint64 bits);
+    rec_lengths / tail_offsets int32 (uint32 bits), one entry per record; fields: the file's auxiliary columns
+    (api.AuxField objects or (elem_bytes, is_array) pairs -- a host table).  -> status, int32 per record (enqueued on the
+    current stream, not synchronised)"""
+    L = api.load_library()
+    n = int(rec_offsets.numel())
+    assert inflated.dtype == torch.uint8 and rec_offsets.dtype == torch.int64
+    assert rec_lengths.dtype == torch.int32 and tail_offsets.dtype == torch.int32
+    assert int(rec_lengths.numel()) == n and int(tail_offsets.numel()) == n
+    if status is None:
+        status = torch.full((max(n, 1),), -1, dtype=torch.int32, device=inflated.device)
+    api.check(L.sgk_zrec_tail_check(_ptr(inflated), _ptr(rec_offsets), _ptr(rec_lengths), _ptr(tail_offsets), n,
+                                    api.aux_table(fields), len(fields), _ptr(status), _stream_ptr()), "sgk_zrec_tail_check")
+    return status
+
+
 # ---------------------------------------------------------------------- TSV rows written on the device (sgk_text_*)
 
 class TextWriter:

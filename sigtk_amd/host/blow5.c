@@ -810,7 +810,7 @@ int b5_parse_head(const b5_file_t *f, const uint8_t *raw, uint64_t size, uint8_t
             continue;
         }
         out->rec = NULL;
-        out->rec_len = 0;
+        out->rec_len = z_room;   /* zstd: what the frame says the record inflates to; zlib: 0, not known from the head */
         out->read_id = (const char *)(p + 2);
         out->id_len = idl;
         const uint8_t *q = p + 2 + idl;
@@ -873,6 +873,60 @@ int64_t b5_aux_fixed_bytes(const b5_file_t *f) {
         q = e + 1;
     }
     return col >= 8 ? total : -1;
+}
+
+/* bytes of one element of the type named by q[0 .. n), or 0 for an unknown name */
+static int aux_elem_bytes(const char *q, size_t n) {
+    if ((n == 6 && !strncmp(q, "int8_t", 6)) || (n == 7 && !strncmp(q, "uint8_t", 7)) || (n == 4 && !strncmp(q, "char", 4))) return 1;
+    if ((n == 7 && !strncmp(q, "int16_t", 7)) || (n == 8 && !strncmp(q, "uint16_t", 8))) return 2;
+    if ((n == 7 && !strncmp(q, "int32_t", 7)) || (n == 8 && !strncmp(q, "uint32_t", 8)) || (n == 5 && !strncmp(q, "float", 5))) return 4;
+    if ((n == 7 && !strncmp(q, "int64_t", 7)) || (n == 8 && !strncmp(q, "uint64_t", 8)) || (n == 6 && !strncmp(q, "double", 6))) return 8;
+    if (n >= 5 && !strncmp(q, "enum{", 5) && q[n - 1] == '}') return 1;  /* enums are stored as uint8_t */
+    return 0;
+}
+
+int64_t b5_aux_fields(const b5_file_t *f, b5_aux_field_t **out) {
+    /* the type line, as b5_aux_fixed_bytes reads it (slow5lib/src/slow5.c:794-881; an array field is a u64 element count
+     * and the elements, slow5.c:3088-3165) */
+    *out = NULL;
+    const char *p = f->hdr_text;
+    const char *line = NULL;
+    while (p && *p) {
+        if (p[0] == '#' && strncmp(p, "#char*", 6) == 0) { line = p; break; }
+        p = strchr(p, '\n');
+        if (p) ++p;
+    }
+    if (!line) return -1;
+    b5_aux_field_t *tab = NULL;
+    int64_t n_tab = 0, cap = 0;
+    int col = 0;
+    const char *q = line + 1;
+    for (;;) {
+        const char *e = q;
+        while (*e && *e != '\t' && *e != '\n') ++e;
+        size_t n = (size_t)(e - q);
+        if (col >= 8) {
+            const int arr = n && q[n - 1] == '*';
+            if (arr) --n;
+            const int sz = aux_elem_bytes(q, n);
+            if (!sz) { free(tab); return -1; }
+            if (n_tab == cap) {
+                cap = cap ? cap * 2 : 16;
+                b5_aux_field_t *t = (b5_aux_field_t *)realloc(tab, sizeof *tab * (size_t)cap);
+                if (!t) { free(tab); return -1; }
+                tab = t;
+            }
+            tab[n_tab].elem_bytes = (uint8_t)sz;
+            tab[n_tab].is_array = (uint8_t)arr;
+            ++n_tab;
+        }
+        ++col;
+        if (*e != '\t') break;
+        q = e + 1;
+    }
+    if (col < 8) { free(tab); return -1; }
+    *out = tab;
+    return n_tab;
 }
 
 int b5_svb_zd_decode(const uint8_t *blob, uint64_t nbytes, int16_t *dst, uint32_t count) {

@@ -107,12 +107,22 @@ int b5_parse_raw(const b5_file_t *f, const uint8_t *raw, uint64_t size, uint8_t 
  * signal_offset tells where the signal starts in the inflated record.  A small part of the whole inflate: the record
  * itself is inflated on the GPU (sgk_job_begin_zrec).  For a zstd record that part is the first block's Huffman and FSE
  * tables, the first 512 literals and the first sequences (zsd_decode_head): some 16 us against 1 ms for the whole record
- * of a 100 000-sample read.  Files with compressed records only; rec_len is 0. */
+ * of a 100 000-sample read.  Files with compressed records only; rec_len is the content size a zstd
+ * frame declares (the inflated length of the record, if the frame keeps its word) and 0 for a zlib record. */
 int b5_parse_head(const b5_file_t *f, const uint8_t *raw, uint64_t size, uint8_t **scratch, uint64_t *scratch_cap,
                   b5_view_t *out);
 /* bytes of a record's auxiliary fields when all of them are primitive (fixed size), else -1 (an array field, an unknown
  * type): with a fixed size the inflated length of a record follows from its head */
 int64_t b5_aux_fixed_bytes(const b5_file_t *f);
+/* The auxiliary columns of the header's type line as a table, one entry per column in header order (malloc'd into *out;
+ * caller frees; NULL for none).  A type ending in '*' is an array of its element type ("char*": 1-byte elements,
+ * "enum{..}*" too), an enum is 1 byte.  Returns the number of columns, or -1 for no table: no type line, fewer than the
+ * eight primary columns, an unknown type name, out of memory. */
+typedef struct {
+    uint8_t elem_bytes; /* 1, 2, 4 or 8 */
+    uint8_t is_array;
+} b5_aux_field_t;
+int64_t b5_aux_fields(const b5_file_t *f, b5_aux_field_t **out);
 /* scalar streamvbyte + zigzag-delta decode of one blob into dst[count] (host-decode fallback path) */
 int b5_svb_zd_decode(const uint8_t *blob, uint64_t nbytes, int16_t *dst, uint32_t count);
 /* scalar parse of a text SLOW5 raw_signal column (nbytes of text, no tab or newline) into dst[count]: the grammar of

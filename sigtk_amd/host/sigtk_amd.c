@@ -302,6 +302,7 @@ typedef struct {
     uint8_t *scratch;           /* inflated record (kept per slot; grows only) */
     uint64_t scratch_cap;
     b5_view_t v;
+    uint32_t room;              /* zrec: what the inflated record may take (load_parse) */
     int err;
 } lrec_t;
 
@@ -371,8 +372,13 @@ typedef struct {
     int mode, nthreads, host_decode;
     int gpu_text;        /* --gpu-text (pa / event, whole-file mode): the rows come from the GPU as text */
     uint64_t text_bytes; /* ... their bytes over PCIe */
-    int zrec;            /* records go to the GPU as they sit in the file (zlib records, svb-zd signal, fixed-size auxiliary fields) */
-    int64_t aux_bytes;   /* ... the bytes of a record's auxiliary fields then */
+    int zrec;            /* records go to the GPU as they sit in the file (zlib / zstd records, svb-zd signal, auxiliary columns of known types) */
+    sgk_aux_field_t *aux_tab; /* ... those columns, in header order */
+    uint32_t n_aux, n_aux_arrays; /* ... how many, and how many of them are arrays (u64 count + elements) */
+    uint64_t aux_fixed;  /* ... the bytes of the others */
+    uint64_t aux_slack;  /* ... zlib records: room per array column behind its count word (--aux-slack) */
+    uint64_t n_zrec_reads;    /* records the GPU decompressed */
+    uint64_t n_redone;        /* zrec batches redone on the host path (an array longer than its slack) */
     opt_t opt;
     queue_t free_q, filled_q, ready_q;
     /* reader thread input */
@@ -420,17 +426,29 @@ static void batch_add_record(batch_t *b, uint64_t size, const uint8_t *ref) {
 typedef struct {
     pipe_t *P;
     batch_t *b;
+    int zrec;   /* parse the head only (batch_launch of a zrec file); 0: the whole record on the host (and batch_redo_host) */
 } lctx_t;
 static void load_parse(void *ctx_, uint32_t i, int tid) {
     (void)tid;
     lctx_t *c = (lctx_t *)ctx_;
+    const pipe_t *P = c->P;
     lrec_t *r = &c->b->recs[i];
     const uint8_t *raw = r->raw_ptr ? r->raw_ptr : c->b->raw + r->raw_off;
+    if (!c->zrec) {
+        r->err = b5_parse_raw(P->f, raw, r->raw_size, &r->scratch, &r->scratch_cap, &r->v);
+        return;
+    }
     /* zrec: the head only (id, scaling, sizes: a few hundred inflated bytes); the record itself is inflated on the GPU */
-    if (c->P->zrec) r->err = b5_parse_head(c->P->f, raw, r->raw_size, &r->scratch, &r->scratch_cap, &r->v);
-    else r->err = b5_parse_raw(c->P->f, raw, r->raw_size, &r->scratch, &r->scratch_cap, &r->v);
-    if (c->P->zrec && !r->err && (r->raw_size > 0xffffffffull || r->v.signal_offset + r->v.signal_bytes + (uint64_t)c->P->aux_bytes > 0xffffffffull))
-        r->err = B5_ERR_FORMAT;
+    r->err = b5_parse_head(P->f, raw, r->raw_size, &r->scratch, &r->scratch_cap, &r->v);
+    if (r->err) return;
+    /* Room for the inflated record.  A zstd frame declares its content size: that is the room, exactly.  A zlib stream
+     * does not: head + signal + the fixed-size fields + for every array column its count word and a slack (a design
+     * constant: ONT's array fields are a few bytes); a record whose arrays are longer comes back 0x108 and its batch is
+     * redone on the host (writer_main).  Either way the GPU checks what the record inflated to against the columns. */
+    const uint64_t end = (uint64_t)r->v.signal_offset + r->v.signal_bytes;
+    const uint64_t room = P->f->record_press == 2 ? r->v.rec_len : end + P->aux_fixed + (uint64_t)P->n_aux_arrays * (8 + P->aux_slack);
+    if (r->raw_size > 0xffffffffull || room > 0xffffffffull || end > room) r->err = B5_ERR_FORMAT;
+    r->room = (uint32_t)room;
 }
 /* phase 2 (parallel): stage record i's signal and scaling into the job's pinned buffers */
 static void load_stage(void *ctx_, uint32_t i, int tid) {
@@ -454,9 +472,59 @@ static void load_stage(void *ctx_, uint32_t i, int tid) {
     }
 }
 
+/* --gpu-text: the ids travel with the batch; the job hands back the rows as the reference prints them */
+static void batch_set_ids(batch_t *b) {
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < b->n; i++) total += b->recs[i].v.id_len;
+    if (total > 0xffffffffull) {
+        ERROR("cmain", "%s", "the read ids of one batch exceed 4 GB: use a smaller --batch-samples");
+        die_now();
+    }
+    if ((uint64_t)b->n + 1 > b->id_offs_cap) {
+        b->id_offs_cap = (uint64_t)b->n + 1;
+        b->id_offs = (uint32_t *)realloc(b->id_offs, sizeof(uint32_t) * b->id_offs_cap);
+    }
+    if (total + 1 > b->id_blob_cap) {
+        b->id_blob_cap = total + 1;
+        b->id_blob = (uint8_t *)realloc(b->id_blob, b->id_blob_cap);
+    }
+    if (!b->id_offs || !b->id_blob) die_mem();
+    uint32_t o = 0;
+    for (uint32_t i = 0; i < b->n; i++) {
+        b->id_offs[i] = o;
+        memcpy(b->id_blob + o, b->recs[i].v.read_id, b->recs[i].v.id_len);
+        o += (uint32_t)b->recs[i].v.id_len;
+    }
+    b->id_offs[b->n] = o;
+    const int rc = sgk_job_set_ids(b->job, b->id_blob, b->id_offs);
+    if (rc != SGK_OK) gpu_fail("sgk_job_set_ids", rc);
+}
+
+/* the staged batch to its subtool */
+static void batch_submit(pipe_t *P, batch_t *b) {
+    int tool = SGK_TOOL_PA, flags = 0, rc;
+    switch (P->mode) {
+        case MODE_EVENT: tool = SGK_TOOL_EVENT; flags = P->opt.compact ? SGK_JOB_EVENTS_LENGTHS : 0; break;
+        case MODE_STAT: tool = SGK_TOOL_STAT; break;
+        case MODE_PREFIX: tool = SGK_TOOL_PREFIX; break;
+        case MODE_JNN: tool = SGK_TOOL_JNN; break;
+        case MODE_ENT: tool = SGK_TOOL_ENT; break;
+        default: break;
+    }
+    if (P->gpu_text) {
+        batch_set_ids(b);
+        flags |= SGK_JOB_TEXT;
+    }
+    if (P->mode == MODE_QTS)
+        rc = sgk_job_submit_qts(b->job, P->q_bits, P->q_method, P->f->signal_press == 1 ? SGK_SIGNAL_SVBZD : SGK_SIGNAL_INT16);
+    else
+        rc = sgk_job_submit(b->job, tool, P->opt.rna, P->opt.pore, flags);
+    if (rc != SGK_OK) gpu_fail("sgk_job_submit", rc);
+}
+
 /* parse + stage + submit the records gathered in b */
 static void batch_launch(pipe_t *P, batch_t *b) {
-    lctx_t c = {P, b};
+    lctx_t c = {P, b, P->zrec};
     double t0 = realtime();
     pfor(P->load_pool, b->n, load_parse, &c);
     for (uint32_t i = 0; i < b->n; i++) {
@@ -473,7 +541,7 @@ static void batch_launch(pipe_t *P, batch_t *b) {
         if (P->zrec) {
             b->sig_off[i] = b->recs[i].v.signal_offset;
             b->sig_len[i] = (uint32_t)b->recs[i].v.signal_bytes;
-            b->room[i] = (uint32_t)(b->recs[i].v.signal_offset + b->recs[i].v.signal_bytes + (uint64_t)P->aux_bytes);
+            b->room[i] = b->recs[i].room;
         }
         P->n_samples += b->recs[i].v.n_samples;
     }
@@ -484,7 +552,7 @@ static void batch_launch(pipe_t *P, batch_t *b) {
     b->sigtext = P->f->text && !P->host_decode;
     b->zrec = P->zrec;
     int rc;
-    if (b->zrec) rc = sgk_job_begin_zrec_format(b->job, b->n, P->f->record_press == 2 ? SGK_RECORD_ZSTD : SGK_RECORD_ZLIB, b->lengths, b->blob_bytes, b->sig_off, b->sig_len, b->room, &b->in);
+    if (b->zrec) rc = sgk_job_begin_zrec_aux(b->job, b->n, P->f->record_press == 2 ? SGK_RECORD_ZSTD : SGK_RECORD_ZLIB, b->lengths, b->blob_bytes, b->sig_off, b->sig_len, b->room, P->aux_tab, P->n_aux, &b->in);
     else rc = sgk_job_begin(b->job, b->n, b->lengths, b->sigtext ? SGK_SIGNAL_TEXT : (b->svb ? SGK_SIGNAL_SVBZD : SGK_SIGNAL_INT16), b->blob_bytes, &b->in);
     if (rc != SGK_OK) gpu_fail("sgk_job_begin", rc);
     pfor(P->load_pool, b->n, load_stage, &c);
@@ -494,48 +562,7 @@ static void batch_launch(pipe_t *P, batch_t *b) {
             die_now();
         }
     }
-    int tool = SGK_TOOL_PA, flags = 0;
-    switch (P->mode) {
-        case MODE_EVENT: tool = SGK_TOOL_EVENT; flags = P->opt.compact ? SGK_JOB_EVENTS_LENGTHS : 0; break;
-        case MODE_STAT: tool = SGK_TOOL_STAT; break;
-        case MODE_PREFIX: tool = SGK_TOOL_PREFIX; break;
-        case MODE_JNN: tool = SGK_TOOL_JNN; break;
-        case MODE_ENT: tool = SGK_TOOL_ENT; break;
-        default: break;
-    }
-    if (P->gpu_text) {
-        /* the ids travel with the batch; the job hands back the rows as the reference prints them */
-        uint64_t total = 0;
-        for (uint32_t i = 0; i < b->n; i++) total += b->recs[i].v.id_len;
-        if (total > 0xffffffffull) {
-            ERROR("cmain", "%s", "the read ids of one batch exceed 4 GB: use a smaller --batch-samples");
-            die_now();
-        }
-        if ((uint64_t)b->n + 1 > b->id_offs_cap) {
-            b->id_offs_cap = (uint64_t)b->n + 1;
-            b->id_offs = (uint32_t *)realloc(b->id_offs, sizeof(uint32_t) * b->id_offs_cap);
-        }
-        if (total + 1 > b->id_blob_cap) {
-            b->id_blob_cap = total + 1;
-            b->id_blob = (uint8_t *)realloc(b->id_blob, b->id_blob_cap);
-        }
-        if (!b->id_offs || !b->id_blob) die_mem();
-        uint32_t o = 0;
-        for (uint32_t i = 0; i < b->n; i++) {
-            b->id_offs[i] = o;
-            memcpy(b->id_blob + o, b->recs[i].v.read_id, b->recs[i].v.id_len);
-            o += (uint32_t)b->recs[i].v.id_len;
-        }
-        b->id_offs[b->n] = o;
-        rc = sgk_job_set_ids(b->job, b->id_blob, b->id_offs);
-        if (rc != SGK_OK) gpu_fail("sgk_job_set_ids", rc);
-        flags |= SGK_JOB_TEXT;
-    }
-    if (P->mode == MODE_QTS)
-        rc = sgk_job_submit_qts(b->job, P->q_bits, P->q_method, P->f->signal_press == 1 ? SGK_SIGNAL_SVBZD : SGK_SIGNAL_INT16);
-    else
-        rc = sgk_job_submit(b->job, tool, P->opt.rna, P->opt.pore, flags);
-    if (rc != SGK_OK) gpu_fail("sgk_job_submit", rc);
+    batch_submit(P, b);
     P->t_stage += realtime() - t1;
     if (g_t_first_submit == 0.0) g_t_first_submit = realtime();
     q_push(&P->ready_q, b);
@@ -766,6 +793,31 @@ static void row_qts(sbuf_t *o, const batch_t *b, const sgk_job_output_t *out, ui
     }
 }
 
+/* A zrec batch of a zlib file with array columns came back with nothing but 0x108: records that inflate to more than
+ * their room, i.e. an array longer than the slack (or a broken record, which then gets the host path's error).  The
+ * batch's records are still where the reader put them: inflate and parse them on the host, stage their svb-zd blobs,
+ * submit and wait again -- in the writer, so the file's order is kept. */
+static int batch_redo_host(pipe_t *P, batch_t *b, pool_t *pool) {
+    lctx_t c = {P, b, 0};
+    pfor(pool, b->n, load_parse, &c);
+    for (uint32_t i = 0; i < b->n; i++) {
+        if (!b->recs[i].err && b->recs[i].v.n_samples != b->lengths[i]) b->recs[i].err = B5_ERR_FORMAT;
+        if (b->recs[i].err) {
+            fprintf(stderr, "Error in slow5_get_next. Error code %d\n", b->recs[i].err);
+            die_now();
+        }
+        b->blob_bytes[i] = (uint32_t)b->recs[i].v.signal_bytes;
+    }
+    b->zrec = 0;
+    b->svb = 1;
+    int rc = sgk_job_begin(b->job, b->n, b->lengths, SGK_SIGNAL_SVBZD, b->blob_bytes, &b->in);
+    if (rc != SGK_OK) gpu_fail("sgk_job_begin", rc);
+    pfor(pool, b->n, load_stage, &c);
+    batch_submit(P, b);
+    P->n_redone++;
+    return sgk_job_wait(b->job);
+}
+
 /* ------------------------------------------------------------------ writer */
 
 typedef struct {
@@ -807,7 +859,14 @@ static void *writer_main(void *arg) {
         if (b->last) break;
         double t0 = realtime();
         int rc = sgk_job_wait(b->job);
-        if (rc == SGK_ERR_FORMAT && (b->zrec || b->sigtext)) {
+        const int was_zrec = b->zrec;
+        if (rc == SGK_ERR_FORMAT && b->zrec && P->f->record_press == 1 && P->n_aux_arrays > 0) {
+            sgk_job_output_t o;
+            int only_room = sgk_job_output(b->job, &o) == SGK_OK && o.decode_status != NULL;
+            for (uint32_t r = 0; only_room && r < b->n; r++) only_room = o.decode_status[r] == 0 || o.decode_status[r] == 0x108u;
+            if (only_room) rc = batch_redo_host(P, b, wpool);
+        }
+        if (rc == SGK_ERR_FORMAT && (was_zrec || b->sigtext)) {
             /* a record that does not inflate (or not to what its head announced), a blob that does not decode, or a text
              * signal column with a malformed token or another number of tokens than the record announces: what the
              * reference reports for it (slow5_get_next's negative return, src/cmain.c:121-124) */
@@ -815,6 +874,7 @@ static void *writer_main(void *arg) {
             die_now();
         }
         if (rc != SGK_OK) gpu_fail("sgk_job_wait", rc);
+        if (b->zrec) P->n_zrec_reads += b->n;
         P->n_long_declined += sgk_job_long_declined(b->job);
         wctx_t c;
         c.P = P;
@@ -1004,6 +1064,9 @@ static void run_pipeline(pipe_t *P, int n_gpus, double t_init) {
     if (getenv("SGK_CLI_TIMING") && P->gpu_text)
         fprintf(stderr, "[sigtk-amd] --gpu-text: %lu bytes of rows over PCIe (formatted on the GPU; no pA floats / event arrays)\n",
                 (unsigned long)P->text_bytes);
+    if (getenv("SGK_CLI_TIMING"))
+        fprintf(stderr, "[sigtk-amd] records decompressed on the GPU: %lu of %lu; batches redone on the host: %lu\n",
+                (unsigned long)P->n_zrec_reads, (unsigned long)P->n_reads, (unsigned long)P->n_redone);
     /* The process is about to leave through _exit (main): the jobs' pinned and device buffers go with it.  Releasing
      * them one hipHostFree / hipFree at a time costs more than a small input's whole pipeline (SGK_CLI_TIMING shows
      * it), so they are only released when asked to (leak checkers: SGK_CLI_FREE=1). */
@@ -1052,7 +1115,7 @@ static struct option long_options[] = {
     {"output", required_argument, 0, 'o'},  {"print-stat", no_argument, 0, 0},   {"no-header", no_argument, 0, 'n'},
     {"compact", no_argument, 0, 'c'},       {"gpus", required_argument, 0, 0},   {"batch-samples", required_argument, 0, 0},
     {"threads", required_argument, 0, 't'}, {"host-decode", no_argument, 0, 0},  {"host-inflate", no_argument, 0, 0},
-    {"gpu-text", no_argument, 0, 0},        {0, 0, 0, 0}};
+    {"gpu-text", no_argument, 0, 0},        {"aux-slack", required_argument, 0, 0}, {0, 0, 0, 0}};
 
 static int cmain(int argc, char *argv[], const char *mode_s) {
     /* `ent` has its own front end in the reference (src/ent.c:63-105): only -h/-V (and --no-header) are options,
@@ -1064,6 +1127,7 @@ static int cmain(int argc, char *argv[], const char *mode_s) {
     int8_t hdr = 1;
     opt_t opt = {0, 0, 0, 0};
     int n_gpus = 1, nthreads = 0, host_decode = 0, host_inflate = 0, batch_set = 0, gpu_text = 0;
+    uint64_t aux_slack = 256; /* bytes of room per array column of a zlib record sent to the GPU (load_parse) */
     /* default batch: small (16 M samples) where the GPU stage is short -- a job's buffers are then cheap to set up
      * and the host stages overlap sooner; 64 M for jnn / prefix, whose one-read-per-lane kernels take as long for
      * a small batch as for a large one */
@@ -1094,6 +1158,9 @@ static int cmain(int argc, char *argv[], const char *mode_s) {
             host_inflate = 1;
         } else if (c == 0 && longindex == 12) {
             gpu_text = 1;
+        } else if (c == 0 && longindex == 13) {
+            aux_slack = strtoull(optarg, NULL, 10);
+            if (aux_slack > (1ull << 20)) aux_slack = 1ull << 20;
         }
     }
     if (is_ent && (argc - optind != 1 || fp_help == stdout)) {
@@ -1118,6 +1185,7 @@ static int cmain(int argc, char *argv[], const char *mode_s) {
         fprintf(fp_help, "   --host-decode              decode svb-zd signals (parse text SLOW5 signals) on the host instead of the GPU\n");
         fprintf(fp_help, "   --host-inflate             decompress zlib / zstd records on the host threads instead of the GPU\n");
         fprintf(fp_help, "   --gpu-text                 pa / event, whole-file mode: format the rows on the GPU and fetch them as text\n");
+        fprintf(fp_help, "   --aux-slack INT            test option\n");
         exit(fp_help == stdout ? EXIT_SUCCESS : EXIT_FAILURE);
     }
 
@@ -1180,11 +1248,29 @@ static int cmain(int argc, char *argv[], const char *mode_s) {
     P.mode = mode;
     P.nthreads = nthreads;
     P.host_decode = host_decode;
-    /* Records go to the GPU as they sit in the file when they are zlib streams or zstd frames around an svb-zd signal and their
-     * auxiliary fields have a fixed size (the inflated length of a record then follows from its head); everything else
-     * -- and --host-inflate / --host-decode -- is inflated by the host threads as before. */
-    P.aux_bytes = b5_aux_fixed_bytes(f);
-    P.zrec = !f->text && !host_inflate && !host_decode && (f->record_press == 1 || f->record_press == 2) && f->signal_press == 1 && P.aux_bytes >= 0;
+    /* Records go to the GPU as they sit in the file when they are zlib streams or zstd frames around an svb-zd signal and the
+     * header's type line names only types this reader knows, arrays included (the GPU then checks every record's auxiliary
+     * fields against that table, sgk_job_begin_zrec_aux); everything else -- and --host-inflate / --host-decode, and reads
+     * fetched by id from a file with array columns -- is inflated by the host threads as before. */
+    b5_aux_field_t *tab = NULL;
+    const int64_t n_tab = b5_aux_fields(f, &tab);
+    for (int64_t k = 0; k < n_tab; k++) {
+        if (tab[k].is_array) P.n_aux_arrays++;
+        else P.aux_fixed += tab[k].elem_bytes;
+    }
+    if (n_tab > 0) {
+        P.aux_tab = (sgk_aux_field_t *)malloc(sizeof(sgk_aux_field_t) * (size_t)n_tab);
+        if (!P.aux_tab) die_mem();
+        for (int64_t k = 0; k < n_tab; k++) {
+            P.aux_tab[k].elem_bytes = tab[k].elem_bytes;
+            P.aux_tab[k].is_array = tab[k].is_array;
+        }
+    }
+    free(tab);
+    P.n_aux = n_tab > 0 ? (uint32_t)n_tab : 0;
+    P.aux_slack = aux_slack;
+    P.zrec = !f->text && !host_inflate && !host_decode && (f->record_press == 1 || f->record_press == 2) && f->signal_press == 1 && n_tab >= 0 &&
+             (argc - optind - 1 == 0 || P.n_aux_arrays == 0);
     /* ... in batches of 128 M samples: the inflate kernel is a wavefront per record and takes ~35 ms however many records
      * it has (up to the ~4 800 the GPU holds at once), so a batch should bring a thousand of them (1e10 samples of `stat`:
      * 5.2 s with the 16 M-sample batches of the host path, 1.7 s with 128 M, profiles/r05_cli_steady.json) */
@@ -1334,7 +1420,9 @@ static int qtsmain(int argc, char *argv[]) {
 }
 
 /* hidden helper for tests: dump id, length, scaling and a checksum of every record.  `--split` goes
- * through the pipelined reader's split API (b5_next_raw + b5_parse_raw + b5_svb_zd_decode; with --id: b5_get_raw). */
+ * through the pipelined reader's split API (b5_next_raw + b5_parse_raw + b5_svb_zd_decode; with --id: b5_get_raw).
+ * `--aux` prints the table of the header's auxiliary columns instead (b5_aux_fields): one line, "#aux", the number of
+ * columns, then every column's element size with a '*' behind it for an array -- or "#aux\tnone" without a table. */
 static uint64_t fnv_i16(const int16_t *x, uint64_t n) {
     uint64_t h = 1469598103934665603ull;
     for (uint64_t i = 0; i < n; i++) {
@@ -1344,10 +1432,11 @@ static uint64_t fnv_i16(const int16_t *x, uint64_t n) {
     return h;
 }
 static int dumpmain(int argc, char *argv[]) {
-    int split = 0;
+    int split = 0, aux = 0;
     const char *path = NULL, *want_id = NULL;
     for (int i = 1; i < argc; i++) {
         if (strcmp(argv[i], "--split") == 0) split = 1;
+        else if (strcmp(argv[i], "--aux") == 0) aux = 1;
         else if (strcmp(argv[i], "--map") == 0) split = 2;  /* split API over the mapped file (b5_map / b5_next_ref) */
         else if (strcmp(argv[i], "--id") == 0 && i + 1 < argc) want_id = argv[++i]; /* one record through the index */
         else path = argv[i];
@@ -1359,6 +1448,19 @@ static int dumpmain(int argc, char *argv[]) {
         return 1;
     }
     int ret;
+    if (aux) {
+        b5_aux_field_t *tab = NULL;
+        const int64_t n = b5_aux_fields(f, &tab);
+        if (n < 0) printf("#aux\tnone\n");
+        else {
+            printf("#aux\t%ld", (long)n);
+            for (int64_t k = 0; k < n; k++) printf("\t%d%s", tab[k].elem_bytes, tab[k].is_array ? "*" : "");
+            printf("\n");
+        }
+        free(tab);
+        b5_close(f);
+        return 0;
+    }
     if (want_id && split) {
         /* the pipeline's read-id path: b5_get_raw (index + verification of the fetched record) + b5_parse_raw */
         uint8_t *raw = NULL, *scratch = NULL;

@@ -14,7 +14,9 @@ body it prints for the base file -- which is compared, byte for byte, with the r
 `--tools` takes any `;`-separated list of subtool command lines, `event` (long form) and `pa` included: their output is
 70 B per event / 10 B per sample, so size the file for the sink (e.g. `--tools "event;pa" --base-reads 1000 --copies 10`:
 1e9 samples, ~10 GB of pa text; the base file's whole output is held in memory once).  `--extra --gpu-text` runs the rows
-through the device-side writer; the JSON records it ("cli_extra", "gpu_text") and the text bytes the CLI reports."""
+through the device-side writer; the JSON records it ("cli_extra", "gpu_text") and the text bytes the CLI reports.
+`--aux` writes the base file with the six auxiliary columns of an ONT file (channel_number is a `char*`), as MinKNOW and
+`slow5tools f2s` do; the JSON then carries the CLI's own count of the records it decompressed on the GPU."""
 import argparse
 import hashlib
 import json
@@ -44,6 +46,16 @@ def replicate(base, big, copies):
     return os.path.getsize(big)
 
 
+# the auxiliary columns of a MinKNOW / slow5tools f2s file, in the order sp1_dna.blow5 has them
+ONT_AUX = [("start_time", "uint64_t"), ("read_number", "int32_t"), ("start_mux", "uint8_t"), ("median_before", "double"),
+           ("end_reason", "enum{unknown,partial,mux_change,unblock_mux_change,data_service_unblock_mux_change,signal_positive,signal_negative}"),
+           ("channel_number", "char*")]
+
+
+def ont_aux(i):
+    return (4000 * i, i, 1 + i % 4, 200.0 + (i % 97) * 0.25, i % 7, str(1 + i % 512))
+
+
 def stages(stderr):
     out = {}
     for ln in stderr.decode(errors="replace").splitlines():
@@ -56,6 +68,9 @@ def stages(stderr):
         m = re.match(r"\[sigtk-amd\] --gpu-text: (\d+) bytes of rows over PCIe", ln)
         if m:
             out["text_bytes_over_pcie"] = int(m.group(1))
+        m = re.match(r"\[sigtk-amd\] records decompressed on the GPU: (\d+) of (\d+); batches redone on the host: (\d+)", ln)
+        if m:
+            out["records_decompressed_on_gpu"], out["records"], out["batches_redone_on_host"] = (int(x) for x in m.groups())
     return out
 
 
@@ -70,20 +85,23 @@ def main():
     ap.add_argument("--tools", default="stat;jnn;prefix --print-stat;event -c")
     ap.add_argument("--runs", type=int, default=2)
     ap.add_argument("--extra", default="", help="extra CLI arguments, e.g. '--batch-samples 64000000'")
+    ap.add_argument("--aux", action="store_true", help="write the base file with ONT's six auxiliary columns")
     a = ap.parse_args()
-    base = os.path.join(a.dir, "steady_base_%d.blow5" % a.base_reads)
-    big = os.path.join(a.dir, "steady_big_%d_x%d.blow5" % (a.base_reads, a.copies))
+    tag = "aux_" if a.aux else ""
+    base = os.path.join(a.dir, "steady_%sbase_%d.blow5" % (tag, a.base_reads))
+    big = os.path.join(a.dir, "steady_%sbig_%d_x%d.blow5" % (tag, a.base_reads, a.copies))
     t0 = time.perf_counter()
     if not os.path.exists(base):
         reads, dig, off, rng = api.synth_reads_host(a.base_reads, a.read_len, 77, 0)
-        recs = [blow5.Read("synth-%08d" % i, 0, float(dig[i]), float(off[i]), float(rng[i]), 4000.0, reads[i])
-                for i in range(a.base_reads)]
-        blow5.write_blow5(base, recs, {"experiment_type": "genomic_dna", "sequencing_kit": "sqk-lsk109"})
+        recs = [blow5.Read("synth-%08d" % i, 0, float(dig[i]), float(off[i]), float(rng[i]), 4000.0, reads[i],
+                           aux=ont_aux(i) if a.aux else None) for i in range(a.base_reads)]
+        blow5.write_blow5(base, recs, {"experiment_type": "genomic_dna", "sequencing_kit": "sqk-lsk109"},
+                          aux_types=ONT_AUX if a.aux else None)
     if not os.path.exists(big):
         replicate(base, big, a.copies)
     out = {"base_file_mb": round(os.path.getsize(base) / 1e6, 1), "big_file_mb": round(os.path.getsize(big) / 1e6, 1),
            "copies": a.copies, "reads": a.base_reads * a.copies, "samples": a.base_reads * a.copies * a.read_len,
-           "host_cpus": os.cpu_count(), "made_in_s": round(time.perf_counter() - t0, 1), "cli_extra": a.extra,
+           "aux_columns": a.aux, "host_cpus": os.cpu_count(), "made_in_s": round(time.perf_counter() - t0, 1), "cli_extra": a.extra,
            "gpu_text": "--gpu-text" in a.extra.split(), "tools": {}}
     env = dict(os.environ, SGK_CLI_TIMING="1")
     targ = (["-t", str(a.threads)] if a.threads else []) + (["--gpus", str(a.gpus)] if a.gpus != 1 else []) + a.extra.split()
