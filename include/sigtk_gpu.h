@@ -73,7 +73,9 @@ extern "C" {
  * 0.2.3: SGK_JOB_EVENTS_LENGTHS (additive submit flag).  Additive to 0.2.3 (no version change): sgk_sigtext_decode;
  *        SGK_SIGNAL_TEXT for sgk_job_begin; sgk_ss_* (`ss paf2tsv`: decode, text, host pipe); sgk_zstd_decompress,
  *        SGK_RECORD_ZLIB / SGK_RECORD_ZSTD and sgk_job_begin_zrec_format (BLOW5 files with zstd records);
- *        sgk_aux_field_t, sgk_zrec_tail_check and sgk_job_begin_zrec_aux (records with variable-length auxiliary fields). */
+ *        sgk_aux_field_t, sgk_zrec_tail_check and sgk_job_begin_zrec_aux (records with variable-length auxiliary fields);
+ *        sgk_deflate, sgk_deflate_bound, sgk_deflate_block_bytes, sgk_job_set_record_frames and SGK_QTS_RECORDS with the
+ *        qts_record* fields at the end of sgk_job_output_t (`qts --gpu-deflate`: records deflated on the GPU). */
 #define SGK_VERSION_STRING "0.2.3"
 
 /* ---- error codes --------------------------------------------------------------- */
@@ -425,6 +427,23 @@ int sgk_inflate(const uint8_t *in, const uint64_t *in_offsets, const uint32_t *i
 int sgk_zstd_decompress(const uint8_t *in, const uint64_t *in_offsets, const uint32_t *in_lengths, uint32_t n, uint8_t *out,
                         const uint64_t *out_offsets, const uint32_t *out_caps, uint32_t *out_lengths, uint32_t *status,
                         void *stream);
+
+/* ---- zlib record deflate on the device (additive to 0.2.3) ---------------------------------------------------------- */
+/* The counterpart of sgk_inflate: n byte strings become n complete zlib streams (RFC 1950 / 1951: header 78 9C, DEFLATE
+ * blocks over sgk_deflate_block_bytes() input bytes each, big-endian Adler-32), one wavefront per stream.  The tokens are
+ * literals and matches of distance 1 (runs), every block dynamic-Huffman or stored, whichever is shorter -- what zlib's
+ * Z_RLE strategy writes, and all that svb-zd bytes reward.  tools/proto/deflate_proto.py writes the same bytes on the CPU.
+ * Buffers as sgk_inflate with the directions swapped, all device memory: stream r's in_lengths[r] bytes at
+ * in + in_offsets[r] (any alignment; 16-byte aligned reads faster); its zlib stream goes to out + out_offsets[r] (out and
+ * every out_offsets[r] 16-byte aligned), out_lengths[r] bytes.  Nothing is written at or behind out_caps[r]:
+ * status[r] is 1 for a stream that needs more (out_lengths[r] is then undefined), else 0.  sgk_deflate_bound(n) bytes
+ * are always enough for n input bytes.  Positions are 32-bit: SGK_ERR_ARG if an in_lengths[r] is 2^29 or more (nothing
+ * is written then; the call waits for the lengths to be looked at on `stream`). */
+uint32_t sgk_deflate_block_bytes(void);
+/* n + 5 * max(1, ceil(n / min(sgk_deflate_block_bytes(), 65535))) + 6: every block stored.  Host arithmetic, no GPU. */
+uint64_t sgk_deflate_bound(uint64_t n);
+int sgk_deflate(const uint8_t *in, const uint64_t *in_offsets, const uint32_t *in_lengths, uint32_t n, uint8_t *out,
+                const uint64_t *out_offsets, const uint32_t *out_caps, uint32_t *out_lengths, uint32_t *status, void *stream);
 
 /* ---- the auxiliary fields of an inflated BLOW5 record, checked on the device (additive to 0.2.3) ----------------------- */
 /* Behind its signal a record carries one field per auxiliary column of the file's header, in header order: a primitive
@@ -783,6 +802,13 @@ typedef struct sgk_job_output {
     const int16_t *qts_samples;
     const sgk_ent_hist_t *ent;            /* ent: one record per read */
     uint16_t *ent_over_raw, *ent_over_delta; /* ent: host copies of the overflow lists (NULL if all empty) */
+    /* qts with SGK_QTS_RECORDS: the rewritten records as zlib streams (record r at qts_records + qts_record_offsets[r],
+     * qts_record_lengths[r] bytes; qts_record_status[r]: sgk_deflate's status), else NULL.  The blobs / samples above
+     * are NULL then: the signal is not downloaded uncompressed */
+    const uint8_t *qts_records;
+    const uint64_t *qts_record_offsets;
+    const uint32_t *qts_record_lengths;
+    const uint32_t *qts_record_status;
 } sgk_job_output_t;
 
 int sgk_job_create(int device, sgk_job_t **out);
@@ -826,6 +852,16 @@ int sgk_job_submit(sgk_job_t *job, int tool, int rna, int pore, int flags);
 /* qts over the staged batch: quantise (bits in [1,15], method SGK_QTS_*), then hand the signal back as svb-zd blobs
  * (out_signal_format SGK_SIGNAL_SVBZD) or int16 samples (SGK_SIGNAL_INT16) */
 int sgk_job_submit_qts(sgk_job_t *job, int bits, int method, int out_signal_format);
+/* qts record mode (additive to 0.2.3).  Between sgk_job_begin* and sgk_job_submit_qts: what a BLOW5 record holds around
+ * its signal.  Frame r is bytes[frame_offsets[r] .. frame_offsets[r + 1]) (frame_offsets[0] = 0): first the record's
+ * head_lengths[r] bytes in front of len_raw_signal, then its bytes behind the signal (the auxiliary fields).  Copied into
+ * the job's pinned staging.  With SGK_QTS_RECORDS or'ed into out_signal_format, sgk_job_submit_qts then assembles
+ * head | u64 len_raw_signal | signal | tail for every read on the device (k_qts_assemble; len_raw_signal is the blob
+ * length for SGK_SIGNAL_SVBZD, the sample count for SGK_SIGNAL_INT16), deflates the records there (sgk_deflate) and
+ * downloads only the zlib streams: sgk_job_output_t::qts_records.  SGK_ERR_ARG without frames, or for text input. */
+#define SGK_QTS_RECORDS 0x100
+int sgk_job_set_record_frames(sgk_job_t *job, const uint8_t *bytes, const uint32_t *frame_offsets /* n + 1 */,
+                              const uint32_t *head_lengths /* n */);
 /* SGK_ERR_FORMAT if a blob (a text column) did not decode, SGK_ERR_CAPACITY on event-slot overflow */
 int sgk_job_wait(sgk_job_t *job);
 /* valid after sgk_job_wait until the job's next sgk_job_begin */

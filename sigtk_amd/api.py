@@ -176,7 +176,9 @@ class JobOutput(C.Structure):
                 ("stat", C.c_void_p), ("prefix", C.c_void_p), ("event_status", EventStatus),
                 ("qts_blobs", C.c_void_p), ("qts_blob_offsets", C.POINTER(C.c_uint64)),
                 ("qts_blob_lengths", C.POINTER(C.c_uint32)), ("qts_samples", C.c_void_p),
-                ("ent", C.c_void_p), ("ent_over_raw", C.c_void_p), ("ent_over_delta", C.c_void_p)]
+                ("ent", C.c_void_p), ("ent_over_raw", C.c_void_p), ("ent_over_delta", C.c_void_p),
+                ("qts_records", C.c_void_p), ("qts_record_offsets", C.POINTER(C.c_uint64)),
+                ("qts_record_lengths", C.POINTER(C.c_uint32)), ("qts_record_status", C.POINTER(C.c_uint32))]
 
 
 class TextIds(C.Structure):      # sgk_text_ids_t (device pointers)
@@ -253,6 +255,7 @@ def aux_table(fields):
         tab[k] = f if isinstance(f, AuxField) else AuxField(int(f[0]), int(bool(f[1])))
     return tab
 JOB_EVENTS_COMPACT = 1
+QTS_RECORDS = 0x100      # launch_qts(records=True): or'ed into the output signal format of sgk_job_submit_qts
 JOB_TEXT = 4             # pa / event: the rows are written on the device; wait() returns "text" and "row_offsets"
 TEXT_PA, TEXT_EVENT, TEXT_EVENT_COMPACT = 0, 1, 2
 JOB_EVENTS_LENGTHS = 2   # only the lengths come back; the starts are their running sums (events are contiguous from 0)
@@ -267,7 +270,7 @@ PREFIX_DTYPE = np.dtype([("adapt_x", "<i4"), ("adapt_y", "<i4"), ("polya_x", "<i
 #: every symbol include/sigtk_gpu.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "sgk_strerror", "sgk_version", "sgk_last_hip_error", "sgk_device_count", "sgk_set_device",
-    "sgk_pa", "sgk_event_workspace_bytes", "sgk_event", "sgk_event_pa", "sgk_event_status", "sgk_event_plan", "sgk_event_plan_opt", "sgk_job_long_declined", "sgk_inflate", "sgk_job_begin_zrec", "sgk_zstd_decompress", "sgk_job_begin_zrec_format", "sgk_zrec_tail_check", "sgk_job_begin_zrec_aux", "sgk_pipeline", "sgk_stat_lane_rules",
+    "sgk_pa", "sgk_event_workspace_bytes", "sgk_event", "sgk_event_pa", "sgk_event_status", "sgk_event_plan", "sgk_event_plan_opt", "sgk_job_long_declined", "sgk_inflate", "sgk_deflate", "sgk_deflate_bound", "sgk_deflate_block_bytes", "sgk_job_set_record_frames", "sgk_job_begin_zrec", "sgk_zstd_decompress", "sgk_job_begin_zrec_format", "sgk_zrec_tail_check", "sgk_job_begin_zrec_aux", "sgk_pipeline", "sgk_stat_lane_rules",
     "sgk_event_workspace_bytes_opt", "sgk_event_opt", "sgk_event_pa_opt", "sgk_event_host_opt",
     "sgk_stat_workspace_bytes", "sgk_stat", "sgk_stat_pa", "sgk_jnn_workspace_bytes", "sgk_jnn",
     "sgk_prefix_workspace_bytes", "sgk_prefix", "sgk_stat_opt", "sgk_stat_long_status", "sgk_stat_plan", "sgk_stat_pa_opt", "sgk_jnn_opt", "sgk_prefix_opt",
@@ -403,6 +406,14 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.sgk_stat_plan.argtypes = [C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, OS, C.POINTER(StatPlan)]
     L.sgk_pipeline.argtypes = [C.POINTER(Batch), C.c_int] + [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, OE, OS]
     L.sgk_inflate.argtypes = [C.c_void_p] * 3 + [C.c_uint32] + [C.c_void_p] * 6
+    L.sgk_deflate.argtypes = [C.c_void_p] * 3 + [C.c_uint32] + [C.c_void_p] * 6
+    L.sgk_deflate.restype = C.c_int
+    L.sgk_deflate_bound.argtypes = [C.c_uint64]
+    L.sgk_deflate_bound.restype = C.c_uint64
+    L.sgk_deflate_block_bytes.argtypes = []
+    L.sgk_deflate_block_bytes.restype = C.c_uint32
+    L.sgk_job_set_record_frames.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p]
+    L.sgk_job_set_record_frames.restype = C.c_int
     L.sgk_zstd_decompress.argtypes = [C.c_void_p] * 3 + [C.c_uint32] + [C.c_void_p] * 6
     L.sgk_svbzd_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p]
@@ -826,12 +837,26 @@ class Job:
         self._text = bool(flags & JOB_TEXT)
         check(self.L.sgk_job_submit(self.h, tool, rna, pore, flags), "sgk_job_submit")
 
-    def launch_qts(self, bits: int, method: int, out_svb: bool):
+    def set_record_frames(self, frames, head_lengths):
+        """sgk_job_set_record_frames: per read of the batch staged last, the record's bytes in front of len_raw_signal
+        (head_lengths[r] of them) followed by its bytes behind the signal"""
+        raw = [bytes(f) for f in frames]
+        offs = np.zeros(len(raw) + 1, dtype=np.uint32)
+        np.cumsum([len(f) for f in raw], out=offs[1:])
+        heads = np.ascontiguousarray(head_lengths, dtype=np.uint32)
+        blob = b"".join(raw)
+        check(self.L.sgk_job_set_record_frames(self.h, blob if blob else None, offs.ctypes.data,
+                                               heads.ctypes.data if len(raw) else None), "sgk_job_set_record_frames")
+
+    def launch_qts(self, bits: int, method: int, out_svb: bool, records: bool = False):
+        """records=True (after set_record_frames): the records are assembled and deflated on the GPU; wait() then
+        returns res["records"] (zlib streams) and res["record_status"] instead of the blobs / samples"""
         self._tool = TOOL_QTS
         self._text = False
         self._qts_svb = out_svb
-        check(self.L.sgk_job_submit_qts(self.h, bits, method, SIGNAL_SVBZD if out_svb else SIGNAL_INT16),
-              "sgk_job_submit_qts")
+        self._qts_records = records
+        check(self.L.sgk_job_submit_qts(self.h, bits, method, (SIGNAL_SVBZD if out_svb else SIGNAL_INT16) |
+                                        (QTS_RECORDS if records else 0)), "sgk_job_submit_qts")
 
     def submit(self, tool: int, signals, dig, off, rng, rna: int = 0, pore: int = 0, flags: int = 0, counts=None, ids=None,
                text=False):
@@ -889,7 +914,11 @@ class Job:
         elif self._tool == TOOL_PREFIX:
             res["prefix"] = np.frombuffer(C.string_at(o.prefix, n * PREFIX_DTYPE.itemsize), dtype=PREFIX_DTYPE).copy()
         elif self._tool == TOOL_QTS:
-            if self._qts_svb:
+            if getattr(self, "_qts_records", False):
+                res["records"] = [C.string_at(o.qts_records + int(o.qts_record_offsets[r]), int(o.qts_record_lengths[r]))
+                                  for r in range(n)]
+                res["record_status"] = _np_from(o.qts_record_status, n, np.uint32).copy() if n else np.zeros(0, np.uint32)
+            elif self._qts_svb:
                 res["blobs"] = [C.string_at(o.qts_blobs + int(o.qts_blob_offsets[r]), int(o.qts_blob_lengths[r]))
                                 for r in range(n)]
             else:

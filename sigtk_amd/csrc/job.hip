@@ -29,6 +29,18 @@ int zrec_tail_check(const uint8_t *inflated, const uint64_t *rec_offsets, const 
                     const uint32_t *tail_offsets, const uint32_t *gate, uint32_t n, const sgk_aux_field_t *fields,
                     uint32_t n_fields, uint32_t *status, hipStream_t st);   // zrec_kernels.hip
 
+// qts record mode, deflate_kernels.hip
+int launch_qts_record_sizes(const uint32_t *frame_offsets, const uint32_t *sig_counts, uint32_t sig_unit, uint32_t n,
+                            uint32_t *rec_lengths, uint32_t *caps, hipStream_t st);
+int launch_qts_assemble(const uint8_t *frames, const uint32_t *frame_offsets, const uint32_t *head_lengths, const uint8_t *signal,
+                        const uint64_t *sig_offsets, const uint32_t *sig_counts, uint32_t sig_unit, uint8_t *arena,
+                        const uint64_t *rec_offsets, uint32_t n, hipStream_t st);
+int launch_bytes_gather(const uint8_t *src, const uint64_t *src_offsets, const uint32_t *lengths, uint32_t n, uint8_t *dst,
+                        const uint64_t *dst_offsets, hipStream_t st);
+int launch_deflate_unchecked(const uint8_t *in, const uint64_t *in_offsets, const uint32_t *in_lengths, uint32_t n, uint8_t *out,
+                             const uint64_t *out_offsets, const uint32_t *out_caps, uint32_t *out_lengths, uint32_t *status,
+                             hipStream_t st);
+
 struct GrowDev {
     void *p = nullptr;
     size_t cap = 0;
@@ -112,6 +124,12 @@ struct sgk_job {
     GrowPin h_idb, h_ido, h_roffs, h_text;
     GrowDev d_idb, d_ido, d_roffs, d_text, d_tws;
     bool have_ids = false;
+    // qts record mode (sgk_job_set_record_frames + SGK_QTS_RECORDS): the frames; the assembled records (d_rec*), their
+    // zlib streams where k_deflate writes them (d_z*: worst-case room each) and gathered densely for the download
+    GrowPin h_frb, h_fro, h_frh, h_zlen, h_zstat, h_zdoffs, h_zdense;
+    GrowDev d_frb, d_fro, d_frh, d_reclen, d_recoffs, d_rec, d_zcap, d_zoffs, d_z, d_zlen, d_zstat, d_zdoffs, d_zdense;
+    bool have_frames = false;
+    size_t frame_bytes = 0;
     bool text_written = false;        // the write pass was enqueued at submit, into the buffer earlier batches grew
     int text_kind = 0;
     size_t tws_bytes = 0, id_bytes = 0;
@@ -316,7 +334,28 @@ static int job_begin(sgk_job_t *j, uint32_t n_reads, const uint32_t *lengths, in
     in->n_samples = j->n_samples;
     j->begun = true;
     j->have_ids = false;
+    j->have_frames = false;
     j->text_bytes = 0;
+    return SGK_OK;
+}
+
+int sgk_job_set_record_frames(sgk_job_t *j, const uint8_t *bytes, const uint32_t *frame_offsets, const uint32_t *head_lengths) {
+    if (!j || !j->begun || j->submitted || !frame_offsets || frame_offsets[0] != 0) return SGK_ERR_ARG;
+    const size_t nr = j->n_reads;
+    if (nr && !head_lengths) return SGK_ERR_ARG;
+    for (size_t r = 0; r < nr; ++r)
+        if (frame_offsets[r + 1] < frame_offsets[r] || head_lengths[r] > frame_offsets[r + 1] - frame_offsets[r]) return SGK_ERR_ARG;
+    if (frame_offsets[nr] && !bytes) return SGK_ERR_ARG;
+    SGK_HIP_TRY(hipSetDevice(j->device));
+    int rc;
+    if ((rc = j->h_fro.ensure((nr + 1) * 4)) != SGK_OK) return rc;
+    if ((rc = j->h_frh.ensure((nr ? nr : 1) * 4)) != SGK_OK) return rc;
+    if ((rc = j->h_frb.ensure((size_t)frame_offsets[nr] + 16)) != SGK_OK) return rc;
+    memcpy(j->h_fro.p, frame_offsets, (nr + 1) * 4);
+    if (nr) memcpy(j->h_frh.p, head_lengths, nr * 4);
+    if (frame_offsets[nr]) memcpy(j->h_frb.p, bytes, frame_offsets[nr]);
+    j->frame_bytes = frame_offsets[nr];
+    j->have_frames = true;
     return SGK_OK;
 }
 
@@ -691,14 +730,75 @@ int sgk_job_submit(sgk_job_t *j, int tool, int rna, int pore, int flags) {
     return SGK_OK;
 }
 
-int sgk_job_submit_qts(sgk_job_t *j, int bits, int method, int out_fmt) {
+// qts record mode: the records assembled around the quantised signal (blobs at d_out[0] / d_out[1] / d_cnt, or the
+// samples), deflated, gathered densely; lengths, statuses and dense offsets on their way home -- the streams themselves
+// follow in sgk_job_wait once their total is known
+static int job_qts_records(sgk_job_t *j, const sgk_batch_t &view, bool svb) {
+    const size_t nr = j->n_reads;
+    hipStream_t st = j->st;
+    int rc;
+    const uint32_t *lens = j->h_lengths.as<uint32_t>();
+    const uint32_t *fro = j->h_fro.as<uint32_t>();
+    size_t rec_bound = 0, z_bound = 0;
+    for (size_t r = 0; r < nr; ++r) {
+        const size_t sig = svb ? 4 + ((size_t)lens[r] + 3) / 4 + 3 * (size_t)lens[r] : 2 * (size_t)lens[r];
+        const size_t rec = (size_t)(fro[r + 1] - fro[r]) + 8 + sig;
+        if (rec >= ((size_t)1 << 29)) return SGK_ERR_ARG;   // (sgk_deflate's limit)
+        rec_bound += round_up(rec, 16);
+        z_bound += round_up(sgk_deflate_bound(rec), 16);
+    }
+    if ((rc = h2d(j->d_frb, j->h_frb, j->frame_bytes, st)) != SGK_OK) return rc;
+    if ((rc = h2d(j->d_fro, j->h_fro, (nr + 1) * 4, st)) != SGK_OK) return rc;
+    if ((rc = h2d(j->d_frh, j->h_frh, nr * 4, st)) != SGK_OK) return rc;
+    if ((rc = j->d_reclen.ensure(nr * 4)) != SGK_OK) return rc;
+    if ((rc = j->d_zcap.ensure(nr * 4)) != SGK_OK) return rc;
+    if ((rc = j->d_zlen.ensure(nr * 4)) != SGK_OK) return rc;
+    if ((rc = j->d_zstat.ensure(nr * 4)) != SGK_OK) return rc;
+    if ((rc = j->d_recoffs.ensure((nr + 1) * 8)) != SGK_OK) return rc;
+    if ((rc = j->d_zoffs.ensure((nr + 1) * 8)) != SGK_OK) return rc;
+    if ((rc = j->d_zdoffs.ensure((nr + 1) * 8)) != SGK_OK) return rc;
+    if ((rc = j->d_rec.ensure(rec_bound + 16)) != SGK_OK) return rc;
+    if ((rc = j->d_z.ensure(z_bound + 16)) != SGK_OK) return rc;
+    if ((rc = j->d_zdense.ensure(z_bound + 16)) != SGK_OK) return rc;
+    const uint32_t *counts = svb ? j->d_cnt.as<uint32_t>() : view.lengths;
+    const uint64_t *sig_offs = svb ? j->d_out[1].as<uint64_t>() : view.offsets;
+    const uint8_t *signal = svb ? j->d_out[0].as<uint8_t>() : reinterpret_cast<const uint8_t *>(view.samples);
+    const uint32_t unit = svb ? 1u : 2u;
+    if ((rc = launch_qts_record_sizes(j->d_fro.as<uint32_t>(), counts, unit, j->n_reads, j->d_reclen.as<uint32_t>(),
+                                      j->d_zcap.as<uint32_t>(), st)) != SGK_OK) return rc;
+    SGK_LAUNCH_UNTIMED(k_layout, 1, 1024, st, j->d_reclen.as<uint32_t>(), static_cast<const uint64_t *>(nullptr), j->n_reads,
+                       16u, j->d_recoffs.as<uint64_t>());
+    SGK_LAUNCH_UNTIMED(k_layout, 1, 1024, st, j->d_zcap.as<uint32_t>(), static_cast<const uint64_t *>(nullptr), j->n_reads,
+                       16u, j->d_zoffs.as<uint64_t>());
+    if ((rc = launch_qts_assemble(j->d_frb.as<uint8_t>(), j->d_fro.as<uint32_t>(), j->d_frh.as<uint32_t>(), signal, sig_offs,
+                                  counts, unit, j->d_rec.as<uint8_t>(), j->d_recoffs.as<uint64_t>(), j->n_reads, st)) != SGK_OK)
+        return rc;
+    if ((rc = launch_deflate_unchecked(j->d_rec.as<uint8_t>(), j->d_recoffs.as<uint64_t>(), j->d_reclen.as<uint32_t>(), j->n_reads,
+                                       j->d_z.as<uint8_t>(), j->d_zoffs.as<uint64_t>(), j->d_zcap.as<uint32_t>(),
+                                       j->d_zlen.as<uint32_t>(), j->d_zstat.as<uint32_t>(), st)) != SGK_OK)
+        return rc;
+    SGK_LAUNCH_UNTIMED(k_layout, 1, 1024, st, j->d_zlen.as<uint32_t>(), static_cast<const uint64_t *>(nullptr), j->n_reads,
+                       16u, j->d_zdoffs.as<uint64_t>());
+    if ((rc = launch_bytes_gather(j->d_z.as<uint8_t>(), j->d_zoffs.as<uint64_t>(), j->d_zlen.as<uint32_t>(), j->n_reads,
+                                  j->d_zdense.as<uint8_t>(), j->d_zdoffs.as<uint64_t>(), st)) != SGK_OK)
+        return rc;
+    if ((rc = d2h(j->h_zlen, j->d_zlen, nr * 4, st)) != SGK_OK) return rc;
+    if ((rc = d2h(j->h_zstat, j->d_zstat, nr * 4, st)) != SGK_OK) return rc;
+    if ((rc = d2h(j->h_zdoffs, j->d_zdoffs, (nr + 1) * 8, st)) != SGK_OK) return rc;
+    return SGK_OK;
+}
+
+int sgk_job_submit_qts(sgk_job_t *j, int bits, int method, int out_fmt_flags) {
     if (!j || !j->begun || j->submitted) return SGK_ERR_ARG;
+    const bool records = (out_fmt_flags & SGK_QTS_RECORDS) != 0;
+    const int out_fmt = out_fmt_flags & ~SGK_QTS_RECORDS;
     if (out_fmt != SGK_SIGNAL_INT16 && out_fmt != SGK_SIGNAL_SVBZD) return SGK_ERR_ARG;
     if (j->fmt == SGK_SIGNAL_TEXT) return SGK_ERR_ARG;  // rewriting text records is not part of qts here
+    if (records && !j->have_frames) return SGK_ERR_ARG;
     if (bits < 1 || bits > 15 || method < SGK_QTS_FLOOR || method > SGK_QTS_FILL_ONES) return SGK_ERR_ARG;
     SGK_HIP_TRY(hipSetDevice(j->device));
     j->tool = SGK_TOOL_QTS;
-    j->flags = out_fmt;
+    j->flags = out_fmt_flags;
     const size_t nr = j->n_reads;
     hipStream_t st = j->st;
     int rc;
@@ -711,7 +811,9 @@ int sgk_job_submit_qts(sgk_job_t *j, int bits, int method, int out_fmt) {
     int16_t *smp = j->d_samples.as<int16_t>();
     if ((rc = sgk_qts(smp, view.offsets, view.lengths, j->n_reads, j->max_len, bits, method, st)) != SGK_OK) return rc;
     if (out_fmt == SGK_SIGNAL_INT16) {
-        if ((rc = d2h(j->h_out[0], j->d_samples, j->n_samples * sizeof(int16_t), st)) != SGK_OK) return rc;
+        if (records) {
+            if ((rc = job_qts_records(j, view, false)) != SGK_OK) return rc;
+        } else if ((rc = d2h(j->h_out[0], j->d_samples, j->n_samples * sizeof(int16_t), st)) != SGK_OK) return rc;
     } else {
         // d_out[0] blobs (worst-case sized), d_out[1] blob offsets, d_out[2] total, d_cnt blob lengths
         const uint32_t *lens = j->h_lengths.as<uint32_t>();
@@ -726,9 +828,13 @@ int sgk_job_submit_qts(sgk_job_t *j, int bits, int method, int out_fmt) {
         rc = sgk_svbzd_encode(smp, view.offsets, view.lengths, j->n_reads, j->d_out[0].as<uint8_t>(),
                               j->d_out[1].as<uint64_t>(), j->d_cnt.as<uint32_t>(), st);
         if (rc != SGK_OK) return rc;
-        if ((rc = d2h(j->h_cnt, j->d_cnt, nr * 4, st)) != SGK_OK) return rc;
-        if ((rc = d2h(j->h_out[1], j->d_out[1], (nr + 1) * 8, st)) != SGK_OK) return rc;
-        // the blobs themselves are fetched by sgk_job_wait once their total size is known
+        if (records) {
+            if ((rc = job_qts_records(j, view, true)) != SGK_OK) return rc;
+        } else {
+            if ((rc = d2h(j->h_cnt, j->d_cnt, nr * 4, st)) != SGK_OK) return rc;
+            if ((rc = d2h(j->h_out[1], j->d_out[1], (nr + 1) * 8, st)) != SGK_OK) return rc;
+            // the blobs themselves are fetched by sgk_job_wait once their total size is known
+        }
     }
     j->submitted = true;
     return SGK_OK;
@@ -788,6 +894,12 @@ int sgk_job_wait(sgk_job_t *j) {
         const uint64_t total = j->h_out[1].as<uint64_t>()[j->n_reads];
         int rc;
         if ((rc = d2h(j->h_out[0], j->d_out[0], (size_t)total, j->st)) != SGK_OK) return rc;
+        SGK_HIP_TRY(hipStreamSynchronize(j->st));
+    }
+    if (j->tool == SGK_TOOL_QTS && (j->flags & SGK_QTS_RECORDS)) {
+        const uint64_t total = j->h_zdoffs.as<uint64_t>()[j->n_reads];
+        int rc;
+        if ((rc = d2h(j->h_zdense, j->d_zdense, (size_t)total, j->st)) != SGK_OK) return rc;
         SGK_HIP_TRY(hipStreamSynchronize(j->st));
     }
     if (j->tool == SGK_TOOL_ENT) {
@@ -860,7 +972,12 @@ int sgk_job_output(const sgk_job_t *j, sgk_job_output_t *out) {
             out->prefix = j->h_out[0].as<sgk_prefix_rec_t>();
             break;
         case SGK_TOOL_QTS:
-            if (j->flags == SGK_SIGNAL_SVBZD) {
+            if (j->flags & SGK_QTS_RECORDS) {
+                out->qts_records = j->h_zdense.as<uint8_t>();
+                out->qts_record_offsets = j->h_zdoffs.as<uint64_t>();
+                out->qts_record_lengths = j->h_zlen.as<uint32_t>();
+                out->qts_record_status = j->h_zstat.as<uint32_t>();
+            } else if (j->flags == SGK_SIGNAL_SVBZD) {
                 out->qts_blobs = j->h_out[0].as<uint8_t>();
                 out->qts_blob_offsets = j->h_out[1].as<uint64_t>();
                 out->qts_blob_lengths = j->h_cnt.as<uint32_t>();

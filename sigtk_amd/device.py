@@ -399,6 +399,58 @@ def inflate(streams, caps=None, device: Optional[torch.device] = None, with_gaps
     return kept, olen, st
 
 
+def deflate_bound(n: int) -> int:
+    """sgk_deflate_bound: bytes that always hold the zlib stream sgk_deflate writes for n input bytes (no GPU needed)"""
+    return int(api.load_library().sgk_deflate_bound(int(n)))
+
+
+def deflate(streams, caps=None, device: Optional[torch.device] = None, with_gaps: bool = False, fill: int = 0):
+    """sgk_deflate over a list of byte strings -> (list of zlib streams as written: out_lengths[r] bytes each, none for a
+    stream with a non-zero status, out_lengths, status) -- the device-side replacement of compress2().  caps[r]: room
+    for stream r (default: deflate_bound); the output buffer is pre-filled with `fill`.  with_gaps: a fourth result, per
+    stream the bytes of the output buffer from out_lengths[r] (0 for a failed stream) up to the next stream's 16-byte
+    aligned area, which the stream must have left alone, a fifth: the byte offset of caps[r] in that gap"""
+    L = api.load_library()
+    dev = device or torch.device("cuda", 0)
+    n = len(streams)
+    in_len = np.asarray([len(s) for s in streams], dtype=np.uint32)
+    in_off = np.zeros(n, dtype=np.uint64)
+    if n > 1:
+        in_off[1:] = np.cumsum((in_len[:-1].astype(np.uint64) + 15) // 16 * 16)
+    pos = int(in_off[-1]) + int(in_len[-1]) if n else 0
+    blob = np.zeros((pos + 19) // 16 * 16, dtype=np.uint8)
+    for r, s in enumerate(streams):
+        blob[int(in_off[r]):int(in_off[r]) + len(s)] = np.frombuffer(bytes(s), dtype=np.uint8)
+    caps_a = np.asarray(caps if caps is not None else [deflate_bound(len(s)) for s in streams], dtype=np.uint32)
+    gap = 48 if with_gaps else 0   # (room that belongs to no stream)
+    out_off = np.zeros(n, dtype=np.uint64)
+    if n > 1:
+        out_off[1:] = np.cumsum((caps_a[:-1].astype(np.uint64) + 15) // 16 * 16 + gap)
+    total = int(out_off[-1] + (int(caps_a[-1]) + 15) // 16 * 16 + gap) if n else 16
+    d_in = torch.from_numpy(blob).to(dev)
+    d_ioff = torch.from_numpy(in_off.view(np.int64)).to(dev)
+    d_ilen = torch.from_numpy(in_len.view(np.int32)).to(dev)
+    d_out = torch.full((max(total, 16),), fill, dtype=torch.uint8, device=dev)
+    assert _ptr(d_out) % 16 == 0
+    d_ooff = torch.from_numpy(out_off.view(np.int64)).to(dev)
+    d_caps = torch.from_numpy(caps_a.view(np.int32)).to(dev)
+    d_olen = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    d_st = torch.full((max(n, 1),), -1, dtype=torch.int32, device=dev)
+    api.check(L.sgk_deflate(_ptr(d_in), _ptr(d_ioff), _ptr(d_ilen), n, _ptr(d_out), _ptr(d_ooff), _ptr(d_caps), _ptr(d_olen),
+                            _ptr(d_st), _stream_ptr()), "sgk_deflate")
+    torch.cuda.synchronize()
+    out = d_out.cpu().numpy()
+    st = d_st.cpu().numpy()[:n]
+    olen = d_olen.cpu().numpy().view(np.uint32)[:n].copy()
+    kept = [out[int(out_off[r]):int(out_off[r]) + int(olen[r])].tobytes() if st[r] == 0 else None for r in range(n)]
+    if with_gaps:
+        ends = [int(out_off[r + 1]) if r + 1 < n else total for r in range(n)]
+        used = [int(olen[r]) if st[r] == 0 else 0 for r in range(n)]
+        return (kept, olen, st, [out[int(out_off[r]) + used[r]:ends[r]].tobytes() for r in range(n)],
+                [int(caps_a[r]) - used[r] for r in range(n)])
+    return kept, olen, st
+
+
 def zstd_decompress(frames, caps=None, device: Optional[torch.device] = None, with_gaps: bool = False, leads=None,
                     fill: int = 0, guard: int = 0):
     """sgk_zstd_decompress over a list of zstd frames (bytes) -> (list of decoded bytes as kept, out_lengths, status) --

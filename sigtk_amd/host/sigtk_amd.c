@@ -323,6 +323,9 @@ typedef struct batch {
     uint8_t *id_blob;   /* --gpu-text: the batch's read ids back to back, id r at id_offs[r] .. id_offs[r + 1] */
     uint32_t *id_offs;
     uint64_t id_blob_cap, id_offs_cap;
+    uint8_t *fr_blob;   /* qts --gpu-deflate: per record its bytes in front of len_raw_signal, then those behind the signal */
+    uint32_t *fr_offs, *fr_heads;   /* frame r at fr_offs[r] .. fr_offs[r + 1], its first fr_heads[r] bytes the head */
+    uint64_t fr_blob_cap, fr_offs_cap;
     struct batch *next;
 } batch_t;
 
@@ -387,6 +390,7 @@ typedef struct {
     int n_ids;
     /* qts */
     int q_bits, q_method;
+    int gpu_deflate;  /* qts --gpu-deflate on a file with compressed records: records assembled and deflated on the GPU */
     FILE *out_fp;    /* rows / records go here (stdout except for qts) */
     pool_t *load_pool; /* the loader's worker pool (the writer creates its own) */
     struct batch *pool; /* all batch slots; [0, n_created) have a job */
@@ -470,6 +474,40 @@ static void load_stage(void *ctx_, uint32_t i, int tid) {
     } else {
         memcpy(b->in.samples + b->in.offsets[i], r->v.signal, r->v.signal_bytes);
     }
+    if (c->P->gpu_deflate) {   /* the record around its signal (batch_frames laid the frames out) */
+        const uint8_t *tail = r->v.signal + r->v.signal_bytes;
+        uint8_t *fr = b->fr_blob + b->fr_offs[i];
+        memcpy(fr, r->v.rec, b->fr_heads[i]);
+        memcpy(fr + b->fr_heads[i], tail, (size_t)(r->v.rec + r->v.rec_len - tail));
+    }
+}
+
+/* qts --gpu-deflate: where every record's frame goes (load_stage fills them) */
+static void batch_frames(batch_t *b) {
+    if ((uint64_t)b->n + 1 > b->fr_offs_cap) {
+        b->fr_offs_cap = (uint64_t)b->n + 1;
+        b->fr_offs = (uint32_t *)realloc(b->fr_offs, sizeof(uint32_t) * b->fr_offs_cap);
+        b->fr_heads = (uint32_t *)realloc(b->fr_heads, sizeof(uint32_t) * b->fr_offs_cap);
+        if (!b->fr_offs || !b->fr_heads) die_mem();
+    }
+    uint64_t o = 0;
+    for (uint32_t i = 0; i < b->n; i++) {
+        const b5_view_t *v = &b->recs[i].v;
+        const uint64_t head = (uint64_t)(v->signal - v->rec) - 8; /* up to the u64 len_raw_signal */
+        b->fr_offs[i] = (uint32_t)o;
+        b->fr_heads[i] = (uint32_t)head;
+        o += head + (uint64_t)(v->rec + v->rec_len - (v->signal + v->signal_bytes));
+        if (o > 0xffffffffull) {
+            ERROR("qts", "%s", "the records of one batch hold more than 4 GB around their signals: use a smaller --batch-samples");
+            die_now();
+        }
+    }
+    b->fr_offs[b->n] = (uint32_t)o;
+    if (o + 1 > b->fr_blob_cap) {
+        b->fr_blob_cap = o + o / 8 + 64;
+        b->fr_blob = (uint8_t *)realloc(b->fr_blob, b->fr_blob_cap);
+        if (!b->fr_blob) die_mem();
+    }
 }
 
 /* --gpu-text: the ids travel with the batch; the job hands back the rows as the reference prints them */
@@ -515,9 +553,12 @@ static void batch_submit(pipe_t *P, batch_t *b) {
         batch_set_ids(b);
         flags |= SGK_JOB_TEXT;
     }
-    if (P->mode == MODE_QTS)
-        rc = sgk_job_submit_qts(b->job, P->q_bits, P->q_method, P->f->signal_press == 1 ? SGK_SIGNAL_SVBZD : SGK_SIGNAL_INT16);
-    else
+    if (P->mode == MODE_QTS) {
+        if (P->gpu_deflate && (rc = sgk_job_set_record_frames(b->job, b->fr_blob, b->fr_offs, b->fr_heads)) != SGK_OK)
+            gpu_fail("sgk_job_set_record_frames", rc);
+        rc = sgk_job_submit_qts(b->job, P->q_bits, P->q_method,
+                                (P->f->signal_press == 1 ? SGK_SIGNAL_SVBZD : SGK_SIGNAL_INT16) | (P->gpu_deflate ? SGK_QTS_RECORDS : 0));
+    } else
         rc = sgk_job_submit(b->job, tool, P->opt.rna, P->opt.pore, flags);
     if (rc != SGK_OK) gpu_fail("sgk_job_submit", rc);
 }
@@ -555,6 +596,7 @@ static void batch_launch(pipe_t *P, batch_t *b) {
     if (b->zrec) rc = sgk_job_begin_zrec_aux(b->job, b->n, P->f->record_press == 2 ? SGK_RECORD_ZSTD : SGK_RECORD_ZLIB, b->lengths, b->blob_bytes, b->sig_off, b->sig_len, b->room, P->aux_tab, P->n_aux, &b->in);
     else rc = sgk_job_begin(b->job, b->n, b->lengths, b->sigtext ? SGK_SIGNAL_TEXT : (b->svb ? SGK_SIGNAL_SVBZD : SGK_SIGNAL_INT16), b->blob_bytes, &b->in);
     if (rc != SGK_OK) gpu_fail("sgk_job_begin", rc);
+    if (P->gpu_deflate) batch_frames(b);
     pfor(P->load_pool, b->n, load_stage, &c);
     for (uint32_t i = 0; i < b->n; i++) {
         if (b->recs[i].err) {
@@ -744,7 +786,19 @@ static void row_ent(sbuf_t *o, const batch_t *b, const sgk_job_output_t *out, ui
  * slow5lib/src/slow5.c:421-423; qtsmain sets the header byte). */
 static __thread uint8_t *qts_tmp;
 static __thread size_t qts_tmp_cap;
-static void row_qts(sbuf_t *o, const batch_t *b, const sgk_job_output_t *out, uint32_t r, const b5_file_t *f) {
+static void row_qts(sbuf_t *o, const batch_t *b, const sgk_job_output_t *out, uint32_t r, const b5_file_t *f, int gpu_deflate) {
+    if (gpu_deflate) {   /* --gpu-deflate: the record came back as the zlib stream the GPU wrote around the new signal */
+        if (out->qts_record_status[r] != 0) {
+            fprintf(stderr, "Error writing record!\n");
+            die_now();
+        }
+        const uint64_t z64 = out->qts_record_lengths[r];
+        char *p = sbuf_room(o, 8 + (size_t)z64);
+        memcpy(p, &z64, 8);
+        memcpy(p + 8, out->qts_records + out->qts_record_offsets[r], (size_t)z64);
+        o->n += 8 + (size_t)z64;
+        return;
+    }
     const b5_view_t *v = &b->recs[r].v;
     const size_t head = (size_t)(v->signal - v->rec) - 8; /* up to the u64 len_raw_signal */
     const uint8_t *tail = v->signal + v->signal_bytes;
@@ -841,7 +895,7 @@ static void write_chunk(void *ctx_, uint32_t k, int tid) {
             case MODE_STAT: row_stat(o, c->b, &c->out, r); break;
             case MODE_PREFIX: row_prefix(o, c->b, &c->out, r, opt); break;
             case MODE_ENT: row_ent(o, c->b, &c->out, r); break;
-            case MODE_QTS: row_qts(o, c->b, &c->out, r, c->P->f); break;
+            case MODE_QTS: row_qts(o, c->b, &c->out, r, c->P->f, c->P->gpu_deflate); break;
             default: row_pa(o, c->b, &c->out, r); break;
         }
     }
@@ -1076,6 +1130,7 @@ static void run_pipeline(pipe_t *P, int n_gpus, double t_init) {
             for (uint32_t k = 0; k < pool[i].cap; k++) free(pool[i].recs[k].scratch);
             free(pool[i].recs); free(pool[i].raw); free(pool[i].lengths); free(pool[i].blob_bytes); free(pool[i].sig_off); free(pool[i].sig_len); free(pool[i].room);
             free(pool[i].id_blob); free(pool[i].id_offs);
+            free(pool[i].fr_blob); free(pool[i].fr_offs); free(pool[i].fr_heads);
         }
         free(pool);
     }
@@ -1294,12 +1349,14 @@ static int cmain(int argc, char *argv[], const char *mode_s) {
  * Same options as the reference (-o FILE, -b INT in [1,8], -m floor|round|fill-ones).  The output keeps the
  * input's header block and compression settings verbatim (the reference re-serialises the header through slow5lib
  * and always writes zlib + svb-zd); records carry the same fields, auxiliary data included, with the quantised
- * signal -- quantised and re-encoded (svb-zd) on the GPU, deflated on the host thread pool. */
+ * signal -- quantised and re-encoded (svb-zd) on the GPU, deflated on the host thread pool, or with --gpu-deflate
+ * assembled and deflated on the GPU as well (Z_RLE-like streams of csrc/deflate_kernels.hip: other bytes, same records). */
 static struct option qts_long_options[] = {
     {"verbose", required_argument, 0, 'v'}, {"help", no_argument, 0, 'h'},   {"version", no_argument, 0, 'V'},
     {"output", required_argument, 0, 'o'},  {"bits", required_argument, 0, 'b'}, {"method", required_argument, 0, 'm'},
     {"gpus", required_argument, 0, 0},      {"batch-samples", required_argument, 0, 0}, {"threads", required_argument, 0, 't'},
     {"gpu-text", no_argument, 0, 0}, /* accepted, changes nothing: qts writes records, not rows */
+    {"gpu-deflate", no_argument, 0, 0}, /* records assembled and deflated on the GPU (k_qts_assemble, k_deflate) */
     {0, 0, 0, 0}};
 
 static int qtsmain(int argc, char *argv[]) {
@@ -1307,7 +1364,7 @@ static int qtsmain(int argc, char *argv[]) {
     int longindex = 0, c;
     FILE *fp_help = stderr;
     char *out_fn = NULL;
-    int b = 1, n_gpus = 1, nthreads = 0;
+    int b = 1, n_gpus = 1, nthreads = 0, gpu_deflate = 0;
     const char *method = "round";
     uint64_t batch_samples = 16ull << 20; /* small batches: the buffers of a job are cheap to set up, the host stages overlap sooner */
     while ((c = getopt_long(argc, argv, optstring, qts_long_options, &longindex)) >= 0) {
@@ -1332,6 +1389,8 @@ static int qtsmain(int argc, char *argv[]) {
             n_gpus = atoi(optarg);
         } else if (c == 0 && longindex == 7) {
             batch_samples = strtoull(optarg, NULL, 10);
+        } else if (c == 0 && longindex == 10) {
+            gpu_deflate = 1;
         }
     }
     if (argc - optind != 1 || fp_help == stdout) {
@@ -1408,6 +1467,7 @@ static int qtsmain(int argc, char *argv[]) {
     P.nthreads = nthreads;
     P.q_bits = b;
     P.q_method = q_method;
+    P.gpu_deflate = gpu_deflate && f->record_press != 0;   /* (uncompressed records: nothing to deflate, the flag changes nothing) */
     P.out_fp = out;
     P.limit_bytes = batch_samples;
     run_pipeline(&P, n_gpus, t_init);
