@@ -48,3 +48,22 @@ def test_chunked_detector_equals_the_sequential_one(oracle, sp1, rna, seg_len, l
         assert stats.get("rerun", 0) > 0          # short warm-ups: speculation does fail, and is repaired
     if lead == 0 and seg_len < 10000:
         assert stats.get("seam_rerun", 0) > 0     # no warm-up at all: the seams fail as well, spans are run again in order
+
+
+@pytest.mark.parametrize("seg_len,lanes,lead", [(1 << 30, 64, 32), (1024, 8, 16), (2048, 64, 0)])
+def test_chunked_detector_on_the_event_catalogue(oracle, seg_len, lanes, lead):
+    """the same scheme over the statistics of the hand-made reads of tests/event_cases.py (up to 7 000 samples each), on
+    which -- unlike on anything above -- the long detector emits boundaries: next to chunk ends, at seams, in runs that
+    cross them"""
+    import event_cases
+    n_long = 0
+    for k in event_cases.catalogue():
+        if k.raw.size > 7000 or k.raw.size == 0:      # (the prototype lays its chunks over at least one sample)
+            continue
+        for label, rna in event_cases.case_runs(k):
+            t1, t2 = _tstats(oracle, k.raw, *event_cases.SCALE, rna)
+            exp = sorted(int(p) for p in oracle.peaks(t1, t2, rna))
+            got = dp.detect_read(t1, t2, rna, seg_len, lanes, lead, {})
+            assert got == exp, (label, seg_len, lanes, lead, sorted(set(got) ^ set(exp))[:6])
+            n_long += len(set(exp) - set(int(p) for p in oracle.peaks(t1, np.zeros_like(t2), rna)))
+    assert n_long > 100      # boundaries the short detector alone does not emit (these reads hold 145)

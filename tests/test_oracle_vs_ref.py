@@ -20,6 +20,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from sigtk_amd import api  # noqa: E402
+import event_cases  # noqa: E402
 import jnn_cases  # noqa: E402
 import prefix_cases  # noqa: E402  (tests/ is on the path: conftest.py lies there)
 
@@ -141,11 +142,33 @@ def observe_jnn_catalogue(lib):
     return out
 
 
+def observe_event_catalogue(lib):
+    """tests/event_cases.py: event on every read with the presets it is run with, starts and lengths by value, mean / stdv
+    bit for bit.  Only the reads the reference lives through: its getevents() runs the trimming pass first, whose
+    assertion fails on reads under 200 samples and on reads whose 100-sample chunks all have the same median absolute
+    deviation (event_cases.ref_cli_prints), and what it does with a read that has no peak is undefined -- on those, the
+    length edges and the bare seeds among them, the oracle is checked against the branch model alone
+    (test_event_cases_cpu.py)"""
+    from oracle.oracle import get_oracle
+    out = {}
+    for k in event_cases.catalogue():
+        if not event_cases.ref_cli_prints(k.raw):
+            continue
+        for label, rna in event_cases.case_runs(k):
+            if get_oracle().event_raw(k.raw, *event_cases.SCALE, rna).start.size < 2:
+                continue
+            e = lib.event_raw(k.raw, *event_cases.SCALE, rna)
+            out[label] = [int(e.start.size), _h(e.start, np.uint64), _h(e.length, np.float32), _h(e.mean, np.float32),
+                          _h(e.stdv, np.float32)]
+    return out
+
+
 OBSERVATIONS = {"pa_event_stat_seed%d" % s: (observe_pa_event_stat, (s,)) for s in (1, 2, 3)}
 OBSERVATIONS.update({"jnn_adaptor_polya_seed%d" % s: (observe_jnn_adaptor_polya, (s,)) for s in (4, 5)})
 OBSERVATIONS["soak_fixtures"] = (observe_soak_fixtures, ())
 OBSERVATIONS["prefix_catalogue"] = (observe_prefix_catalogue, ())
 OBSERVATIONS["jnn_catalogue"] = (observe_jnn_catalogue, ())
+OBSERVATIONS["event_catalogue"] = (observe_event_catalogue, ())
 
 
 def _check(name, oracle, reflib):
@@ -185,6 +208,12 @@ def test_jnn_catalogue(oracle, reflib):
     """every branch of the segmenter, the err-- correction among them (tests/jnn_cases.py): the oracle the GPU tests compare
     against equals the real reference on the whole catalogue"""
     _check("jnn_catalogue", oracle, reflib)
+
+
+def test_event_catalogue(oracle, reflib):
+    """every branch of the peak detector, the boundaries of its long detector among them (tests/event_cases.py): the oracle
+    the GPU tests compare against equals the real reference on every read of the catalogue the reference can take"""
+    _check("event_catalogue", oracle, reflib)
 
 
 if __name__ == "__main__":
