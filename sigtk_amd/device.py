@@ -404,19 +404,24 @@ def deflate_bound(n: int) -> int:
     return int(api.load_library().sgk_deflate_bound(int(n)))
 
 
-def deflate(streams, caps=None, device: Optional[torch.device] = None, with_gaps: bool = False, fill: int = 0):
+def deflate(streams, caps=None, device: Optional[torch.device] = None, with_gaps: bool = False, fill: int = 0,
+            in_shift=None):
     """sgk_deflate over a list of byte strings -> (list of zlib streams as written: out_lengths[r] bytes each, none for a
     stream with a non-zero status, out_lengths, status) -- the device-side replacement of compress2().  caps[r]: room
     for stream r (default: deflate_bound); the output buffer is pre-filled with `fill`.  with_gaps: a fourth result, per
     stream the bytes of the output buffer from out_lengths[r] (0 for a failed stream) up to the next stream's 16-byte
-    aligned area, which the stream must have left alone, a fifth: the byte offset of caps[r] in that gap"""
+    aligned area, which the stream must have left alone, a fifth: the byte offset of caps[r] in that gap.  in_shift[r]
+    (0 .. 15, default 0): stream r's input lies that many bytes behind a 16-byte boundary of the input buffer"""
     L = api.load_library()
     dev = device or torch.device("cuda", 0)
     n = len(streams)
     in_len = np.asarray([len(s) for s in streams], dtype=np.uint32)
+    shift = np.asarray(in_shift if in_shift is not None else [0] * n, dtype=np.uint64)
+    assert shift.size == n and (n == 0 or int(shift.max()) <= 15)
     in_off = np.zeros(n, dtype=np.uint64)
     if n > 1:
-        in_off[1:] = np.cumsum((in_len[:-1].astype(np.uint64) + 15) // 16 * 16)
+        in_off[1:] = np.cumsum((in_len[:-1].astype(np.uint64) + shift[:-1] + 15) // 16 * 16)
+    in_off += shift
     pos = int(in_off[-1]) + int(in_len[-1]) if n else 0
     blob = np.zeros((pos + 19) // 16 * 16, dtype=np.uint8)
     for r, s in enumerate(streams):
@@ -428,6 +433,7 @@ def deflate(streams, caps=None, device: Optional[torch.device] = None, with_gaps
         out_off[1:] = np.cumsum((caps_a[:-1].astype(np.uint64) + 15) // 16 * 16 + gap)
     total = int(out_off[-1] + (int(caps_a[-1]) + 15) // 16 * 16 + gap) if n else 16
     d_in = torch.from_numpy(blob).to(dev)
+    assert _ptr(d_in) % 16 == 0
     d_ioff = torch.from_numpy(in_off.view(np.int64)).to(dev)
     d_ilen = torch.from_numpy(in_len.view(np.int32)).to(dev)
     d_out = torch.full((max(total, 16),), fill, dtype=torch.uint8, device=dev)

@@ -71,6 +71,63 @@ def test_job_records_are_the_host_records(gpu, svb_out):
         job.close()
 
 
+@pytest.mark.parametrize("svb_out", [True, False])
+def test_job_records_at_every_head_and_source_alignment(gpu, svb_out):
+    """k_qts_assemble copies a signal of 64 bytes or more as dwords when (source address + lead) % 4 == 0, where lead =
+    (4 - head % 4) % 4 because records start on 16-byte boundaries; otherwise, and below 64 bytes, byte by byte.  The job's
+    sources are aligned whatever the reads are: int16 samples start on 128-byte boundaries, svb-zd blobs on 8-byte ones.  So
+    the condition is lead == 0: the dword branch is taken exactly by the reads with sbytes >= 64 and head % 4 == 0, and its
+    lead > 0 form cannot be reached through the job.  The head lengths 40 .. 47 cycle over the reads, which puts every
+    fourth read (heads 40 and 44) on the dword branch and the others, at leads 3, 2 and 1, on the byte loop.  The signals
+    are 24 .. 60 samples, twice over and two more (int16: 48 .. 120 bytes, on both sides of the 64; svb-zd blobs of such
+    reads likewise), then large reads: 30001, 4096 and 4097 samples under heads 44, 40 and 44, whose copies are several
+    rounds of the 256-dword stride with (30001, 4097 as int16; whatever the blobs give) a byte tail behind them, and the
+    same lengths under the heads between for the byte loop.  The test works out which reads take the dword branch and
+    asserts that the cases named here are among them.  Every record must inflate to head | u64 | signal | tail: a dword
+    copy from a wrong place, of a wrong count or with a wrong stride shows as other bytes."""
+    lens = list(range(24, 61)) * 2 + [33, 35]
+    assert len(lens) % 8 == 4
+    lens += [30001, 4096, 30001, 4097, 4096, 30001, 4096, 30001, 4097]     # heads 44, 45, 46, 47, 40, 41, 42, 43, 44
+    big = {len(lens) - 9: 30001, len(lens) - 5: 4096, len(lens) - 1: 4097}
+    n = len(lens)
+    reads, dig, off, rng = gpu.synth_reads_host(n, lens, seed=43, kind=0)
+    rs = np.random.RandomState(78)
+    heads = [rs.bytes(40 + r % 8) for r in range(n)]
+    tails = [rs.bytes((0, 1, 37)[r % 3]) for r in range(n)]
+    job = gpu.Job(0)
+    try:
+        blobs = [blow5.svb_zd_encode(r) for r in reads]
+        job.stage(blobs, dig, off, rng, counts=[r.size for r in reads])
+        job.launch_qts(3, 1, svb_out)
+        plain = job.wait()
+        job.set_record_frames([h + t for h, t in zip(heads, tails)], [len(h) for h in heads])
+        job.launch_qts(3, 1, svb_out, records=True)
+        res = job.wait()
+        assert [int(s) for s in res["record_status"]] == [0] * n
+        sbytes = []
+        for r in range(n):
+            if svb_out:
+                sig, ln = plain["blobs"][r], len(plain["blobs"][r])
+            else:
+                sig, ln = plain["samples"][r].astype("<i2").tobytes(), lens[r]
+            sbytes.append(len(sig))
+            assert zlib.decompress(res["records"][r]) == heads[r] + struct.pack("<Q", ln) + sig + tails[r], (r, lens[r])
+        # which reads took which path (the docstring's rule), and that every case it names is there
+        dword = [r for r in range(n) if sbytes[r] >= 64 and len(heads[r]) % 4 == 0]
+        loop = [r for r in range(n) if r not in dword]
+        assert all(lens[r] == v and r in dword for r, v in big.items()), dword
+        assert {len(heads[r]) for r in dword} == {40, 44} and {len(heads[r]) % 4 for r in loop} == {0, 1, 2, 3}
+        small = sorted(sbytes[r] for r in dword if sbytes[r] <= 70)
+        assert len(small) >= 2 and any(v % 4 for v in small), small                       # 64 .. 70 bytes, one with a tail
+        assert any(60 <= sbytes[r] < 64 for r in loop) and any(sbytes[r] < 64 and len(heads[r]) % 4 == 0 for r in loop)
+        strides = [r for r in dword if sbytes[r] // 4 > 512]
+        assert any(sbytes[r] % 4 for r in strides) and any(sbytes[r] // 4 % 256 for r in strides), [sbytes[r] for r in strides]
+        assert all(any(sbytes[r] > 4096 and len(heads[r]) % 4 == k for r in loop) for k in (1, 2, 3))
+        print("dword copies: %d reads of %s bytes; byte loops: %d reads" % (len(dword), [sbytes[r] for r in dword], len(loop)))
+    finally:
+        job.close()
+
+
 def test_fixture_records_are_no_longer_than_huffman_only(gpu, sp1):
     """-b 1 -m round over the 100 fixture reads: the GPU's records, summed, against zlib's Z_HUFFMAN_ONLY of the same
     records (Z_RLE is 8 % under that line: a run-plus-Huffman coder has room, a literal-only one fails)"""

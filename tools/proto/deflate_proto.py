@@ -237,8 +237,10 @@ def plan_block(b: np.ndarray):
                 has_match=has_match)
 
 
-def deflate(data, block: int = DEF_BLOCK, info=None) -> bytes:
-    """info (a list) receives one dict per block: type ('dynamic' / 'stored'), the plan of its dynamic form"""
+def deflate(data, block: int = DEF_BLOCK, info=None, choose=None) -> bytes:
+    """info (a list) receives one dict per block: type ('dynamic' / 'stored'), pos (the bit position in its byte at which
+    the block starts), the plan of its dynamic form.  choose(dynamic bits, pos, block bytes) -> bool replaces the rule
+    that picks the form (tests: a block forced dynamic, wrong rules that the checks must catch)"""
     x = np.frombuffer(bytes(data), dtype=np.uint8)
     w = BitWriter()
     w.put(0x78 | (0x9C << 8), 16)
@@ -249,9 +251,9 @@ def deflate(data, block: int = DEF_BLOCK, info=None) -> bytes:
         p = plan_block(b)
         pos = w.nbits & 7
         stored_bits = 3 + ((-(pos + 3)) % 8) + 32 + 8 * b.size
-        dynamic = p["bits"] < stored_bits
+        dynamic = p["bits"] < stored_bits if choose is None else bool(choose(p["bits"], pos, b.size))
         if info is not None:
-            info.append(dict(type="dynamic" if dynamic else "stored", **p))
+            info.append(dict(type="dynamic" if dynamic else "stored", pos=pos, **p))
         if not dynamic:
             w.put(final, 3)
             w.align()
