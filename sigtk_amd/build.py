@@ -25,6 +25,10 @@ EVENT_SOURCES = ["event_launch.hip", "event_whole.hip", "event_seg.hip", "event_
 HIP_SOURCES = ["api.hip", "api_stat.hip", *EVENT_SOURCES, "stat_launch.hip", "stat_lane.hip", "stat_wave.hip", "stat_long.hip",
                "misc_kernels.hip", "svb_kernels.hip", "sigtext_kernels.hip", "inflate_kernels.hip", "deflate_kernels.hip", "zstd_kernels.hip", "zrec_kernels.hip", "ent_kernels.hip",
                "qts_kernels.hip", "text_kernels.hip", "sref_kernels.hip", "ss_kernels.hip", "job.hip", "shims.hip"]
+# Per-source flags.  The SLP vectoriser pairs the detector's f32 arithmetic into v_pk_*_f32, which issue at the cost of
+# two plain instructions and take no |x| / -x operand modifier: every fabsf becomes a v_and_b32 of its own.  Without it
+# k_event and k_event_multi need fewer registers and spills; k_event_seg and k_event_fallback need more, so they keep it.
+SOURCE_FLAGS = {"event_whole.hip": ["-fno-slp-vectorize"], "event_multi.hip": ["-fno-slp-vectorize"]}
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
                "-fhip-fp32-correctly-rounded-divide-sqrt", "-fPIC", "-shared", "-Wall",
                "-Wno-unused-function", "-Wno-bitwise-instead-of-logical", "-Wno-c++20-extensions", "-Wno-pass-failed"]
@@ -63,7 +67,7 @@ def build_lib(force: bool = False, verbose: bool = False) -> str:
         obj = os.path.join(objdir, os.path.basename(src)[:-4] + ".o")
         objs.append(obj)
         if force or not _newer(obj, [src] + hdrs):
-            jobs.append([cc, *flags, "-c", "-o", obj, src])
+            jobs.append([cc, *flags, *SOURCE_FLAGS.get(os.path.basename(src), []), "-c", "-o", obj, src])
 
     def run(cmd):
         if verbose:
@@ -92,7 +96,7 @@ def build_variant(tag: str, defines, sources=(*EVENT_SOURCES, "api.hip"), verbos
         base = s_[:-4]
         if s_ in sources:
             obj = os.path.join(vdir, "%s_%s.o" % (base, tag))
-            cmd = [cc, *flags, "-c", "-o", obj, os.path.join(CSRC, s_)]
+            cmd = [cc, *flags, *SOURCE_FLAGS.get(s_, []), "-c", "-o", obj, os.path.join(CSRC, s_)]
             if verbose:
                 print(" ".join(cmd), file=sys.stderr)
             subprocess.check_call(cmd)
@@ -146,15 +150,25 @@ def build_cli_asan(force: bool = False, verbose: bool = False) -> str:
 
 
 def build_tools(force: bool = False, verbose: bool = False) -> None:
-    """the stand-alone HIP programs of tools/ (issue-rate microbenchmark, hardware accuracy check of v_rsq_f32)"""
+    """the stand-alone programs of tools/: HIP (issue-rate microbenchmark, hardware accuracy check of v_rsq_f32, the
+    certified square root on the GPU: with the library's numerics flags) and host (sqrt_check: the same form against sqrtf)"""
     tdir = os.path.join(ROOT, "tools")
-    for name in ("rsq_check", "valu_rate", "fetch_calib"):
+    math_h = os.path.join(CSRC, "tstat_math.h")
+    numerics = ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]
+    for name in ("rsq_check", "valu_rate", "fetch_calib", "sqrt_cert_gpu"):
         src = os.path.join(tdir, name + ".hip")
         exe = os.path.join(tdir, name)
         deps = [src] + ([os.path.join(tdir, "valu_rate_tests.inc")] if name == "valu_rate" else [])
+        deps += [math_h] if name == "sqrt_cert_gpu" else []
         if not os.path.exists(src) or (not force and _newer(exe, deps)):
             continue
-        cmd = [hipcc(), "--offload-arch=gfx950", "-O2", "-o", exe, src]
+        cmd = [hipcc(), "--offload-arch=gfx950", "-O2", *(numerics if name == "sqrt_cert_gpu" else []), "-o", exe, src]
+        if verbose:
+            print(" ".join(cmd), file=sys.stderr)
+        subprocess.check_call(cmd)
+    src, exe = os.path.join(tdir, "sqrt_check.cpp"), os.path.join(tdir, "sqrt_check")
+    if os.path.exists(src) and (force or not _newer(exe, [src, math_h])):
+        cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-pthread", "-o", exe, src]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         subprocess.check_call(cmd)

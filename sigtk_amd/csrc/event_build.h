@@ -32,7 +32,15 @@ __device__ __forceinline__ void store_event_fast(const EvOut &o, uint32_t k, uin
     const float r1 = sgk_refined_rcp(len);
     const float m = sgk_div_with_rcp((float)dsum, len, r1);
     const float var = sgk_div_with_rcp((float)dsumsq, len, r1) - m * m;
-    const float sd = sqrtf(fmaxf(var, 0.0f));
+    // certified square root (tstat_math.h); the two conditions meet as lane masks, the rare lane takes sqrtf
+    const float v = fmaxf(var, 0.0f);
+    bool dom_ok, cert_ok;
+    float sd = sgk_sqrt_cert(v, dom_ok, cert_ok);
+    const lmask_t sq_ok = __ballot(dom_ok) & __ballot(cert_ok);
+    if (!lane_of(sq_ok)) {
+        __asm__ volatile("" ::: "memory");  // a real branch: if-converted, every lane would evaluate both forms
+        sd = sqrtf(v);
+    }
     uint4 e;
     e.x = ps;
     e.y = pe - ps;
@@ -88,6 +96,9 @@ __device__ __forceinline__ void build_walk(const TileRegs<T> &buf, uint32_t bits
     typedef __attribute__((address_space(3))) uint16_t *LdsU16;
     uint32_t rr32 = (uint32_t)(uintptr_t)(LdsBytes)(char *)L->rec + (uint32_t)excl * 16u;
     uint32_t rp32 = (uint32_t)(uintptr_t)(LdsBytes)(char *)L->p + (uint32_t)excl * 2u;
+    // The boundary bits are taken from the top of the reversed word: doubling it hands the next bit out as the carry, a
+    // lane mask in scalar registers from one add (v_add_co_u32) instead of v_and_b32 + v_cmp_ne_u32 per sample.
+    uint32_t rbits = __builtin_bitreverse32(bits);
 #pragma unroll
     for (int k = 0; k < BT; ++k) {
         float x = buf.pa(k, sc);
@@ -101,7 +112,9 @@ __device__ __forceinline__ void build_walk(const TileRegs<T> &buf, uint32_t bits
             mxb = ab > mxb ? ab : mxb;
             mnb = (ab - 1u) < mnb ? (ab - 1u) : mnb;
         }
-        if ((bits >> k) & 1u) {
+        lmask_t bnd;
+        asm("v_add_co_u32 %0, %1, %0, %0" : "+v"(rbits), "=s"(bnd));
+        if (lane_of(bnd)) {
             typedef double __attribute__((ext_vector_type(2))) sgk_d2;
             *(__attribute__((address_space(3))) sgk_d2 *)(uintptr_t)rr32 = sgk_d2{S, S2};   // BuildRec {S, S2}
             *(LdsU16)(uintptr_t)rp32 = (uint16_t)(l * BT + k);

@@ -314,10 +314,19 @@ struct LazyPass {
         const double b1 = Ps[(U + W1) % NP] - p0, b1q = Pq[(U + W1) % NP] - q0;
         const double b2 = Ps[(U + W2) % NP] - p0, b2q = Pq[(U + W2) % NP] - q0;
         // short window: its A side was ringed W1 indices ago
-        bool ok;
-        const float v = sgk_tstat_try_ab<W1>(b1, b1q, ar[(U + NA - W1) % NA], ok);
-        bool clean = true;
-        if constexpr (FLAGGED) {
+        const SgkLSide lb = sgk_lside<W2>(b2, b2q);  // long window: bound only
+        if constexpr (!FLAGGED) {
+            // the certificate's two conditions are combined as lane masks, on the scalar unit (see sgk_tstat_try_ab)
+            bool cv_ok, tail_ok;
+            t1[U & 3] = sgk_tstat_try_ab<W1>(b1, b1q, ar[(U + NA - W1) % NA], cv_ok, tail_ok);
+            nk[U & 3] = ~(__ballot(cv_ok) & __ballot(tail_ok));
+            ar[U % NA] = sgk_arole<W1, true>(b1, b1q);
+            hc[U & 3] = ~__ballot(sgk_long_cold<W2>(ls[(U + NL - W2) % NL], lb));
+            ls[U % NL] = lb;
+        } else {
+            // (the fallback kernel keeps its conditions as bools: as masks they cost it registers and spills)
+            bool ok;
+            const float v = sgk_tstat_try_ab<W1>(b1, b1q, ar[(U + NA - W1) % NA], ok);
             ok = ok && sgk_try_domain<W1>(b1, b1q, ar[(U + NA - W1) % NA]);
             // A flagged read failed the magnitude guard: the lane's running prefix can round as well, and not where
             // the reference's sequential scan did (other origin, other magnitudes), so `rep` does not list those
@@ -328,19 +337,17 @@ struct LazyPass {
             const double a_q = Pq[(U + W2) % NP], b_q = (double)xqn, r_q = Pq[(U + W2 + 1) % NP];
             const double t_s = r_s - a_s, t_q = r_q - a_q;
             const double e_s = (a_s - (r_s - t_s)) + (b_s - t_s), e_q = (a_q - (r_q - t_q)) + (b_q - t_q);
-            clean = U > dirty;
+            const bool clean = U > dirty;
             if (e_s != 0.0 || e_q != 0.0) dirty = dirty > U + 2 * W2 ? dirty : U + 2 * W2;
             ok = ok && clean;
+            ar[U % NA] = sgk_arole<W1, false>(b1, b1q);
+            bool cold = sgk_long_cold<W2>(ls[(U + NL - W2) % NL], lb);
+            cold = cold && clean && sgk_lside_domain(ls[(U + NL - W2) % NL]) && sgk_lside_domain(lb);
+            ls[U % NL] = lb;
+            t1[U & 3] = v;
+            nk[U & 3] = ~__ballot(ok);
+            hc[U & 3] = ~__ballot(cold);
         }
-        ar[U % NA] = sgk_arole<W1, !FLAGGED>(b1, b1q);
-        // long window: bound only
-        const SgkLSide lb = sgk_lside<W2>(b2, b2q);
-        bool cold = sgk_long_cold<W2>(ls[(U + NL - W2) % NL], lb);
-        if constexpr (FLAGGED) cold = cold && clean && sgk_lside_domain(ls[(U + NL - W2) % NL]) && sgk_lside_domain(lb);
-        ls[U % NL] = lb;
-        t1[U & 3] = v;
-        nk[U & 3] = ~__ballot(ok);
-        hc[U & 3] = ~__ballot(cold);
     }
 
     // One step of the short detector (events.c:383-440, k = 0) and of the lazy long detector's bookkeeping, on lane
@@ -698,8 +705,9 @@ __device__ __forceinline__ void pass_lazy(const ReadCtx<T> &rc, bool given, int 
         // (... or a peak in front of the lane's own range in the range's first block: it may be emitted there within
         // w/2 indices, as a "usual" peak whose bit the fast steps would put into the bitmap word; in later blocks it is
         // an "older peak", which the fast steps hand to the ring or, in front of the range, to LZ_PRE)
-        const bool old_peak = f.sp < -(256 - 2 * R) || (f.sp + jb < own_lo && jb == own_lo);
-        f.oldpeak = (__ballot(old_peak) & f.inpk & ~f.done) != 0ull;
+        // (one ballot per compare, combined as masks: a bool OR / AND of compares reaches __ballot through a vector 0/1)
+        const lmask_t old_peak = __ballot(f.sp < -(256 - 2 * R)) | (__ballot(f.sp + jb < own_lo) & __ballot(jb == own_lo));
+        f.oldpeak = (old_peak & f.inpk & ~f.done) != 0ull;
         f.slow = f.oldpeak || (__ballot(lane_edge) & ~f.done) != 0ull;
         f.ib = ib;
         f.jb = jb;

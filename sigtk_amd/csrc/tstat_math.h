@@ -253,8 +253,11 @@ SGK_TM SgkARole sgk_arole(double S, double Sq) {
 // reference expression instead.  Preconditions (read-level guard, event_device.h): every non-zero |x| in
 // [2^-20, 2^20], so window sums are 0 or >= 2^-43, the f32 constant divisions below never see a non-zero dividend
 // under 2^-100, and a non-zero delta is >= 2^-69.
+// (The two conditions of the certificate come back separately: a wave forms its mask as
+// __ballot(cv_ok) & __ballot(tail_ok), two compares and one scalar AND.  ANDed as bools in front of one ballot, the
+// second compare's mask went through a vector 0/1 and back: v_cndmask 0, 1 + v_cmp_ne 0 per index.)
 template <int W>
-SGK_TM float sgk_tstat_try_ab(double S, double Sq, const SgkARole &a, bool &ok) {
+SGK_TM float sgk_tstat_try_ab(double S, double Sq, const SgkARole &a, bool &cv_ok, bool &tail_ok) {
     const float sum2 = (float)S;
     const float sumsq2 = (float)Sq;
     const float mean2 = sgk_div_f32<W>(sum2);
@@ -263,11 +266,15 @@ SGK_TM float sgk_tstat_try_ab(double S, double Sq, const SgkARole &a, bool &ok) 
     double acc = a.va + (double)q2;
     acc = acc - (double)m2sq;
     const float cv = (float)acc;
-    const bool cv_ok = cv > SGK_CV_MIN;  // also false for NaN
+    cv_ok = cv > SGK_CV_MIN;  // also false for NaN
     const float delta = mean2 - a.mean1;
     const float cvw = sgk_div_f32<W>(cv);
-    bool tail_ok;
-    const float v = sgk_tail_f32(delta, cvw, tail_ok);
+    return sgk_tail_f32(delta, cvw, tail_ok);
+}
+template <int W>
+SGK_TM float sgk_tstat_try_ab(double S, double Sq, const SgkARole &a, bool &ok) {
+    bool cv_ok, tail_ok;
+    const float v = sgk_tstat_try_ab<W>(S, Sq, a, cv_ok, tail_ok);
     ok = cv_ok & tail_ok;
     return v;
 }
@@ -322,6 +329,46 @@ SGK_TM float sgk_div_with_rcp(float a, float b, float r1) {
     const float q1 = fmaf(rem0, r1, q0);
     const float rem1 = fmaf(-b, q1, a);
     return fmaf(rem1, r1, q1);
+}
+
+// ---- create_event's standard deviation: sqrtf(v), v = max(sumsq/len - mean*mean, 0) (events.c:468-471) ----
+// The correctly rounded f32 square root the compiler emits is 16 instructions (scaling, v_sqrt_f32, two corrections,
+// fix-ups); the form below is 12, in the style of sgk_tail_f32:
+//   y0 = rsq(v) (relative error eta),  s0 = RN(v*y0),  e = RN(v - s0^2) (FMA: the residual is rounded once),
+//   sl = RN(e * y0/2):  sqrt(v) = s0 + (v - s0^2) / (sqrt(v) + s0), and y0/2 stands for 1 / (sqrt(v) + s0) within
+//   1.5 eta + u, so  |s0 + sl - sqrt(v)| <= |s0 - sqrt(v)| (1.5 eta + 3u) <= (eta + u)(1.5 eta + 3u) sqrt(v):
+//   2^-44.2 sqrt(v) with the hardware's eta = 2^-23.3 (tools/rsq_check.hip), 2^-42.9 sqrt(v) with twice that.
+//   m = 2^-40 s0:  if RN(s0 + (sl - m)) == RN(s0 + (sl + m)) no float rounding boundary lies within the error band
+//   (forming sl -+ m by FMA adds 2^-45 of it), so the common value IS RN(sqrt(v)); otherwise (2^-15 of the inputs), or
+//   on NaN, the caller takes sqrtf.
+// Domain.  Under the read-level guard (event_device.h: guard_ok) every non-zero |x| lies in [2^-20, 2^20], so the mean
+// square q and the squared mean p are floats with 2^-40 <= q <= 2^40 and 0 <= p <= 2^40.  If p >= q/2 the difference
+// q - p is exact (Sterbenz), a multiple of ulp(2^-41) = 2^-64; otherwise it is at least q/2 >= 2^-41.  The variance
+// is therefore 0 or in [2^-64, 2^41), and nothing above is subnormal there (|e| is 0 or at least 2^-46 v).  The
+// bounds are tested on the bit pattern; everything outside them -- zero (events of constant samples), negative zero,
+// values of reads that fail the guard (their events are stored before the verdict and redone by the fallback
+// kernel), infinities -- takes sqrtf.  Checked on all 2^32 bit patterns by tools/sqrt_check.cpp, on the GPU by
+// tests/test_gpu_sqrt_cert.py.
+#define SGK_SQRT_LO 0x1F800000u /* 2^-64 */
+#define SGK_SQRT_HI 0x54000000u /* 2^41 */
+// the two conditions separately: a wave combines them as lane masks (see sgk_tstat_try_ab)
+SGK_TM float sgk_sqrt_cert(float v, bool &dom_ok, bool &cert_ok) {
+    dom_ok = (sgk_f2u(v) - SGK_SQRT_LO) < (SGK_SQRT_HI - SGK_SQRT_LO);
+    const float y0 = SGK_RSQ32(v);
+    const float s0 = v * y0;
+    const float e = fmaf(-s0, s0, v);
+    const float yh = 0.5f * y0;
+    const float sl = e * yh;
+    const float lo = s0 + fmaf(s0, -9.094947017729282e-13f, sl);  // 2^-40
+    const float hi = s0 + fmaf(s0, 9.094947017729282e-13f, sl);
+    cert_ok = lo == hi;
+    return lo;
+}
+SGK_TM float sgk_sqrt_cert(float v, bool &ok) {
+    bool dom_ok, cert_ok;
+    const float s = sgk_sqrt_cert(v, dom_ok, cert_ok);
+    ok = dom_ok & cert_ok;
+    return s;
 }
 
 // ---- lazy long detector: a rigorous "cannot exceed thr2" test ----------------------------------------

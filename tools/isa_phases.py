@@ -77,8 +77,8 @@ def analyse(lines):
     insts = []   # (line index in `lines`, op, rest)
     labels = {}
     for i, ln in enumerate(lines):
-        t = ln.strip()
-        if not t or t.startswith((";", "//", ".")) and not t.endswith(":"):
+        t = ln.split(";")[0].strip()   # (labels carry comments: ".LBB17_38:   ; =>This Inner Loop Header")
+        if not t or t.startswith(("//", ".")) and not t.endswith(":"):
             continue
         if t.endswith(":") and not t.startswith(("s_", "v_")):
             labels[t[:-1]] = len(insts)
@@ -118,6 +118,9 @@ def main():
                "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wno-unused-function", "-Wno-bitwise-instead-of-logical",
                "-Wno-c++20-extensions", "-Wno-pass-failed", "-I", os.path.join(root, "include"), "--cuda-device-only", "-S",
                "-o", a.asm, a.build] + ["-D" + d for d in a.define]
+        sys.path.insert(0, root)
+        from sigtk_amd.build import SOURCE_FLAGS   # the unit's own flags of the shipped build
+        cmd += SOURCE_FLAGS.get(os.path.basename(a.build), [])
         subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
     if a.list:
         txt = open(a.asm).read()
