@@ -75,7 +75,8 @@ extern "C" {
  *        SGK_RECORD_ZLIB / SGK_RECORD_ZSTD and sgk_job_begin_zrec_format (BLOW5 files with zstd records);
  *        sgk_aux_field_t, sgk_zrec_tail_check and sgk_job_begin_zrec_aux (records with variable-length auxiliary fields);
  *        sgk_deflate, sgk_deflate_bound, sgk_deflate_block_bytes, sgk_job_set_record_frames and SGK_QTS_RECORDS with the
- *        qts_record* fields at the end of sgk_job_output_t (`qts --gpu-deflate`: records deflated on the GPU). */
+ *        qts_record* fields at the end of sgk_job_output_t (`qts --gpu-deflate`: records deflated on the GPU);
+ *        sgk_slow5_text_* and SGK_SIGNAL_TEXT as input and output format of sgk_job_submit_qts (`qts` on text SLOW5). */
 #define SGK_VERSION_STRING "0.2.3"
 
 /* ---- error codes --------------------------------------------------------------- */
@@ -526,6 +527,28 @@ int sgk_text_status(const void *workspace, sgk_text_status_t *out);
 int sgk_text_numbers_f32(const float *v, uint64_t n, uint8_t *slots48, uint8_t *lengths, void *stream);
 int sgk_text_numbers_i64(const int64_t *v, uint64_t n, uint8_t *slots48, uint8_t *lengths, void *stream);
 
+/* ---- text SLOW5: the raw_signal column written on the device (csrc/slow5_text_kernels.hip; additive to 0.2.3) ------ */
+/* The inverse of sgk_sigtext_decode, for `qts` on text files.  Row r of the batch is head_r | v0,v1,...,v(n-1) | tail_r
+ * with n = lengths[r] and every sample as printf("%d") (slow5lib/src/slow5.c:3826-3860); a read of 0 samples has an
+ * empty column.  heads / tails (device pointers, as sgk_text_ids_t: entry r is bytes[offsets[r] .. offsets[r + 1]))
+ * hold arbitrary bytes of any length; NULL means all empty.  The kernels add no tab and no newline: for whole lines
+ * the head ends with the tab in front of the column and the tail with the newline.  samples / offsets / lengths as in
+ * sgk_batch_t (device pointers).  measure / write / status work as for sgk_text_*: both calls asynchronous on `stream`
+ * with the same inputs and the same workspace (16-byte aligned; n_samples_capacity: the sum of the lengths or more),
+ * row_offsets[r] the byte offset of row r and row_offsets[n_reads] the total, `text` at any byte address, no byte
+ * outside [text, text + row_offsets[n_reads]) written, text_capacity checked on the device, sgk_text_status afterwards
+ * (SGK_ERR_CAPACITY / SGK_ERR_WORKSPACE).  Tiles of 256 samples are staged in an LDS image of
+ * SGK_SLOW5_TEXT_STAGE_BYTES and leave as 16-byte stores; a tile that carries a head or a tail and does not fit the
+ * image writes its bytes straight to global memory.  A tile of 4 GiB or more reports SGK_ERR_CAPACITY. */
+#define SGK_SLOW5_TEXT_STAGE_BYTES 8192
+size_t sgk_slow5_text_workspace_bytes(uint32_t n_reads, uint64_t n_samples_capacity);
+int sgk_slow5_text_measure(const int16_t *samples, const uint64_t *offsets, const uint32_t *lengths, uint32_t n_reads,
+                           const sgk_text_ids_t *heads, const sgk_text_ids_t *tails, uint64_t *row_offsets /* n_reads + 1 */,
+                           void *workspace, size_t workspace_bytes, void *stream);
+int sgk_slow5_text_write(const int16_t *samples, const uint64_t *offsets, const uint32_t *lengths, uint32_t n_reads,
+                         const sgk_text_ids_t *heads, const sgk_text_ids_t *tails, uint8_t *text, uint64_t text_capacity,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- sref: the synthetic reference signal of a sequence (csrc/sref_kernels.hip) -------------------------------------- */
 /* `sigtk sref` (src/sref.c:100-210): position j of a strand's row is level_mean[rank(bases j .. j + k)], rank with the
  * first base most significant, A/a 0, C/c 1, G/g 2, T/t 3 and every other byte 0; the '-' strand is the reverse
@@ -757,7 +780,8 @@ typedef struct sgk_job sgk_job_t;
                             * GPU (sgk_job_begin_zrec) */
 #define SGK_SIGNAL_TEXT 3  /* caller stages the raw_signal column of text SLOW5 records (blob_bytes[r] = its byte length) at
                             * in.blobs + in.blob_offsets[r]; parsed on the GPU (sgk_sigtext_decode; additive to 0.2.3).
-                            * Every sgk_job_submit kind takes it; sgk_job_submit_qts returns SGK_ERR_ARG */
+                            * Every sgk_job_submit kind and sgk_job_submit_qts take it.  As the OUTPUT format of
+                            * sgk_job_submit_qts: the quantised signal written as text on the device (sgk_slow5_text_*) */
 
 #define SGK_JOB_EVENTS_COMPACT 1 /* submit flag: only event start/length are copied back (event -c) */
 #define SGK_JOB_EVENTS_LENGTHS 2 /* submit flag (0.2.3): only the event lengths are copied back -- ev_start, ev_mean and
@@ -849,8 +873,12 @@ int sgk_job_begin_zrec_aux(sgk_job_t *job, uint32_t n_reads, int record_format, 
                            const uint32_t *rec_room, const sgk_aux_field_t *fields, uint32_t n_fields, sgk_job_input_t *in);
 /* may be called again after sgk_job_wait to run another tool over the same staged batch */
 int sgk_job_submit(sgk_job_t *job, int tool, int rna, int pore, int flags);
-/* qts over the staged batch: quantise (bits in [1,15], method SGK_QTS_*), then hand the signal back as svb-zd blobs
- * (out_signal_format SGK_SIGNAL_SVBZD) or int16 samples (SGK_SIGNAL_INT16) */
+/* qts over the staged batch (any input format; text input with bare SGK_SIGNAL_INT16 samples out, without
+ * SGK_QTS_RECORDS, is SGK_ERR_ARG as it always was): quantise (bits in [1,15], method SGK_QTS_*), then hand the signal back
+ * as svb-zd blobs (out_signal_format SGK_SIGNAL_SVBZD), int16 samples (SGK_SIGNAL_INT16) or -- additive to 0.2.3 --
+ * as the raw_signal columns of text SLOW5 records (SGK_SIGNAL_TEXT): row r is the column of read r, fetched with
+ * sgk_job_text after sgk_job_wait.  With SGK_QTS_RECORDS (below) the rows are whole lines: frame r's first
+ * head_lengths[r] bytes, the column, the rest of the frame; nothing is inserted between them and nothing is deflated. */
 int sgk_job_submit_qts(sgk_job_t *job, int bits, int method, int out_signal_format);
 /* qts record mode (additive to 0.2.3).  Between sgk_job_begin* and sgk_job_submit_qts: what a BLOW5 record holds around
  * its signal.  Frame r is bytes[frame_offsets[r] .. frame_offsets[r + 1]) (frame_offsets[0] = 0): first the record's
@@ -858,7 +886,7 @@ int sgk_job_submit_qts(sgk_job_t *job, int bits, int method, int out_signal_form
  * the job's pinned staging.  With SGK_QTS_RECORDS or'ed into out_signal_format, sgk_job_submit_qts then assembles
  * head | u64 len_raw_signal | signal | tail for every read on the device (k_qts_assemble; len_raw_signal is the blob
  * length for SGK_SIGNAL_SVBZD, the sample count for SGK_SIGNAL_INT16), deflates the records there (sgk_deflate) and
- * downloads only the zlib streams: sgk_job_output_t::qts_records.  SGK_ERR_ARG without frames, or for text input. */
+ * downloads only the zlib streams: sgk_job_output_t::qts_records.  SGK_ERR_ARG without frames. */
 #define SGK_QTS_RECORDS 0x100
 int sgk_job_set_record_frames(sgk_job_t *job, const uint8_t *bytes, const uint32_t *frame_offsets /* n + 1 */,
                               const uint32_t *head_lengths /* n */);
@@ -878,7 +906,8 @@ typedef struct sgk_job_text {
     const uint64_t *row_offsets; /* n_reads + 1 */
     uint64_t n_bytes;            /* row_offsets[n_reads] */
 } sgk_job_text_t;
-/* after sgk_job_wait of a submit with SGK_JOB_TEXT; valid until the job's next sgk_job_begin */
+/* after sgk_job_wait of a submit with SGK_JOB_TEXT, or of sgk_job_submit_qts with SGK_SIGNAL_TEXT as the output format;
+ * valid until the job's next sgk_job_begin */
 int sgk_job_text(const sgk_job_t *job, sgk_job_text_t *out);
 
 /* ---- per-read shims with the reference's own signatures (batch of one) ------------- */

@@ -240,7 +240,8 @@ class JobText(C.Structure):      # sgk_job_text_t
 TOOL_PA, TOOL_EVENT, TOOL_STAT, TOOL_JNN, TOOL_PREFIX, TOOL_ENT, TOOL_QTS = range(7)
 ENT_HIST_BYTES = 4 * (4 + 8192 + 4096 + 512)   # sizeof(sgk_ent_hist_t)
 SIGNAL_INT16, SIGNAL_SVBZD = 0, 1
-SIGNAL_TEXT = 3   # the raw_signal column of text SLOW5 records, parsed on the GPU
+SIGNAL_TEXT = 3   # the raw_signal column of text SLOW5 records, parsed on the GPU (launch_qts(out_text=True): written there)
+SLOW5_TEXT_STAGE_BYTES = 8192   # SGK_SLOW5_TEXT_STAGE_BYTES: a tile's LDS image in sgk_slow5_text_write
 RECORD_ZLIB, RECORD_ZSTD = 1, 2   # SGK_RECORD_*: what the records of Job.stage_zrec are compressed with
 
 
@@ -285,6 +286,8 @@ ABI_SYMBOLS = [
     # the TSV rows written on the device (csrc/text_kernels.hip)
     "sgk_text_workspace_bytes", "sgk_text_measure", "sgk_text_write", "sgk_text_status", "sgk_text_numbers_f32",
     "sgk_text_numbers_i64", "sgk_job_set_ids", "sgk_job_text",
+    # the raw_signal column of text SLOW5 records written on the device (csrc/slow5_text_kernels.hip)
+    "sgk_slow5_text_workspace_bytes", "sgk_slow5_text_measure", "sgk_slow5_text_write",
     # sref: the synthetic reference signal as floats and as rows (csrc/sref_kernels.hip)
     "sgk_sref_levels", "sgk_sref_text_workspace_bytes", "sgk_sref_text_measure", "sgk_sref_text_write",
     "sgk_sref_pipe_create", "sgk_sref_pipe_destroy", "sgk_sref_pipe_begin", "sgk_sref_pipe_submit", "sgk_sref_pipe_wait",
@@ -457,6 +460,12 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.sgk_text_numbers_f32.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.sgk_text_numbers_i64.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.sgk_sref_levels.argtypes = [C.POINTER(SrefBatch), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sgk_slow5_text_workspace_bytes.restype = C.c_size_t
+    L.sgk_slow5_text_workspace_bytes.argtypes = [C.c_uint32, C.c_uint64]
+    L.sgk_slow5_text_measure.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(TextIds), C.POINTER(TextIds),
+                                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.sgk_slow5_text_write.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(TextIds), C.POINTER(TextIds),
+                                       C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p]
     L.sgk_sref_text_workspace_bytes.restype = C.c_size_t
     L.sgk_sref_text_workspace_bytes.argtypes = [C.c_uint32, C.c_uint64]
     L.sgk_sref_text_measure.argtypes = [C.POINTER(SrefBatch), C.POINTER(TextIds), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -848,14 +857,19 @@ class Job:
         check(self.L.sgk_job_set_record_frames(self.h, blob if blob else None, offs.ctypes.data,
                                                heads.ctypes.data if len(raw) else None), "sgk_job_set_record_frames")
 
-    def launch_qts(self, bits: int, method: int, out_svb: bool, records: bool = False):
+    def launch_qts(self, bits: int, method: int, out_svb: bool, records: bool = False, out_text: bool = False):
         """records=True (after set_record_frames): the records are assembled and deflated on the GPU; wait() then
-        returns res["records"] (zlib streams) and res["record_status"] instead of the blobs / samples"""
+        returns res["records"] (zlib streams) and res["record_status"] instead of the blobs / samples.
+        out_text=True (SGK_SIGNAL_TEXT as the output format): the quantised signal as text SLOW5 columns written on the
+        GPU; wait() returns res["text"] and res["row_offsets"] -- with records=True the rows are frame head | column |
+        frame tail"""
         self._tool = TOOL_QTS
         self._text = False
         self._qts_svb = out_svb
-        self._qts_records = records
-        check(self.L.sgk_job_submit_qts(self.h, bits, method, (SIGNAL_SVBZD if out_svb else SIGNAL_INT16) |
+        self._qts_records = records and not out_text
+        self._qts_text = out_text
+        check(self.L.sgk_job_submit_qts(self.h, bits, method,
+                                        (SIGNAL_TEXT if out_text else SIGNAL_SVBZD if out_svb else SIGNAL_INT16) |
                                         (QTS_RECORDS if records else 0)), "sgk_job_submit_qts")
 
     def submit(self, tool: int, signals, dig, off, rng, rna: int = 0, pore: int = 0, flags: int = 0, counts=None, ids=None,
@@ -914,7 +928,12 @@ class Job:
         elif self._tool == TOOL_PREFIX:
             res["prefix"] = np.frombuffer(C.string_at(o.prefix, n * PREFIX_DTYPE.itemsize), dtype=PREFIX_DTYPE).copy()
         elif self._tool == TOOL_QTS:
-            if getattr(self, "_qts_records", False):
+            if getattr(self, "_qts_text", False):
+                t = JobText()
+                check(self.L.sgk_job_text(self.h, C.byref(t)), "sgk_job_text")
+                res["text"] = C.string_at(t.text, t.n_bytes) if t.n_bytes else b""
+                res["row_offsets"] = _np_from(t.row_offsets, n + 1, np.uint64).copy()
+            elif getattr(self, "_qts_records", False):
                 res["records"] = [C.string_at(o.qts_records + int(o.qts_record_offsets[r]), int(o.qts_record_lengths[r]))
                                   for r in range(n)]
                 res["record_status"] = _np_from(o.qts_record_status, n, np.uint32).copy() if n else np.zeros(0, np.uint32)

@@ -130,6 +130,10 @@ struct sgk_job {
     GrowDev d_frb, d_fro, d_frh, d_reclen, d_recoffs, d_rec, d_zcap, d_zoffs, d_z, d_zlen, d_zstat, d_zdoffs, d_zdense;
     bool have_frames = false;
     size_t frame_bytes = 0;
+    // qts with SGK_SIGNAL_TEXT out: the frames again as the heads and the tails of the rows (sgk_slow5_text_*)
+    GrowPin h_hdb, h_hdo, h_tlb, h_tlo;
+    GrowDev d_hdb, d_hdo, d_tlb, d_tlo;
+    bool text_frames = false;
     bool text_written = false;        // the write pass was enqueued at submit, into the buffer earlier batches grew
     int text_kind = 0;
     size_t tws_bytes = 0, id_bytes = 0;
@@ -541,8 +545,15 @@ __global__ __launch_bounds__(256) void k_gather_events(const sgk_event_rec_t *sr
     }
 }
 
-// SGK_JOB_TEXT: the write pass over the measured batch, into d_text as far as it reaches (checked on the device)
+// SGK_JOB_TEXT / qts text: the write pass over the measured batch, into d_text as far as it reaches (checked on the device)
 static int job_text_write(sgk_job_t *j) {
+    if (j->tool == SGK_TOOL_QTS) {
+        const sgk_text_ids_t heads = {j->d_hdb.as<uint8_t>(), j->d_hdo.as<uint32_t>()};
+        const sgk_text_ids_t tails = {j->d_tlb.as<uint8_t>(), j->d_tlo.as<uint32_t>()};
+        return sgk_slow5_text_write(j->text_view.samples, j->text_view.offsets, j->text_view.lengths, j->n_reads,
+                                    j->text_frames ? &heads : nullptr, j->text_frames ? &tails : nullptr,
+                                    j->d_text.as<uint8_t>(), j->d_text.cap, j->d_tws.p, j->tws_bytes, j->st);
+    }
     const bool ev = j->text_kind != SGK_TEXT_PA;
     const sgk_text_ids_t ids = {j->d_idb.as<uint8_t>(), j->d_ido.as<uint32_t>()};
     return sgk_text_write(j->text_kind, &j->text_view, &ids, ev ? j->d_slots.as<uint64_t>() : nullptr,
@@ -568,6 +579,59 @@ static int job_text_submit(sgk_job_t *j, int kind, const sgk_batch_t *view, uint
     rc = sgk_text_measure(kind, view, &ids, ev ? j->d_slots.as<uint64_t>() : nullptr,
                           ev ? j->d_out[0].as<sgk_event_rec_t>() : nullptr, ev ? j->d_cnt.as<uint32_t>() : nullptr,
                           j->d_roffs.as<uint64_t>(), j->d_tws.p, j->tws_bytes, st);
+    if (rc != SGK_OK) return rc;
+    if ((rc = d2h(j->h_roffs, j->d_roffs, (nr + 1) * 8, st)) != SGK_OK) return rc;
+    j->text_written = false;
+    if (j->d_text.cap) {
+        if ((rc = job_text_write(j)) != SGK_OK) return rc;
+        j->text_written = true;
+    }
+    return SGK_OK;
+}
+
+// qts with SGK_SIGNAL_TEXT out: the quantised samples as the rows' columns; with frames, head r and tail r around them.
+// The frames are split into a blob of heads and one of tails here (a few hundred bytes per read), then as job_text_submit.
+static int job_qts_text_submit(sgk_job_t *j, const sgk_batch_t *view, bool records) {
+    const size_t nr = j->n_reads;
+    hipStream_t st = j->st;
+    int rc;
+    j->text_frames = records;
+    if (records) {
+        const uint32_t *fro = j->h_fro.as<uint32_t>(), *frh = j->h_frh.as<uint32_t>();
+        const uint8_t *frb = j->h_frb.as<uint8_t>();
+        size_t hb = 0;
+        for (size_t r = 0; r < nr; ++r) hb += frh[r];
+        const size_t tb = j->frame_bytes - hb;
+        if ((rc = j->h_hdb.ensure(hb + 16)) != SGK_OK) return rc;
+        if ((rc = j->h_tlb.ensure(tb + 16)) != SGK_OK) return rc;
+        if ((rc = j->h_hdo.ensure((nr + 1) * 4)) != SGK_OK) return rc;
+        if ((rc = j->h_tlo.ensure((nr + 1) * 4)) != SGK_OK) return rc;
+        uint32_t *ho = j->h_hdo.as<uint32_t>(), *to = j->h_tlo.as<uint32_t>();
+        uint32_t h = 0, t = 0;
+        for (size_t r = 0; r < nr; ++r) {
+            const uint32_t hl = frh[r], tl = fro[r + 1] - fro[r] - hl;
+            ho[r] = h;
+            to[r] = t;
+            if (hl) memcpy(j->h_hdb.as<uint8_t>() + h, frb + fro[r], hl);
+            if (tl) memcpy(j->h_tlb.as<uint8_t>() + t, frb + fro[r] + hl, tl);
+            h += hl;
+            t += tl;
+        }
+        ho[nr] = h;
+        to[nr] = t;
+        if ((rc = h2d(j->d_hdb, j->h_hdb, hb, st)) != SGK_OK) return rc;
+        if ((rc = h2d(j->d_tlb, j->h_tlb, tb, st)) != SGK_OK) return rc;
+        if ((rc = h2d(j->d_hdo, j->h_hdo, (nr + 1) * 4, st)) != SGK_OK) return rc;
+        if ((rc = h2d(j->d_tlo, j->h_tlo, (nr + 1) * 4, st)) != SGK_OK) return rc;
+    }
+    j->tws_bytes = sgk_slow5_text_workspace_bytes(j->n_reads, j->n_samples);
+    if ((rc = j->d_tws.ensure(j->tws_bytes)) != SGK_OK) return rc;
+    if ((rc = j->d_roffs.ensure((nr + 1) * 8)) != SGK_OK) return rc;
+    j->text_view = *view;
+    const sgk_text_ids_t heads = {j->d_hdb.as<uint8_t>(), j->d_hdo.as<uint32_t>()};
+    const sgk_text_ids_t tails = {j->d_tlb.as<uint8_t>(), j->d_tlo.as<uint32_t>()};
+    rc = sgk_slow5_text_measure(view->samples, view->offsets, view->lengths, j->n_reads, records ? &heads : nullptr,
+                                records ? &tails : nullptr, j->d_roffs.as<uint64_t>(), j->d_tws.p, j->tws_bytes, st);
     if (rc != SGK_OK) return rc;
     if ((rc = d2h(j->h_roffs, j->d_roffs, (nr + 1) * 8, st)) != SGK_OK) return rc;
     j->text_written = false;
@@ -792,8 +856,10 @@ int sgk_job_submit_qts(sgk_job_t *j, int bits, int method, int out_fmt_flags) {
     if (!j || !j->begun || j->submitted) return SGK_ERR_ARG;
     const bool records = (out_fmt_flags & SGK_QTS_RECORDS) != 0;
     const int out_fmt = out_fmt_flags & ~SGK_QTS_RECORDS;
-    if (out_fmt != SGK_SIGNAL_INT16 && out_fmt != SGK_SIGNAL_SVBZD) return SGK_ERR_ARG;
-    if (j->fmt == SGK_SIGNAL_TEXT) return SGK_ERR_ARG;  // rewriting text records is not part of qts here
+    if (out_fmt != SGK_SIGNAL_INT16 && out_fmt != SGK_SIGNAL_SVBZD && out_fmt != SGK_SIGNAL_TEXT) return SGK_ERR_ARG;
+    // text in, bare int16 samples out stays refused (tests/test_gpu_slow5_cli.py pins it): that is the decoder alone,
+    // and no record of either container holds uncompressed samples next to text ones
+    if (j->fmt == SGK_SIGNAL_TEXT && out_fmt == SGK_SIGNAL_INT16 && !records) return SGK_ERR_ARG;
     if (records && !j->have_frames) return SGK_ERR_ARG;
     if (bits < 1 || bits > 15 || method < SGK_QTS_FLOOR || method > SGK_QTS_FILL_ONES) return SGK_ERR_ARG;
     SGK_HIP_TRY(hipSetDevice(j->device));
@@ -803,6 +869,10 @@ int sgk_job_submit_qts(sgk_job_t *j, int bits, int method, int out_fmt_flags) {
     hipStream_t st = j->st;
     int rc;
     if (nr == 0) {
+        if (out_fmt == SGK_SIGNAL_TEXT) {
+            if ((rc = j->h_roffs.ensure(8)) != SGK_OK) return rc;
+            j->h_roffs.as<uint64_t>()[0] = 0;
+        }
         j->submitted = true;
         return SGK_OK;
     }
@@ -810,7 +880,9 @@ int sgk_job_submit_qts(sgk_job_t *j, int bits, int method, int out_fmt_flags) {
     if ((rc = job_upload(j, &view)) != SGK_OK) return rc;
     int16_t *smp = j->d_samples.as<int16_t>();
     if ((rc = sgk_qts(smp, view.offsets, view.lengths, j->n_reads, j->max_len, bits, method, st)) != SGK_OK) return rc;
-    if (out_fmt == SGK_SIGNAL_INT16) {
+    if (out_fmt == SGK_SIGNAL_TEXT) {
+        if ((rc = job_qts_text_submit(j, &view, records)) != SGK_OK) return rc;
+    } else if (out_fmt == SGK_SIGNAL_INT16) {
         if (records) {
             if ((rc = job_qts_records(j, view, false)) != SGK_OK) return rc;
         } else if ((rc = d2h(j->h_out[0], j->d_samples, j->n_samples * sizeof(int16_t), st)) != SGK_OK) return rc;
@@ -874,7 +946,8 @@ int sgk_job_wait(sgk_job_t *j) {
         for (uint32_t r = 0; r < j->n_reads; ++r)
             if (ds[r] != 0) return SGK_ERR_FORMAT;
     }
-    if ((j->flags & SGK_JOB_TEXT) && j->tool != SGK_TOOL_QTS) {
+    const bool qts_text = j->tool == SGK_TOOL_QTS && (j->flags & ~SGK_QTS_RECORDS) == SGK_SIGNAL_TEXT;
+    if (((j->flags & SGK_JOB_TEXT) && j->tool != SGK_TOOL_QTS) || qts_text) {
         const int rc = job_text_fetch(j);
         if (rc != SGK_OK) return rc;
     } else if (j->tool == SGK_TOOL_EVENT || j->tool == SGK_TOOL_JNN) {
@@ -896,7 +969,7 @@ int sgk_job_wait(sgk_job_t *j) {
         if ((rc = d2h(j->h_out[0], j->d_out[0], (size_t)total, j->st)) != SGK_OK) return rc;
         SGK_HIP_TRY(hipStreamSynchronize(j->st));
     }
-    if (j->tool == SGK_TOOL_QTS && (j->flags & SGK_QTS_RECORDS)) {
+    if (j->tool == SGK_TOOL_QTS && (j->flags & SGK_QTS_RECORDS) && !qts_text) {
         const uint64_t total = j->h_zdoffs.as<uint64_t>()[j->n_reads];
         int rc;
         if ((rc = d2h(j->h_zdense, j->d_zdense, (size_t)total, j->st)) != SGK_OK) return rc;
@@ -921,7 +994,8 @@ uint32_t sgk_job_long_declined(const sgk_job_t *j) { return j ? j->long_declined
 
 int sgk_job_text(const sgk_job_t *j, sgk_job_text_t *out) {
     if (!j || !out) return SGK_ERR_ARG;
-    if (!(j->flags & SGK_JOB_TEXT) || (j->tool != SGK_TOOL_PA && j->tool != SGK_TOOL_EVENT)) return SGK_ERR_ARG;
+    const bool qts_text = j->tool == SGK_TOOL_QTS && (j->flags & ~SGK_QTS_RECORDS) == SGK_SIGNAL_TEXT;
+    if (!qts_text && (!(j->flags & SGK_JOB_TEXT) || (j->tool != SGK_TOOL_PA && j->tool != SGK_TOOL_EVENT))) return SGK_ERR_ARG;
     out->text = j->h_text.as<uint8_t>();
     out->row_offsets = j->h_roffs.as<uint64_t>();
     out->n_bytes = j->n_reads ? j->text_bytes : 0;
@@ -972,6 +1046,7 @@ int sgk_job_output(const sgk_job_t *j, sgk_job_output_t *out) {
             out->prefix = j->h_out[0].as<sgk_prefix_rec_t>();
             break;
         case SGK_TOOL_QTS:
+            if ((j->flags & ~SGK_QTS_RECORDS) == SGK_SIGNAL_TEXT) break;  // the results are the rows: sgk_job_text
             if (j->flags & SGK_QTS_RECORDS) {
                 out->qts_records = j->h_zdense.as<uint8_t>();
                 out->qts_record_offsets = j->h_zdoffs.as<uint64_t>();

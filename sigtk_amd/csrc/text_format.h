@@ -91,6 +91,20 @@ SGK_TF int sgk_tf_i64(char *p, int64_t v) {
     return sgk_tf_u64(p, (uint64_t)v);
 }
 
+/* "%d" of an int16 (the raw_signal column of a text SLOW5 record): 1 to 6 bytes */
+#define SGK_TF_I16_MAX_BYTES 6 /* "-32768" */
+SGK_TF int sgk_tf_i16_len(int16_t v) {
+    const uint32_t a = v < 0 ? (uint32_t)(-(int32_t)v) : (uint32_t)v;
+    return (v < 0) + 1 + (a >= 10u) + (a >= 100u) + (a >= 1000u) + (a >= 10000u);
+}
+/* writes sgk_tf_i16_len(v) bytes at p and returns that count */
+SGK_TF int sgk_tf_i16(char *p, int16_t v) {
+    const int neg = v < 0, n = sgk_tf_i16_len(v);
+    if (neg) *p = '-';
+    sgk_tf_digits(p + neg, neg ? (uint32_t)(-(int32_t)v) : (uint32_t)v, n - neg);
+    return n;
+}
+
 SGK_TF uint32_t sgk_tf_bits(float f) {
     uint32_t u;
     memcpy(&u, &f, 4);

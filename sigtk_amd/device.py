@@ -315,6 +315,69 @@ def sigtext_decode(texts, counts, device: torch.device):
     return reads, status
 
 
+class Slow5TextWriter:
+    """sgk_slow5_text_measure + sgk_slow5_text_write over one resident batch, in the manner of TextWriter: row r is
+    heads[r] | the samples of read r as decimal numbers joined by ',' | tails[r] (heads / tails: one bytes object per
+    read, or None for all empty).  measure() and write() only enqueue; status() synchronises.  ws_bytes overrides the
+    workspace size (tests)."""
+
+    def __init__(self, b: DeviceReads, heads=None, tails=None, ws_bytes: Optional[int] = None):
+        L = api.load_library()
+        dev = b.samples.device
+        self.b = b
+        self._keep = []
+
+        def ids(parts):
+            if parts is None:
+                return None
+            raw = [bytes(p) for p in parts]
+            assert len(raw) == b.n_reads
+            offs = np.zeros(b.n_reads + 1, dtype=np.int64)
+            np.cumsum([len(p) for p in raw], out=offs[1:])
+            d_bytes = torch.from_numpy(np.frombuffer(b"".join(raw) + b"\0" * 16, dtype=np.uint8).copy()).to(dev)
+            d_offs = torch.from_numpy(offs.astype(np.uint32).view(np.int32)).to(dev)
+            self._keep += [d_bytes, d_offs]
+            return api.TextIds(_ptr(d_bytes), _ptr(d_offs))
+
+        self.heads, self.tails = ids(heads), ids(tails)
+        self.ws_bytes = int(L.sgk_slow5_text_workspace_bytes(b.n_reads, b.n_samples)) if ws_bytes is None else int(ws_bytes)
+        self.ws = torch.zeros(self.ws_bytes + 16, dtype=torch.uint8, device=dev)
+        self.row_offsets = torch.zeros(b.n_reads + 1, dtype=torch.int64, device=dev)
+
+    def _rows(self):
+        b = self.b
+        return (_ptr(b.samples), _ptr(b.offsets), _ptr(b.lengths), b.n_reads,
+                C.byref(self.heads) if self.heads is not None else None, C.byref(self.tails) if self.tails is not None else None)
+
+    def measure(self) -> int:
+        return int(api.load_library().sgk_slow5_text_measure(*self._rows(), _ptr(self.row_offsets), _ptr(self.ws),
+                                                             self.ws_bytes, _stream_ptr()))
+
+    def write(self, text: torch.Tensor, capacity: Optional[int] = None) -> int:
+        """text: uint8 tensor (or a view of one starting at any byte); capacity defaults to its length"""
+        return int(api.load_library().sgk_slow5_text_write(*self._rows(), _ptr(text),
+                                                           int(text.numel() if capacity is None else capacity),
+                                                           _ptr(self.ws), self.ws_bytes, _stream_ptr()))
+
+    def status(self):
+        """-> (return code of sgk_text_status: 0, api.SGK_ERR_CAPACITY or api.SGK_ERR_WORKSPACE; api.TextStatus); synchronises"""
+        torch.cuda.synchronize()
+        st = api.TextStatus()
+        return int(api.load_library().sgk_text_status(_ptr(self.ws), C.byref(st))), st
+
+    def run(self) -> bytes:
+        """measure, allocate exactly, write -> the rows as bytes (and self.row_offsets_host)"""
+        api.check(self.measure(), "sgk_slow5_text_measure")
+        torch.cuda.synchronize()
+        self.row_offsets_host = self.row_offsets.cpu().numpy().astype(np.uint64)
+        total = int(self.row_offsets_host[-1])
+        text = torch.zeros(max(total, 1), dtype=torch.uint8, device=self.b.samples.device)
+        api.check(self.write(text, total), "sgk_slow5_text_write")
+        rc, _ = self.status()
+        api.check(rc, "sgk_slow5_text_write")
+        return text[:total].cpu().numpy().tobytes()
+
+
 # ---------------------------------------------------------------------- qts + svb-zd encode (device API)
 
 def qts(b: DeviceReads, bits: int, method: int) -> None:

@@ -142,6 +142,51 @@ static int s5_parse_line(const uint8_t *p, uint64_t n, b5_view_t *out, int id_on
     return 0;
 }
 
+/* a double column as slow5lib writes it (slow5_double_to_str, slow5_misc.c:379-406): "%f", then the trailing zeros go,
+ * the point with them when nothing is left behind it, and "-0" becomes "0".  At most 72 bytes for a value s5_double took
+ * (fewer than 64 characters in: below 1e63). */
+static size_t s5_double_str(char *dst, size_t cap, double x) {
+    int n = snprintf(dst, cap, "%f", x);
+    if (n < 0 || (size_t)n >= cap) return 0;
+    if (memchr(dst, '.', (size_t)n)) {   /* (always, for a finite value) */
+        while (n > 1 && dst[n - 1] == '0') n--;
+        if (n > 1 && dst[n - 1] == '.') n--;
+    }
+    if (n == 2 && dst[0] == '-' && dst[1] == '0') {
+        dst[0] = '0';
+        n = 1;
+    }
+    return (size_t)n;
+}
+
+int64_t b5_s5_qts_head(const b5_view_t *v, uint8_t **buf, uint64_t *cap) {
+    const uint8_t *p = v->rec;
+    const uint64_t n = v->signal_offset;   /* the seven columns in front of raw_signal, each with its tab */
+    uint64_t col2 = 0, col6 = 0;
+    int tabs = 0;
+    for (uint64_t i = 0; i < n; i++)
+        if (p[i] == '\t') {
+            tabs++;
+            if (tabs == 2) col2 = i + 1;
+            if (tabs == 6) col6 = i + 1;
+        }
+    if (tabs != 7 || p[n - 1] != '\t') return B5_ERR_FORMAT;
+    const double d[4] = {v->digitisation, v->offset, v->range, v->sampling_rate};
+    if (grow(buf, cap, col2 + 4 * 80 + (n - col6))) return B5_ERR_MEM;
+    uint8_t *o = *buf;
+    memcpy(o, p, (size_t)col2);
+    o += col2;
+    for (int k = 0; k < 4; k++) {
+        const size_t m = s5_double_str((char *)o, 79, d[k]);
+        if (m == 0) return B5_ERR_FORMAT;
+        o += m;
+        *o++ = '\t';
+    }
+    memcpy(o, p + col6, (size_t)(n - col6));
+    o += n - col6;
+    return (int64_t)(o - *buf);
+}
+
 static int has_ext(const char *path, const char *ext) {
     const size_t n = strlen(path), e = strlen(ext);
     return n >= e && strcmp(path + n - e, ext) == 0;

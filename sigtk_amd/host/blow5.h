@@ -111,6 +111,13 @@ int b5_parse_raw(const b5_file_t *f, const uint8_t *raw, uint64_t size, uint8_t 
  * frame declares (the inflated length of the record, if the frame keeps its word) and 0 for a zlib record. */
 int b5_parse_head(const b5_file_t *f, const uint8_t *raw, uint64_t size, uint8_t **scratch, uint64_t *scratch_cap,
                   b5_view_t *out);
+/* Text files, `qts`: the line of a parsed record (b5_parse_raw's view) up to its raw_signal column as the reference
+ * writes it back, into *buf (realloc'd as needed): read_id, read_group and len_raw_signal as they stand, digitisation,
+ * offset, range and sampling_rate re-printed the way slow5lib prints a double ("%f" without its trailing zeros and
+ * without the point when nothing follows it, "-0" as "0"; slow5_misc.c:379-406), every column with its tab.  What
+ * follows the column -- v->rec + v->signal_offset + v->signal_bytes up to v->rec + v->rec_len, the auxiliary columns --
+ * is written back as it stands.  Returns the byte count, or a negative error.  Re-entrant. */
+int64_t b5_s5_qts_head(const b5_view_t *v, uint8_t **buf, uint64_t *cap);
 /* bytes of a record's auxiliary fields when all of them are primitive (fixed size), else -1 (an array field, an unknown
  * type): with a fixed size the inflated length of a record follows from its head */
 int64_t b5_aux_fixed_bytes(const b5_file_t *f);

@@ -13,7 +13,8 @@
  * rows of finished batches on a pool of threads (exact fast number formatting, fmt.h) and emits them
  * in file order.  Whole batches are the multi-GPU sharding unit: no collective.
  * Text SLOW5 files (.slow5) go the same way: a record is a line, its signal column is handed to the GPU as text and
- * parsed there (k_sigtext_decode), or by the pool with --host-decode.
+ * parsed there (k_sigtext_decode), or by the pool with --host-decode; `qts a.slow5 -o q.slow5` gets its lines back from
+ * the GPU with the new column written there (k_slow5_text_write) and copies them out.
  * Extra options: --gpus N, --batch-samples M, -t/--threads T, --host-decode.
  */
 #include <getopt.h>
@@ -303,6 +304,7 @@ typedef struct {
     uint64_t scratch_cap;
     b5_view_t v;
     uint32_t room;              /* zrec: what the inflated record may take (load_parse) */
+    uint64_t head_len;          /* qts on a text file: bytes of the line's head as it is written back, in `scratch` (load_parse) */
     int err;
 } lrec_t;
 
@@ -391,6 +393,7 @@ typedef struct {
     /* qts */
     int q_bits, q_method;
     int gpu_deflate;  /* qts --gpu-deflate on a file with compressed records: records assembled and deflated on the GPU */
+    int q_text;       /* qts on a text file: the lines are written on the GPU around the new signal column */
     FILE *out_fp;    /* rows / records go here (stdout except for qts) */
     pool_t *load_pool; /* the loader's worker pool (the writer creates its own) */
     struct batch *pool; /* all batch slots; [0, n_created) have a job */
@@ -440,6 +443,11 @@ static void load_parse(void *ctx_, uint32_t i, int tid) {
     const uint8_t *raw = r->raw_ptr ? r->raw_ptr : c->b->raw + r->raw_off;
     if (!c->zrec) {
         r->err = b5_parse_raw(P->f, raw, r->raw_size, &r->scratch, &r->scratch_cap, &r->v);
+        if (!r->err && P->q_text) {   /* the line up to its signal column, as it goes back out (the parser left scratch alone) */
+            const int64_t h = b5_s5_qts_head(&r->v, &r->scratch, &r->scratch_cap);
+            if (h < 0) r->err = (int)h;
+            else r->head_len = (uint64_t)h;
+        }
         return;
     }
     /* zrec: the head only (id, scaling, sizes: a few hundred inflated bytes); the record itself is inflated on the GPU */
@@ -474,7 +482,14 @@ static void load_stage(void *ctx_, uint32_t i, int tid) {
     } else {
         memcpy(b->in.samples + b->in.offsets[i], r->v.signal, r->v.signal_bytes);
     }
-    if (c->P->gpu_deflate) {   /* the record around its signal (batch_frames laid the frames out) */
+    if (c->P->q_text) {   /* the line around its signal column: the re-printed head, then what follows the column and the newline */
+        const uint8_t *tail = r->v.signal + r->v.signal_bytes;
+        const size_t tl = (size_t)(r->v.rec + r->v.rec_len - tail);
+        uint8_t *fr = b->fr_blob + b->fr_offs[i];
+        memcpy(fr, r->scratch, b->fr_heads[i]);
+        memcpy(fr + b->fr_heads[i], tail, tl);
+        fr[b->fr_heads[i] + tl] = '\n';
+    } else if (c->P->gpu_deflate) {   /* the record around its signal (batch_frames laid the frames out) */
         const uint8_t *tail = r->v.signal + r->v.signal_bytes;
         uint8_t *fr = b->fr_blob + b->fr_offs[i];
         memcpy(fr, r->v.rec, b->fr_heads[i]);
@@ -482,8 +497,8 @@ static void load_stage(void *ctx_, uint32_t i, int tid) {
     }
 }
 
-/* qts --gpu-deflate: where every record's frame goes (load_stage fills them) */
-static void batch_frames(batch_t *b) {
+/* qts --gpu-deflate, qts on a text file: where every record's frame goes (load_stage fills them) */
+static void batch_frames(batch_t *b, int text) {
     if ((uint64_t)b->n + 1 > b->fr_offs_cap) {
         b->fr_offs_cap = (uint64_t)b->n + 1;
         b->fr_offs = (uint32_t *)realloc(b->fr_offs, sizeof(uint32_t) * b->fr_offs_cap);
@@ -493,10 +508,11 @@ static void batch_frames(batch_t *b) {
     uint64_t o = 0;
     for (uint32_t i = 0; i < b->n; i++) {
         const b5_view_t *v = &b->recs[i].v;
-        const uint64_t head = (uint64_t)(v->signal - v->rec) - 8; /* up to the u64 len_raw_signal */
+        /* up to the u64 len_raw_signal; text: the head load_parse made, and a newline behind the tail */
+        const uint64_t head = text ? b->recs[i].head_len : (uint64_t)(v->signal - v->rec) - 8;
         b->fr_offs[i] = (uint32_t)o;
         b->fr_heads[i] = (uint32_t)head;
-        o += head + (uint64_t)(v->rec + v->rec_len - (v->signal + v->signal_bytes));
+        o += head + (uint64_t)(v->rec + v->rec_len - (v->signal + v->signal_bytes)) + (text ? 1u : 0u);
         if (o > 0xffffffffull) {
             ERROR("qts", "%s", "the records of one batch hold more than 4 GB around their signals: use a smaller --batch-samples");
             die_now();
@@ -554,10 +570,10 @@ static void batch_submit(pipe_t *P, batch_t *b) {
         flags |= SGK_JOB_TEXT;
     }
     if (P->mode == MODE_QTS) {
-        if (P->gpu_deflate && (rc = sgk_job_set_record_frames(b->job, b->fr_blob, b->fr_offs, b->fr_heads)) != SGK_OK)
+        if ((P->gpu_deflate || P->q_text) && (rc = sgk_job_set_record_frames(b->job, b->fr_blob, b->fr_offs, b->fr_heads)) != SGK_OK)
             gpu_fail("sgk_job_set_record_frames", rc);
-        rc = sgk_job_submit_qts(b->job, P->q_bits, P->q_method,
-                                (P->f->signal_press == 1 ? SGK_SIGNAL_SVBZD : SGK_SIGNAL_INT16) | (P->gpu_deflate ? SGK_QTS_RECORDS : 0));
+        const int out_fmt = P->q_text ? SGK_SIGNAL_TEXT : (P->f->signal_press == 1 ? SGK_SIGNAL_SVBZD : SGK_SIGNAL_INT16);
+        rc = sgk_job_submit_qts(b->job, P->q_bits, P->q_method, out_fmt | (P->gpu_deflate || P->q_text ? SGK_QTS_RECORDS : 0));
     } else
         rc = sgk_job_submit(b->job, tool, P->opt.rna, P->opt.pore, flags);
     if (rc != SGK_OK) gpu_fail("sgk_job_submit", rc);
@@ -596,7 +612,7 @@ static void batch_launch(pipe_t *P, batch_t *b) {
     if (b->zrec) rc = sgk_job_begin_zrec_aux(b->job, b->n, P->f->record_press == 2 ? SGK_RECORD_ZSTD : SGK_RECORD_ZLIB, b->lengths, b->blob_bytes, b->sig_off, b->sig_len, b->room, P->aux_tab, P->n_aux, &b->in);
     else rc = sgk_job_begin(b->job, b->n, b->lengths, b->sigtext ? SGK_SIGNAL_TEXT : (b->svb ? SGK_SIGNAL_SVBZD : SGK_SIGNAL_INT16), b->blob_bytes, &b->in);
     if (rc != SGK_OK) gpu_fail("sgk_job_begin", rc);
-    if (P->gpu_deflate) batch_frames(b);
+    if (P->gpu_deflate || P->q_text) batch_frames(b, P->q_text);
     pfor(P->load_pool, b->n, load_stage, &c);
     for (uint32_t i = 0; i < b->n; i++) {
         if (b->recs[i].err) {
@@ -937,8 +953,8 @@ static void *writer_main(void *arg) {
         if (rc != SGK_OK) gpu_fail("sgk_job_output", rc);
         double t1 = realtime();
         P->t_wait += t1 - t0;
-        if (P->gpu_text) {
-            /* the batch's rows arrived as text: one buffered write, nothing to format */
+        if (P->gpu_text || P->q_text) {
+            /* the batch's rows (qts on a text file: its lines) arrived as text: one buffered write, nothing to format */
             sgk_job_text_t tx;
             rc = sgk_job_text(b->job, &tx);
             if (rc != SGK_OK) gpu_fail("sgk_job_text", rc);
@@ -1350,7 +1366,11 @@ static int cmain(int argc, char *argv[], const char *mode_s) {
  * input's header block and compression settings verbatim (the reference re-serialises the header through slow5lib
  * and always writes zlib + svb-zd); records carry the same fields, auxiliary data included, with the quantised
  * signal -- quantised and re-encoded (svb-zd) on the GPU, deflated on the host thread pool, or with --gpu-deflate
- * assembled and deflated on the GPU as well (Z_RLE-like streams of csrc/deflate_kernels.hip: other bytes, same records). */
+ * assembled and deflated on the GPU as well (Z_RLE-like streams of csrc/deflate_kernels.hip: other bytes, same records).
+ * A text SLOW5 file is written back as a text SLOW5 file (both through slow5lib by extension in the reference,
+ * src/qts.c:101-108): the header as it stands, every line with its four doubles re-printed as slow5lib prints them
+ * (b5_s5_qts_head), the quantised column written on the GPU between the line's head and its auxiliary columns
+ * (SGK_SIGNAL_TEXT | SGK_QTS_RECORDS).  Text in with BLOW5 out, or the reverse, is refused. */
 static struct option qts_long_options[] = {
     {"verbose", required_argument, 0, 'v'}, {"help", no_argument, 0, 'h'},   {"version", no_argument, 0, 'V'},
     {"output", required_argument, 0, 'o'},  {"bits", required_argument, 0, 'b'}, {"method", required_argument, 0, 'm'},
@@ -1394,7 +1414,7 @@ static int qtsmain(int argc, char *argv[]) {
         }
     }
     if (argc - optind != 1 || fp_help == stdout) {
-        fprintf(fp_help, "Usage: sigtk qts a.blow5 -o out.blow5\n");
+        fprintf(fp_help, "Usage: sigtk qts a.blow5 -o out.blow5   (or a.slow5 -o out.slow5: text in, text out)\n");
         fprintf(fp_help, "\nbasic options:\n");
         fprintf(fp_help, "   -h                            help\n");
         fprintf(fp_help, "   -o FILE                       output file\n");
@@ -1415,19 +1435,22 @@ static int qtsmain(int argc, char *argv[]) {
         fprintf(stderr, "Unknown method for -m. Available options are floor,round,fill-ones.\n");
         die_now();
     }
-    {   /* records are rewritten byte for byte around the new signal: text records (their auxiliary columns) are not */
-        const size_t ni = strlen(argv[optind]), no = strlen(out_fn);
-        if ((ni >= 6 && strcmp(argv[optind] + ni - 6, ".slow5") == 0) || (no >= 6 && strcmp(out_fn + no - 6, ".slow5") == 0)) {
-            fprintf(stderr, "Error: qts on text SLOW5 files is not supported: use BLOW5 for the input and the output\n");
-            die_now();
-        }
+    /* Records are rewritten around the new signal in the container they came in: BLOW5 records byte for byte, text lines
+     * with their auxiliary columns as they stand.  Going from one container to the other would mean re-serialising the
+     * header and every typed auxiliary field: refused, whichever way the names or the content say it is mixed. */
+    const size_t ni = strlen(argv[optind]), no = strlen(out_fn);
+    const int in_text = ni >= 6 && strcmp(argv[optind] + ni - 6, ".slow5") == 0;
+    const int out_text = no >= 6 && strcmp(out_fn + no - 6, ".slow5") == 0;
+    if (in_text != out_text) {
+        fprintf(stderr, "Error: qts on text SLOW5 files is not supported: use BLOW5 for the input and the output\n");
+        die_now();
     }
     b5_file_t *f = b5_open(argv[optind]);
     if (!f) {
         fprintf(stderr, "Error in opening file\n");
         die_now();
     }
-    if (f->text) {
+    if ((f->text != 0) != out_text) {   /* (text under a name that does not say so) */
         fprintf(stderr, "Error: qts on text SLOW5 files is not supported: use BLOW5 for the input and the output\n");
         die_now();
     }
@@ -1436,8 +1459,19 @@ static int qtsmain(int argc, char *argv[]) {
         fprintf(stderr, "Error opening file!\n");
         die_now();
     }
+    if (f->text) {
+        /* the header is everything in front of the first record, as it stands */
+        const size_t hb = (size_t)f->first_rec;
+        uint8_t *h = (uint8_t *)malloc(hb ? hb : 1);
+        if (!h) die_mem();
+        if (fseek(f->fp, 0, SEEK_SET) != 0 || fread(h, 1, hb, f->fp) != hb || fwrite(h, 1, hb, out) != hb ||
+            fseek(f->fp, (long)f->first_rec, SEEK_SET) != 0) {
+            fprintf(stderr, "Error writing header!\n");
+            die_now();
+        }
+        free(h);
+    } else {
     /* header block: the fixed 68 bytes and the header text, as they are */
-    {
         const size_t hb = 68 + (size_t)f->hdr_size;
         uint8_t *h = (uint8_t *)malloc(hb);
         if (!h) die_mem();
@@ -1468,10 +1502,11 @@ static int qtsmain(int argc, char *argv[]) {
     P.q_bits = b;
     P.q_method = q_method;
     P.gpu_deflate = gpu_deflate && f->record_press != 0;   /* (uncompressed records: nothing to deflate, the flag changes nothing) */
+    P.q_text = f->text;   /* lines out: no record sizes and no end-of-file marker */
     P.out_fp = out;
-    P.limit_bytes = batch_samples;
+    P.limit_bytes = f->text ? batch_samples * 4 : batch_samples;   /* (on-disk bytes: four to five per sample in a text file) */
     run_pipeline(&P, n_gpus, t_init);
-    if (fwrite("5WOLB", 1, 5, out) != 5 || fclose(out) != 0) {
+    if ((!f->text && fwrite("5WOLB", 1, 5, out) != 5) || fclose(out) != 0) {
         fprintf(stderr, "Error writing record!\n");
         die_now();
     }
@@ -1772,6 +1807,60 @@ static int textcheckmain(int argc, char *argv[]) {
 
 /* ------------------------------------------------------------------ main (src/main.c:49-123) */
 
+/* hidden helper for tests, no GPU: _qtsframes [FILE].  For every record of the text SLOW5 file FILE, what `qts` uploads
+ * around its signal column (b5_s5_qts_head and the bytes behind the column with the newline), as two lines
+ * "H <bytes> <hex>" and "T <bytes> <hex>"; a record the reader refuses ends the listing as it ends the subtools.  Then the
+ * int16 writer of csrc/text_format.h over all 65 536 values against snprintf("%d"), the bytes and the length-only form. */
+static void qtsframes_hex(char tag, const uint8_t *p, uint64_t n) {
+    printf("%c %lu ", tag, (unsigned long)n);
+    for (uint64_t i = 0; i < n; i++) printf("%02x", p[i]);
+    printf("\n");
+}
+static int qtsframesmain(int argc, char *argv[]) {
+    int ret = 0;
+    if (argc > 1) {
+        b5_file_t *f = b5_open(argv[1]);
+        if (!f || !f->text) {
+            fprintf(stderr, "Error in opening file\n");
+            return 1;
+        }
+        uint8_t *raw = NULL, *head = NULL, *scratch = NULL;
+        uint64_t raw_len = 0, raw_cap = 0, head_cap = 0, scratch_cap = 0, size = 0;
+        int rc;
+        while ((rc = b5_next_raw(f, &raw, &raw_len, &raw_cap, &size)) >= 0) {
+            b5_view_t v;
+            rc = b5_parse_raw(f, raw, size, &scratch, &scratch_cap, &v);
+            raw_len = 0;
+            if (rc < 0) break;
+            const int64_t h = b5_s5_qts_head(&v, &head, &head_cap);
+            if (h < 0) {
+                rc = (int)h;
+                break;
+            }
+            const uint8_t *tail = v.signal + v.signal_bytes;
+            qtsframes_hex('H', head, (uint64_t)h);
+            printf("T %lu ", (unsigned long)(v.rec + v.rec_len - tail) + 1);
+            for (const uint8_t *q = tail; q < v.rec + v.rec_len; q++) printf("%02x", *q);
+            printf("0a\n");
+        }
+        if (rc != B5_EOF) {
+            fprintf(stderr, "Error in slow5_get_next. Error code %d\n", rc);
+            ret = 1;
+        }
+        free(raw); free(head); free(scratch);
+        b5_close(f);
+    }
+    uint64_t bad = 0;
+    for (int32_t x = -32768; x <= 32767; x++) {
+        char a[16], w[16];
+        memset(a, '#', sizeof a);
+        const int n = sgk_tf_i16(a, (int16_t)x), m = snprintf(w, sizeof w, "%d", x);
+        if (n != m || n != sgk_tf_i16_len((int16_t)x) || memcmp(a, w, (size_t)m) != 0 || a[n] != '#') bad++;
+    }
+    printf("i16 checked 65536 values, %lu mismatches\n", (unsigned long)bad);
+    return ret || bad ? 1 : 0;
+}
+
 static void print_usage(FILE *fp) {
     fprintf(fp, "Usage: sigtk <command> [options]\n\n");
     fprintf(fp, "command:\n");
@@ -1816,6 +1905,8 @@ int main(int argc, char *argv[]) {
         return fmtcheckmain(argc - 1, argv + 1);
     } else if (strcmp(argv[1], "_textcheck") == 0) {
         return textcheckmain(argc - 1, argv + 1);
+    } else if (strcmp(argv[1], "_qtsframes") == 0) {
+        return qtsframesmain(argc - 1, argv + 1);
     } else if (strcmp(argv[1], "--version") == 0 || strcmp(argv[1], "-V") == 0) {
         fprintf(stdout, "sigtk %s\n", SIGTK_VERSION);
         exit(EXIT_SUCCESS);
