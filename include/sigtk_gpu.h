@@ -76,7 +76,8 @@ extern "C" {
  *        sgk_aux_field_t, sgk_zrec_tail_check and sgk_job_begin_zrec_aux (records with variable-length auxiliary fields);
  *        sgk_deflate, sgk_deflate_bound, sgk_deflate_block_bytes, sgk_job_set_record_frames and SGK_QTS_RECORDS with the
  *        qts_record* fields at the end of sgk_job_output_t (`qts --gpu-deflate`: records deflated on the GPU);
- *        sgk_slow5_text_* and SGK_SIGNAL_TEXT as input and output format of sgk_job_submit_qts (`qts` on text SLOW5). */
+ *        sgk_slow5_text_* and SGK_SIGNAL_TEXT as input and output format of sgk_job_submit_qts (`qts` on text SLOW5);
+ *        SGK_QTS_ZREC_FRAMES (`qts --gpu-inflate`: the frames of the record mode taken from the records inflated on the GPU). */
 #define SGK_VERSION_STRING "0.2.3"
 
 /* ---- error codes --------------------------------------------------------------- */
@@ -827,7 +828,8 @@ typedef struct sgk_job_output {
     const sgk_ent_hist_t *ent;            /* ent: one record per read */
     uint16_t *ent_over_raw, *ent_over_delta; /* ent: host copies of the overflow lists (NULL if all empty) */
     /* qts with SGK_QTS_RECORDS: the rewritten records as zlib streams (record r at qts_records + qts_record_offsets[r],
-     * qts_record_lengths[r] bytes; qts_record_status[r]: sgk_deflate's status), else NULL.  The blobs / samples above
+     * qts_record_lengths[r] bytes; qts_record_status[r]: sgk_deflate's status, or with SGK_QTS_ZREC_FRAMES 2 and length 0
+     * for a record that did not inflate or fill its fields), else NULL.  The blobs / samples above
      * are NULL then: the signal is not downloaded uncompressed */
     const uint8_t *qts_records;
     const uint64_t *qts_record_offsets;
@@ -890,6 +892,15 @@ int sgk_job_submit_qts(sgk_job_t *job, int bits, int method, int out_signal_form
 #define SGK_QTS_RECORDS 0x100
 int sgk_job_set_record_frames(sgk_job_t *job, const uint8_t *bytes, const uint32_t *frame_offsets /* n + 1 */,
                               const uint32_t *head_lengths /* n */);
+/* Record mode without staged frames (additive to 0.2.3): or'ed into out_signal_format together with SGK_QTS_RECORDS, for a
+ * batch begun with sgk_job_begin_zrec / _format / _aux and SGK_SIGNAL_SVBZD out (anything else: SGK_ERR_ARG, as is a
+ * sig_offset below 8).  Record r's frame is read where the record was inflated on the device: its head is bytes
+ * [0, sig_offset[r] - 8), its tail bytes [sig_offset[r] + sig_bytes[r], what the record inflated to); no
+ * sgk_job_set_record_frames is needed and the records never leave the device between the file's bytes and the new zlib
+ * streams.  A record that did not inflate, or whose auxiliary fields do not fill it, is not read from: its
+ * qts_record_status is 2 and its qts_record_lengths 0 (1 stays sgk_deflate's "no room"); sgk_job_wait returns
+ * SGK_ERR_FORMAT with decode_status as for every SGK_SIGNAL_ZREC batch, and the other records' streams are valid. */
+#define SGK_QTS_ZREC_FRAMES 0x200
 /* SGK_ERR_FORMAT if a blob (a text column) did not decode, SGK_ERR_CAPACITY on event-slot overflow */
 int sgk_job_wait(sgk_job_t *job);
 /* valid after sgk_job_wait until the job's next sgk_job_begin */

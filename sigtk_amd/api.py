@@ -257,6 +257,7 @@ def aux_table(fields):
     return tab
 JOB_EVENTS_COMPACT = 1
 QTS_RECORDS = 0x100      # launch_qts(records=True): or'ed into the output signal format of sgk_job_submit_qts
+QTS_ZREC_FRAMES = 0x200  # launch_qts(records=True, zrec_frames=True): the frames are the records inflated on the GPU
 JOB_TEXT = 4             # pa / event: the rows are written on the device; wait() returns "text" and "row_offsets"
 TEXT_PA, TEXT_EVENT, TEXT_EVENT_COMPACT = 0, 1, 2
 JOB_EVENTS_LENGTHS = 2   # only the lengths come back; the starts are their running sums (events are contiguous from 0)
@@ -857,9 +858,13 @@ class Job:
         check(self.L.sgk_job_set_record_frames(self.h, blob if blob else None, offs.ctypes.data,
                                                heads.ctypes.data if len(raw) else None), "sgk_job_set_record_frames")
 
-    def launch_qts(self, bits: int, method: int, out_svb: bool, records: bool = False, out_text: bool = False):
+    def launch_qts(self, bits: int, method: int, out_svb: bool, records: bool = False, out_text: bool = False,
+                   zrec_frames: bool = False):
         """records=True (after set_record_frames): the records are assembled and deflated on the GPU; wait() then
         returns res["records"] (zlib streams) and res["record_status"] instead of the blobs / samples.
+        zrec_frames=True (SGK_QTS_ZREC_FRAMES; with records=True on a stage_zrec batch, svb-zd out): no frames are staged,
+        head and tail of every record are read where the record was inflated on the GPU; a record that did not inflate
+        or fill its fields has record_status 2 and an empty stream (wait_rc() then output() for such a batch).
         out_text=True (SGK_SIGNAL_TEXT as the output format): the quantised signal as text SLOW5 columns written on the
         GPU; wait() returns res["text"] and res["row_offsets"] -- with records=True the rows are frame head | column |
         frame tail"""
@@ -870,7 +875,8 @@ class Job:
         self._qts_text = out_text
         check(self.L.sgk_job_submit_qts(self.h, bits, method,
                                         (SIGNAL_TEXT if out_text else SIGNAL_SVBZD if out_svb else SIGNAL_INT16) |
-                                        (QTS_RECORDS if records else 0)), "sgk_job_submit_qts")
+                                        (QTS_RECORDS if records else 0) | (QTS_ZREC_FRAMES if zrec_frames else 0)),
+              "sgk_job_submit_qts")
 
     def submit(self, tool: int, signals, dig, off, rng, rna: int = 0, pore: int = 0, flags: int = 0, counts=None, ids=None,
                text=False):
@@ -889,6 +895,11 @@ class Job:
     def wait(self):
         """-> dict of numpy results (per read lists for the variable-length outputs)"""
         check(self.L.sgk_job_wait(self.h), "sgk_job_wait")
+        return self.output()
+
+    def output(self):
+        """the results of the batch waited for last, as wait() returns them (after wait_rc(): what a batch that came
+        back SGK_ERR_FORMAT still holds, e.g. the sound records of launch_qts(zrec_frames=True))"""
         o = JobOutput()
         check(self.L.sgk_job_output(self.h, C.byref(o)), "sgk_job_output")
         n = o.n_reads

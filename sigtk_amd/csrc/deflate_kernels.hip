@@ -556,10 +556,17 @@ __global__ __launch_bounds__(64) void k_deflate(DefArgs a) {
 }
 
 // ---- qts record mode: head | u64 len_raw_signal | signal | tail of every read, behind each other in an arena
+// Head and tail are two sources of their own (base, 64-bit offset, length per record): the frames the host staged, where
+// the tail lies directly behind the head (k_qts_record_sizes), or the record as k_inflate / k_zstd left it in the job's
+// arena, where the old signal lies between them (k_qts_zrec_sizes).
 struct AsmArgs {
-    const uint8_t *frames;         // frame r: head_lengths[r] bytes of head, then the tail, at frames + frame_offsets[r]
-    const uint32_t *frame_offsets; // n + 1
+    const uint8_t *head_src;       // head r: head_lengths[r] bytes at head_src + head_offsets[r]
+    const uint64_t *head_offsets;  // n
     const uint32_t *head_lengths;  // n
+    const uint8_t *tail_src;       // tail r: tail_lengths[r] bytes at tail_src + tail_offsets[r]
+    const uint64_t *tail_offsets;  // n
+    const uint32_t *tail_lengths;  // n
+    const uint32_t *skip;          // n or null: non-zero: record r is not assembled (nothing of it is read or written)
     const uint8_t *signal;         // svb-zd blobs or int16 samples (bytes)
     const uint64_t *sig_offsets;   // n: offsets into signal, in units of sig_unit bytes
     const uint32_t *sig_counts;    // n: blob bytes / samples: the value of len_raw_signal
@@ -568,25 +575,80 @@ struct AsmArgs {
     const uint64_t *rec_offsets;   // n: where record r goes
     uint32_t n;
 };
+__device__ __forceinline__ uint32_t qts_deflate_cap(uint32_t len) {   // what k_deflate may need for len bytes
+    return len + 5u * (len ? (len + DEF_BLOCK - 1u) / DEF_BLOCK : 1u) + 6u;
+}
+// staged frames (frame r: head_lengths[r] bytes of head, then the tail, at frame_offsets[r]): the two sources,
 // rec_lengths[r] = frame + 8 + signal bytes; caps[r] = what k_deflate may need for it
-__global__ __launch_bounds__(256) void k_qts_record_sizes(const uint32_t *frame_offsets, const uint32_t *sig_counts, uint32_t sig_unit,
-                                                          uint32_t n, uint32_t *rec_lengths, uint32_t *caps) {
+__global__ __launch_bounds__(256) void k_qts_record_sizes(const uint32_t *frame_offsets, const uint32_t *head_lengths,
+                                                          const uint32_t *sig_counts, uint32_t sig_unit, uint32_t n,
+                                                          uint64_t *head_offsets, uint64_t *tail_offsets, uint32_t *tail_lengths,
+                                                          uint32_t *rec_lengths, uint32_t *caps) {
     const uint32_t r = blockIdx.x * 256u + threadIdx.x;
     if (r >= n) return;
-    const uint32_t len = frame_offsets[r + 1] - frame_offsets[r] + 8u + sig_counts[r] * sig_unit;
+    const uint32_t f0 = frame_offsets[r], flen = frame_offsets[r + 1] - f0, head = head_lengths[r];
+    head_offsets[r] = f0;
+    tail_offsets[r] = (uint64_t)f0 + head;
+    tail_lengths[r] = flen - head;
+    const uint32_t len = flen + 8u + sig_counts[r] * sig_unit;
     rec_lengths[r] = len;
-    caps[r] = len + 5u * (len ? (len + DEF_BLOCK - 1u) / DEF_BLOCK : 1u) + 6u;
+    caps[r] = qts_deflate_cap(len);
+}
+// The same for records inflated on the device (SGK_SIGNAL_ZREC): record r lies at rec_offsets[r] of the arena with room
+// rec_caps[r], its old svb-zd blob at sig_offsets[r] (arena offset) with sig_lengths[r] bytes; inflated_lengths[r] is what
+// it inflated to.  head = [0, blob - 8), tail = [blob end, inflated length).  A record whose inflate status or tail
+// status (null: the batch has no column table) is non-zero has an inflated length nobody vouches for -- 0, short of the
+// signal's end, or a word that lies behind the room: it gets length 0 everywhere and bad[r] = 2, as does one whose length
+// does not hold its head and signal or exceeds its room.  new_counts[r]: the bytes of the new blob.
+struct ZrecSizeArgs {
+    const uint64_t *rec_offsets;
+    const uint32_t *rec_caps, *inflated_lengths;
+    const uint64_t *sig_offsets;
+    const uint32_t *sig_lengths, *inflate_status, *tail_status, *new_counts;
+    uint32_t n;
+    uint64_t *head_offsets, *tail_offsets;
+    uint32_t *head_lengths, *tail_lengths, *rec_lengths, *caps, *bad;
+};
+__global__ __launch_bounds__(256) void k_qts_zrec_sizes(ZrecSizeArgs a) {
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    if (r >= a.n) return;
+    const uint64_t ro = a.rec_offsets[r];
+    const uint64_t so = a.sig_offsets[r] - ro, end = so + a.sig_lengths[r];   // relative to the record
+    bool ok = a.inflate_status[r] == 0u && (!a.tail_status || a.tail_status[r] == 0u);
+    uint32_t il = 0u;
+    if (ok) {
+        il = a.inflated_lengths[r];
+        ok = so >= 8u && il <= a.rec_caps[r] && (uint64_t)il >= end;
+    }
+    const uint32_t head = ok ? (uint32_t)so - 8u : 0u, tail = ok ? il - (uint32_t)end : 0u;
+    const uint32_t len = ok ? head + 8u + a.new_counts[r] + tail : 0u;
+    a.head_offsets[r] = ro;
+    a.head_lengths[r] = head;
+    a.tail_offsets[r] = ok ? ro + end : ro;
+    a.tail_lengths[r] = tail;
+    a.rec_lengths[r] = len;
+    a.caps[r] = qts_deflate_cap(len);
+    a.bad[r] = ok ? 0u : 2u;
+}
+// after k_deflate: the records k_qts_zrec_sizes gave up on report their status and no stream (k_deflate made an empty one)
+__global__ __launch_bounds__(256) void k_qts_zrec_mark(const uint32_t *bad, uint32_t n, uint32_t *out_lengths, uint32_t *status) {
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    if (r >= n || bad[r] == 0u) return;
+    out_lengths[r] = 0u;
+    status[r] = bad[r];
 }
 __global__ __launch_bounds__(256) void k_qts_assemble(AsmArgs a) {
     const uint32_t r = blockIdx.x;
     if (r >= a.n) return;
-    const uint32_t f0 = a.frame_offsets[r], flen = a.frame_offsets[r + 1] - f0, head = a.head_lengths[r];
+    if (a.skip && a.skip[r] != 0u) return;
+    const uint32_t head = a.head_lengths[r], tail = a.tail_lengths[r];
     const uint32_t cnt = a.sig_counts[r], sbytes = cnt * a.sig_unit;
-    const uint8_t *fr = a.frames + f0;
+    const uint8_t *hs = a.head_src + a.head_offsets[r];
+    const uint8_t *ts = a.tail_src + a.tail_offsets[r];
     const uint8_t *sg = a.signal + a.sig_offsets[r] * a.sig_unit;
     uint8_t *dst = a.arena + a.rec_offsets[r];
     const uint32_t t = threadIdx.x;
-    for (uint32_t i = t; i < head; i += 256u) dst[i] = fr[i];
+    for (uint32_t i = t; i < head; i += 256u) dst[i] = hs[i];
     if (t < 8u) dst[head + t] = t < 4u ? (uint8_t)(cnt >> (8u * t)) : (uint8_t)0;
     uint8_t *sd = dst + head + 8u;
     // the signal: whole aligned dwords of the destination where the source allows it
@@ -602,7 +664,7 @@ __global__ __launch_bounds__(256) void k_qts_assemble(AsmArgs a) {
         for (uint32_t i = t; i < sbytes; i += 256u) sd[i] = sg[i];
     }
     uint8_t *td = sd + sbytes;
-    for (uint32_t i = t; i < flen - head; i += 256u) td[i] = fr[head + i];
+    for (uint32_t i = t; i < tail; i += 256u) td[i] = ts[i];
 }
 // bytes [src_offsets[r], + lengths[r]) of src -> dst + dst_offsets[r] (both 16-byte aligned offsets)
 __global__ __launch_bounds__(256) void k_bytes_gather(const uint8_t *src, const uint64_t *src_offsets, const uint32_t *lengths,
@@ -616,17 +678,37 @@ __global__ __launch_bounds__(256) void k_bytes_gather(const uint8_t *src, const 
     for (uint32_t i = nq * 16u + threadIdx.x; i < len; i += 256u) d[i] = s[i];
 }
 
-int launch_qts_record_sizes(const uint32_t *frame_offsets, const uint32_t *sig_counts, uint32_t sig_unit, uint32_t n,
-                            uint32_t *rec_lengths, uint32_t *caps, hipStream_t st) {
+int launch_qts_record_sizes(const uint32_t *frame_offsets, const uint32_t *head_lengths, const uint32_t *sig_counts,
+                            uint32_t sig_unit, uint32_t n, uint64_t *head_offsets, uint64_t *tail_offsets,
+                            uint32_t *tail_lengths, uint32_t *rec_lengths, uint32_t *caps, hipStream_t st) {
     if (n == 0) return SGK_OK;
-    SGK_LAUNCH_UNTIMED(k_qts_record_sizes, (n + 255u) / 256u, 256, st, frame_offsets, sig_counts, sig_unit, n, rec_lengths, caps);
+    SGK_LAUNCH_UNTIMED(k_qts_record_sizes, (n + 255u) / 256u, 256, st, frame_offsets, head_lengths, sig_counts, sig_unit, n,
+                       head_offsets, tail_offsets, tail_lengths, rec_lengths, caps);
     return SGK_OK;
 }
-int launch_qts_assemble(const uint8_t *frames, const uint32_t *frame_offsets, const uint32_t *head_lengths, const uint8_t *signal,
-                        const uint64_t *sig_offsets, const uint32_t *sig_counts, uint32_t sig_unit, uint8_t *arena,
-                        const uint64_t *rec_offsets, uint32_t n, hipStream_t st) {
+int launch_qts_zrec_sizes(const uint64_t *rec_offsets, const uint32_t *rec_caps, const uint32_t *inflated_lengths,
+                          const uint64_t *sig_offsets, const uint32_t *sig_lengths, const uint32_t *inflate_status,
+                          const uint32_t *tail_status, const uint32_t *new_counts, uint32_t n, uint64_t *head_offsets,
+                          uint32_t *head_lengths, uint64_t *tail_offsets, uint32_t *tail_lengths, uint32_t *rec_lengths,
+                          uint32_t *caps, uint32_t *bad, hipStream_t st) {
     if (n == 0) return SGK_OK;
-    AsmArgs a = {frames, frame_offsets, head_lengths, signal, sig_offsets, sig_counts, sig_unit, arena, rec_offsets, n};
+    ZrecSizeArgs a = {rec_offsets, rec_caps, inflated_lengths, sig_offsets, sig_lengths, inflate_status, tail_status, new_counts, n,
+                      head_offsets, tail_offsets, head_lengths, tail_lengths, rec_lengths, caps, bad};
+    SGK_LAUNCH_UNTIMED(k_qts_zrec_sizes, (n + 255u) / 256u, 256, st, a);
+    return SGK_OK;
+}
+int launch_qts_zrec_mark(const uint32_t *bad, uint32_t n, uint32_t *out_lengths, uint32_t *status, hipStream_t st) {
+    if (n == 0) return SGK_OK;
+    SGK_LAUNCH_UNTIMED(k_qts_zrec_mark, (n + 255u) / 256u, 256, st, bad, n, out_lengths, status);
+    return SGK_OK;
+}
+int launch_qts_assemble(const uint8_t *head_src, const uint64_t *head_offsets, const uint32_t *head_lengths,
+                        const uint8_t *tail_src, const uint64_t *tail_offsets, const uint32_t *tail_lengths, const uint32_t *skip,
+                        const uint8_t *signal, const uint64_t *sig_offsets, const uint32_t *sig_counts, uint32_t sig_unit,
+                        uint8_t *arena, const uint64_t *rec_offsets, uint32_t n, hipStream_t st) {
+    if (n == 0) return SGK_OK;
+    AsmArgs a = {head_src, head_offsets, head_lengths, tail_src, tail_offsets, tail_lengths, skip,
+                 signal, sig_offsets, sig_counts, sig_unit, arena, rec_offsets, n};
     SGK_LAUNCH("k_qts_assemble", k_qts_assemble, n, 256, st, a);
     return SGK_OK;
 }

@@ -30,11 +30,19 @@ int zrec_tail_check(const uint8_t *inflated, const uint64_t *rec_offsets, const 
                     uint32_t n_fields, uint32_t *status, hipStream_t st);   // zrec_kernels.hip
 
 // qts record mode, deflate_kernels.hip
-int launch_qts_record_sizes(const uint32_t *frame_offsets, const uint32_t *sig_counts, uint32_t sig_unit, uint32_t n,
-                            uint32_t *rec_lengths, uint32_t *caps, hipStream_t st);
-int launch_qts_assemble(const uint8_t *frames, const uint32_t *frame_offsets, const uint32_t *head_lengths, const uint8_t *signal,
-                        const uint64_t *sig_offsets, const uint32_t *sig_counts, uint32_t sig_unit, uint8_t *arena,
-                        const uint64_t *rec_offsets, uint32_t n, hipStream_t st);
+int launch_qts_record_sizes(const uint32_t *frame_offsets, const uint32_t *head_lengths, const uint32_t *sig_counts,
+                            uint32_t sig_unit, uint32_t n, uint64_t *head_offsets, uint64_t *tail_offsets,
+                            uint32_t *tail_lengths, uint32_t *rec_lengths, uint32_t *caps, hipStream_t st);
+int launch_qts_zrec_sizes(const uint64_t *rec_offsets, const uint32_t *rec_caps, const uint32_t *inflated_lengths,
+                          const uint64_t *sig_offsets, const uint32_t *sig_lengths, const uint32_t *inflate_status,
+                          const uint32_t *tail_status, const uint32_t *new_counts, uint32_t n, uint64_t *head_offsets,
+                          uint32_t *head_lengths, uint64_t *tail_offsets, uint32_t *tail_lengths, uint32_t *rec_lengths,
+                          uint32_t *caps, uint32_t *bad, hipStream_t st);
+int launch_qts_zrec_mark(const uint32_t *bad, uint32_t n, uint32_t *out_lengths, uint32_t *status, hipStream_t st);
+int launch_qts_assemble(const uint8_t *head_src, const uint64_t *head_offsets, const uint32_t *head_lengths,
+                        const uint8_t *tail_src, const uint64_t *tail_offsets, const uint32_t *tail_lengths, const uint32_t *skip,
+                        const uint8_t *signal, const uint64_t *sig_offsets, const uint32_t *sig_counts, uint32_t sig_unit,
+                        uint8_t *arena, const uint64_t *rec_offsets, uint32_t n, hipStream_t st);
 int launch_bytes_gather(const uint8_t *src, const uint64_t *src_offsets, const uint32_t *lengths, uint32_t n, uint8_t *dst,
                         const uint64_t *dst_offsets, hipStream_t st);
 int launch_deflate_unchecked(const uint8_t *in, const uint64_t *in_offsets, const uint32_t *in_lengths, uint32_t n, uint8_t *out,
@@ -130,6 +138,10 @@ struct sgk_job {
     GrowDev d_frb, d_fro, d_frh, d_reclen, d_recoffs, d_rec, d_zcap, d_zoffs, d_z, d_zlen, d_zstat, d_zdoffs, d_zdense;
     bool have_frames = false;
     size_t frame_bytes = 0;
+    // ... where k_qts_assemble finds every record's head and tail (the frames, or with SGK_QTS_ZREC_FRAMES the records in
+    // d_inflated: d_ahl the head lengths there, d_abad the records whose inflated length nobody vouches for)
+    GrowDev d_aho, d_ato, d_atl, d_ahl, d_abad;
+    bool zrec_frames = false;         // the submit in flight / waited for last was one with SGK_QTS_ZREC_FRAMES
     // qts with SGK_SIGNAL_TEXT out: the frames again as the heads and the tails of the rows (sgk_slow5_text_*)
     GrowPin h_hdb, h_hdo, h_tlb, h_tlo;
     GrowDev d_hdb, d_hdo, d_tlb, d_tlo;
@@ -797,23 +809,35 @@ int sgk_job_submit(sgk_job_t *j, int tool, int rna, int pore, int flags) {
 // qts record mode: the records assembled around the quantised signal (blobs at d_out[0] / d_out[1] / d_cnt, or the
 // samples), deflated, gathered densely; lengths, statuses and dense offsets on their way home -- the streams themselves
 // follow in sgk_job_wait once their total is known
-static int job_qts_records(sgk_job_t *j, const sgk_batch_t &view, bool svb) {
+static int job_qts_records(sgk_job_t *j, const sgk_batch_t &view, bool svb, bool zrec) {
     const size_t nr = j->n_reads;
     hipStream_t st = j->st;
     int rc;
     const uint32_t *lens = j->h_lengths.as<uint32_t>();
     const uint32_t *fro = j->h_fro.as<uint32_t>();
+    const uint32_t *icaps = j->h_icaps.as<uint32_t>(), *slens = j->h_slens.as<uint32_t>();
+    const uint64_t *ioffs = j->h_ioffs.as<uint64_t>(), *soffs = j->h_soffs.as<uint64_t>();
     size_t rec_bound = 0, z_bound = 0;
     for (size_t r = 0; r < nr; ++r) {
         const size_t sig = svb ? 4 + ((size_t)lens[r] + 3) / 4 + 3 * (size_t)lens[r] : 2 * (size_t)lens[r];
-        const size_t rec = (size_t)(fro[r + 1] - fro[r]) + 8 + sig;
+        // zrec: the host does not know the tail: whatever the record's room leaves around its old blob (the u64 included)
+        if (zrec && soffs[r] - ioffs[r] < 8) return SGK_ERR_ARG;   // (no len_raw_signal in front of the blob)
+        const size_t rec = zrec ? (size_t)(icaps[r] - slens[r]) + sig : (size_t)(fro[r + 1] - fro[r]) + 8 + sig;
         if (rec >= ((size_t)1 << 29)) return SGK_ERR_ARG;   // (sgk_deflate's limit)
         rec_bound += round_up(rec, 16);
         z_bound += round_up(sgk_deflate_bound(rec), 16);
     }
-    if ((rc = h2d(j->d_frb, j->h_frb, j->frame_bytes, st)) != SGK_OK) return rc;
-    if ((rc = h2d(j->d_fro, j->h_fro, (nr + 1) * 4, st)) != SGK_OK) return rc;
-    if ((rc = h2d(j->d_frh, j->h_frh, nr * 4, st)) != SGK_OK) return rc;
+    if (!zrec) {
+        if ((rc = h2d(j->d_frb, j->h_frb, j->frame_bytes, st)) != SGK_OK) return rc;
+        if ((rc = h2d(j->d_fro, j->h_fro, (nr + 1) * 4, st)) != SGK_OK) return rc;
+        if ((rc = h2d(j->d_frh, j->h_frh, nr * 4, st)) != SGK_OK) return rc;
+    } else {
+        if ((rc = j->d_ahl.ensure(nr * 4)) != SGK_OK) return rc;
+        if ((rc = j->d_abad.ensure(nr * 4)) != SGK_OK) return rc;
+    }
+    if ((rc = j->d_aho.ensure(nr * 8)) != SGK_OK) return rc;
+    if ((rc = j->d_ato.ensure(nr * 8)) != SGK_OK) return rc;
+    if ((rc = j->d_atl.ensure(nr * 4)) != SGK_OK) return rc;
     if ((rc = j->d_reclen.ensure(nr * 4)) != SGK_OK) return rc;
     if ((rc = j->d_zcap.ensure(nr * 4)) != SGK_OK) return rc;
     if ((rc = j->d_zlen.ensure(nr * 4)) != SGK_OK) return rc;
@@ -828,18 +852,33 @@ static int job_qts_records(sgk_job_t *j, const sgk_batch_t &view, bool svb) {
     const uint64_t *sig_offs = svb ? j->d_out[1].as<uint64_t>() : view.offsets;
     const uint8_t *signal = svb ? j->d_out[0].as<uint8_t>() : reinterpret_cast<const uint8_t *>(view.samples);
     const uint32_t unit = svb ? 1u : 2u;
-    if ((rc = launch_qts_record_sizes(j->d_fro.as<uint32_t>(), counts, unit, j->n_reads, j->d_reclen.as<uint32_t>(),
-                                      j->d_zcap.as<uint32_t>(), st)) != SGK_OK) return rc;
+    if (zrec)   // (d_tstat: only a batch with a column table has had its tails checked)
+        rc = launch_qts_zrec_sizes(j->d_ioffs.as<uint64_t>(), j->d_icaps.as<uint32_t>(), j->d_ilens.as<uint32_t>(),
+                                   j->d_soffs.as<uint64_t>(), j->d_slens.as<uint32_t>(), j->d_istat.as<uint32_t>(),
+                                   j->aux ? j->d_tstat.as<uint32_t>() : nullptr, counts, j->n_reads, j->d_aho.as<uint64_t>(),
+                                   j->d_ahl.as<uint32_t>(), j->d_ato.as<uint64_t>(), j->d_atl.as<uint32_t>(),
+                                   j->d_reclen.as<uint32_t>(), j->d_zcap.as<uint32_t>(), j->d_abad.as<uint32_t>(), st);
+    else
+        rc = launch_qts_record_sizes(j->d_fro.as<uint32_t>(), j->d_frh.as<uint32_t>(), counts, unit, j->n_reads,
+                                     j->d_aho.as<uint64_t>(), j->d_ato.as<uint64_t>(), j->d_atl.as<uint32_t>(),
+                                     j->d_reclen.as<uint32_t>(), j->d_zcap.as<uint32_t>(), st);
+    if (rc != SGK_OK) return rc;
     SGK_LAUNCH_UNTIMED(k_layout, 1, 1024, st, j->d_reclen.as<uint32_t>(), static_cast<const uint64_t *>(nullptr), j->n_reads,
                        16u, j->d_recoffs.as<uint64_t>());
     SGK_LAUNCH_UNTIMED(k_layout, 1, 1024, st, j->d_zcap.as<uint32_t>(), static_cast<const uint64_t *>(nullptr), j->n_reads,
                        16u, j->d_zoffs.as<uint64_t>());
-    if ((rc = launch_qts_assemble(j->d_frb.as<uint8_t>(), j->d_fro.as<uint32_t>(), j->d_frh.as<uint32_t>(), signal, sig_offs,
-                                  counts, unit, j->d_rec.as<uint8_t>(), j->d_recoffs.as<uint64_t>(), j->n_reads, st)) != SGK_OK)
+    const uint8_t *src = zrec ? j->d_inflated.as<uint8_t>() : j->d_frb.as<uint8_t>();
+    if ((rc = launch_qts_assemble(src, j->d_aho.as<uint64_t>(), (zrec ? j->d_ahl : j->d_frh).as<uint32_t>(), src,
+                                  j->d_ato.as<uint64_t>(), j->d_atl.as<uint32_t>(), zrec ? j->d_abad.as<uint32_t>() : nullptr,
+                                  signal, sig_offs, counts, unit, j->d_rec.as<uint8_t>(), j->d_recoffs.as<uint64_t>(),
+                                  j->n_reads, st)) != SGK_OK)
         return rc;
     if ((rc = launch_deflate_unchecked(j->d_rec.as<uint8_t>(), j->d_recoffs.as<uint64_t>(), j->d_reclen.as<uint32_t>(), j->n_reads,
                                        j->d_z.as<uint8_t>(), j->d_zoffs.as<uint64_t>(), j->d_zcap.as<uint32_t>(),
                                        j->d_zlen.as<uint32_t>(), j->d_zstat.as<uint32_t>(), st)) != SGK_OK)
+        return rc;
+    if (zrec && (rc = launch_qts_zrec_mark(j->d_abad.as<uint32_t>(), j->n_reads, j->d_zlen.as<uint32_t>(),
+                                           j->d_zstat.as<uint32_t>(), st)) != SGK_OK)
         return rc;
     SGK_LAUNCH_UNTIMED(k_layout, 1, 1024, st, j->d_zlen.as<uint32_t>(), static_cast<const uint64_t *>(nullptr), j->n_reads,
                        16u, j->d_zdoffs.as<uint64_t>());
@@ -855,16 +894,22 @@ static int job_qts_records(sgk_job_t *j, const sgk_batch_t &view, bool svb) {
 int sgk_job_submit_qts(sgk_job_t *j, int bits, int method, int out_fmt_flags) {
     if (!j || !j->begun || j->submitted) return SGK_ERR_ARG;
     const bool records = (out_fmt_flags & SGK_QTS_RECORDS) != 0;
+    // SGK_QTS_ZREC_FRAMES: the frames are the records where they were inflated -- records of a ZREC batch (svb-zd by
+    // definition) only; j->flags keeps the other bits, as every reader of it expects
+    const bool zrec_frames = (out_fmt_flags & SGK_QTS_ZREC_FRAMES) != 0;
+    out_fmt_flags &= ~SGK_QTS_ZREC_FRAMES;
     const int out_fmt = out_fmt_flags & ~SGK_QTS_RECORDS;
+    if (zrec_frames && (!records || j->fmt != SGK_SIGNAL_ZREC || out_fmt != SGK_SIGNAL_SVBZD)) return SGK_ERR_ARG;
     if (out_fmt != SGK_SIGNAL_INT16 && out_fmt != SGK_SIGNAL_SVBZD && out_fmt != SGK_SIGNAL_TEXT) return SGK_ERR_ARG;
     // text in, bare int16 samples out stays refused (tests/test_gpu_slow5_cli.py pins it): that is the decoder alone,
     // and no record of either container holds uncompressed samples next to text ones
     if (j->fmt == SGK_SIGNAL_TEXT && out_fmt == SGK_SIGNAL_INT16 && !records) return SGK_ERR_ARG;
-    if (records && !j->have_frames) return SGK_ERR_ARG;
+    if (records && !zrec_frames && !j->have_frames) return SGK_ERR_ARG;
     if (bits < 1 || bits > 15 || method < SGK_QTS_FLOOR || method > SGK_QTS_FILL_ONES) return SGK_ERR_ARG;
     SGK_HIP_TRY(hipSetDevice(j->device));
     j->tool = SGK_TOOL_QTS;
     j->flags = out_fmt_flags;
+    j->zrec_frames = zrec_frames;
     const size_t nr = j->n_reads;
     hipStream_t st = j->st;
     int rc;
@@ -884,7 +929,7 @@ int sgk_job_submit_qts(sgk_job_t *j, int bits, int method, int out_fmt_flags) {
         if ((rc = job_qts_text_submit(j, &view, records)) != SGK_OK) return rc;
     } else if (out_fmt == SGK_SIGNAL_INT16) {
         if (records) {
-            if ((rc = job_qts_records(j, view, false)) != SGK_OK) return rc;
+            if ((rc = job_qts_records(j, view, false, false)) != SGK_OK) return rc;
         } else if ((rc = d2h(j->h_out[0], j->d_samples, j->n_samples * sizeof(int16_t), st)) != SGK_OK) return rc;
     } else {
         // d_out[0] blobs (worst-case sized), d_out[1] blob offsets, d_out[2] total, d_cnt blob lengths
@@ -901,7 +946,7 @@ int sgk_job_submit_qts(sgk_job_t *j, int bits, int method, int out_fmt_flags) {
                               j->d_out[1].as<uint64_t>(), j->d_cnt.as<uint32_t>(), st);
         if (rc != SGK_OK) return rc;
         if (records) {
-            if ((rc = job_qts_records(j, view, true)) != SGK_OK) return rc;
+            if ((rc = job_qts_records(j, view, true, zrec_frames)) != SGK_OK) return rc;
         } else {
             if ((rc = d2h(j->h_cnt, j->d_cnt, nr * 4, st)) != SGK_OK) return rc;
             if ((rc = d2h(j->h_out[1], j->d_out[1], (nr + 1) * 8, st)) != SGK_OK) return rc;
@@ -938,6 +983,13 @@ int sgk_job_wait(sgk_job_t *j) {
             if (is[r] != 0) ds[r] = (j->rec_fmt == SGK_RECORD_ZSTD ? 0x200u : 0x100u) | is[r];
             else if (ts && ts[r] != 0) ds[r] = 0x400u | ts[r];
             bad = bad || ds[r] != 0;
+        }
+        if (bad && j->tool == SGK_TOOL_QTS && j->zrec_frames) {
+            // the sound records of the batch were assembled and deflated all the same (the others: qts_record_status 2)
+            const uint64_t total = j->h_zdoffs.as<uint64_t>()[j->n_reads];
+            int rc;
+            if ((rc = d2h(j->h_zdense, j->d_zdense, (size_t)total, j->st)) != SGK_OK) return rc;
+            SGK_HIP_TRY(hipStreamSynchronize(j->st));
         }
         if (bad) return SGK_ERR_FORMAT;
     }

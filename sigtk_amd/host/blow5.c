@@ -974,6 +974,14 @@ int64_t b5_aux_fields(const b5_file_t *f, b5_aux_field_t **out) {
     return n_tab;
 }
 
+int64_t b5_zrec_room(const b5_file_t *f, const b5_view_t *v, uint64_t raw_size, uint64_t aux_fixed, uint32_t n_aux_arrays,
+                     uint64_t aux_slack) {
+    const uint64_t end = (uint64_t)v->signal_offset + v->signal_bytes;
+    const uint64_t room = f->record_press == 2 ? v->rec_len : end + aux_fixed + (uint64_t)n_aux_arrays * (8 + aux_slack);
+    if (raw_size > 0xffffffffull || room > 0xffffffffull || end > room) return B5_ERR_FORMAT;
+    return (int64_t)room;
+}
+
 int b5_svb_zd_decode(const uint8_t *blob, uint64_t nbytes, int16_t *dst, uint32_t count) {
     if (nbytes < 4) return B5_ERR_PRESS;
     uint32_t c;

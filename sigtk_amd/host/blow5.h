@@ -130,6 +130,13 @@ typedef struct {
     uint8_t is_array;
 } b5_aux_field_t;
 int64_t b5_aux_fields(const b5_file_t *f, b5_aux_field_t **out);
+/* Room for the inflated record of a head-parsed view (b5_parse_head), for whoever inflates the record elsewhere.  A zstd
+ * frame declares its content size: that is the room, exactly.  A zlib stream does not: head + signal + aux_fixed (the
+ * bytes of the fixed-size columns) + for each of the n_aux_arrays array columns its u64 count and aux_slack bytes.
+ * raw_size: the record's on-disk bytes.  Returns the room, or B5_ERR_FORMAT where a size does not fit 32 bits or the
+ * signal ends behind the room. */
+int64_t b5_zrec_room(const b5_file_t *f, const b5_view_t *v, uint64_t raw_size, uint64_t aux_fixed, uint32_t n_aux_arrays,
+                     uint64_t aux_slack);
 /* scalar streamvbyte + zigzag-delta decode of one blob into dst[count] (host-decode fallback path) */
 int b5_svb_zd_decode(const uint8_t *blob, uint64_t nbytes, int16_t *dst, uint32_t count);
 /* scalar parse of a text SLOW5 raw_signal column (nbytes of text, no tab or newline) into dst[count]: the grammar of

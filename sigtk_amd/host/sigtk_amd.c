@@ -457,10 +457,9 @@ static void load_parse(void *ctx_, uint32_t i, int tid) {
      * does not: head + signal + the fixed-size fields + for every array column its count word and a slack (a design
      * constant: ONT's array fields are a few bytes); a record whose arrays are longer comes back 0x108 and its batch is
      * redone on the host (writer_main).  Either way the GPU checks what the record inflated to against the columns. */
-    const uint64_t end = (uint64_t)r->v.signal_offset + r->v.signal_bytes;
-    const uint64_t room = P->f->record_press == 2 ? r->v.rec_len : end + P->aux_fixed + (uint64_t)P->n_aux_arrays * (8 + P->aux_slack);
-    if (r->raw_size > 0xffffffffull || room > 0xffffffffull || end > room) r->err = B5_ERR_FORMAT;
-    r->room = (uint32_t)room;
+    const int64_t room = b5_zrec_room(P->f, &r->v, r->raw_size, P->aux_fixed, P->n_aux_arrays, P->aux_slack);
+    if (room < 0) r->err = (int)room;
+    else r->room = (uint32_t)room;
 }
 /* phase 2 (parallel): stage record i's signal and scaling into the job's pinned buffers */
 static void load_stage(void *ctx_, uint32_t i, int tid) {
@@ -489,7 +488,8 @@ static void load_stage(void *ctx_, uint32_t i, int tid) {
         memcpy(fr, r->scratch, b->fr_heads[i]);
         memcpy(fr + b->fr_heads[i], tail, tl);
         fr[b->fr_heads[i] + tl] = '\n';
-    } else if (c->P->gpu_deflate) {   /* the record around its signal (batch_frames laid the frames out) */
+    } else if (c->P->gpu_deflate && !b->zrec) {   /* the record around its signal (batch_frames laid the frames out; a zrec
+                                                    * batch has no inflated record here: its frames are taken on the GPU) */
         const uint8_t *tail = r->v.signal + r->v.signal_bytes;
         uint8_t *fr = b->fr_blob + b->fr_offs[i];
         memcpy(fr, r->v.rec, b->fr_heads[i]);
@@ -570,10 +570,12 @@ static void batch_submit(pipe_t *P, batch_t *b) {
         flags |= SGK_JOB_TEXT;
     }
     if (P->mode == MODE_QTS) {
-        if ((P->gpu_deflate || P->q_text) && (rc = sgk_job_set_record_frames(b->job, b->fr_blob, b->fr_offs, b->fr_heads)) != SGK_OK)
+        /* --gpu-inflate (b->zrec): head and tail of every record are read where the GPU inflated it; else the frames go up */
+        if (((P->gpu_deflate && !b->zrec) || P->q_text) && (rc = sgk_job_set_record_frames(b->job, b->fr_blob, b->fr_offs, b->fr_heads)) != SGK_OK)
             gpu_fail("sgk_job_set_record_frames", rc);
         const int out_fmt = P->q_text ? SGK_SIGNAL_TEXT : (P->f->signal_press == 1 ? SGK_SIGNAL_SVBZD : SGK_SIGNAL_INT16);
-        rc = sgk_job_submit_qts(b->job, P->q_bits, P->q_method, out_fmt | (P->gpu_deflate || P->q_text ? SGK_QTS_RECORDS : 0));
+        rc = sgk_job_submit_qts(b->job, P->q_bits, P->q_method, out_fmt | (P->gpu_deflate || P->q_text ? SGK_QTS_RECORDS : 0) |
+                                                                   (b->zrec ? SGK_QTS_ZREC_FRAMES : 0));
     } else
         rc = sgk_job_submit(b->job, tool, P->opt.rna, P->opt.pore, flags);
     if (rc != SGK_OK) gpu_fail("sgk_job_submit", rc);
@@ -612,7 +614,7 @@ static void batch_launch(pipe_t *P, batch_t *b) {
     if (b->zrec) rc = sgk_job_begin_zrec_aux(b->job, b->n, P->f->record_press == 2 ? SGK_RECORD_ZSTD : SGK_RECORD_ZLIB, b->lengths, b->blob_bytes, b->sig_off, b->sig_len, b->room, P->aux_tab, P->n_aux, &b->in);
     else rc = sgk_job_begin(b->job, b->n, b->lengths, b->sigtext ? SGK_SIGNAL_TEXT : (b->svb ? SGK_SIGNAL_SVBZD : SGK_SIGNAL_INT16), b->blob_bytes, &b->in);
     if (rc != SGK_OK) gpu_fail("sgk_job_begin", rc);
-    if (P->gpu_deflate || P->q_text) batch_frames(b, P->q_text);
+    if ((P->gpu_deflate && !b->zrec) || P->q_text) batch_frames(b, P->q_text);
     pfor(P->load_pool, b->n, load_stage, &c);
     for (uint32_t i = 0; i < b->n; i++) {
         if (b->recs[i].err) {
@@ -882,6 +884,7 @@ static int batch_redo_host(pipe_t *P, batch_t *b, pool_t *pool) {
     b->svb = 1;
     int rc = sgk_job_begin(b->job, b->n, b->lengths, SGK_SIGNAL_SVBZD, b->blob_bytes, &b->in);
     if (rc != SGK_OK) gpu_fail("sgk_job_begin", rc);
+    if (P->gpu_deflate) batch_frames(b, 0);   /* qts --gpu-inflate: the frames from the host's inflated records after all */
     pfor(pool, b->n, load_stage, &c);
     batch_submit(P, b);
     P->n_redone++;
@@ -1188,6 +1191,32 @@ static struct option long_options[] = {
     {"threads", required_argument, 0, 't'}, {"host-decode", no_argument, 0, 0},  {"host-inflate", no_argument, 0, 0},
     {"gpu-text", no_argument, 0, 0},        {"aux-slack", required_argument, 0, 0}, {0, 0, 0, 0}};
 
+/* What a pipeline needs to send the records of P->f to the GPU as they sit in the file (cmain, qts --gpu-inflate): the
+ * header's auxiliary columns as sgk_job_begin_zrec_aux takes them, how many are arrays, the bytes of the others, the slack
+ * per array (load_parse makes every record's room from these).  Returns whether the file is one of those: BLOW5 with zlib
+ * or zstd records around an svb-zd signal and a type line of known types only -- the caller adds its own conditions. */
+static int pipe_zrec_setup(pipe_t *P, uint64_t aux_slack) {
+    const b5_file_t *f = P->f;
+    b5_aux_field_t *tab = NULL;
+    const int64_t n_tab = b5_aux_fields(f, &tab);
+    for (int64_t k = 0; k < n_tab; k++) {
+        if (tab[k].is_array) P->n_aux_arrays++;
+        else P->aux_fixed += tab[k].elem_bytes;
+    }
+    if (n_tab > 0) {
+        P->aux_tab = (sgk_aux_field_t *)malloc(sizeof(sgk_aux_field_t) * (size_t)n_tab);
+        if (!P->aux_tab) die_mem();
+        for (int64_t k = 0; k < n_tab; k++) {
+            P->aux_tab[k].elem_bytes = tab[k].elem_bytes;
+            P->aux_tab[k].is_array = tab[k].is_array;
+        }
+    }
+    free(tab);
+    P->n_aux = n_tab > 0 ? (uint32_t)n_tab : 0;
+    P->aux_slack = aux_slack;
+    return !f->text && (f->record_press == 1 || f->record_press == 2) && f->signal_press == 1 && n_tab >= 0;
+}
+
 static int cmain(int argc, char *argv[], const char *mode_s) {
     /* `ent` has its own front end in the reference (src/ent.c:63-105): only -h/-V (and --no-header) are options,
      * exactly one file argument, no DNA/RNA or pore detection */
@@ -1323,25 +1352,7 @@ static int cmain(int argc, char *argv[], const char *mode_s) {
      * header's type line names only types this reader knows, arrays included (the GPU then checks every record's auxiliary
      * fields against that table, sgk_job_begin_zrec_aux); everything else -- and --host-inflate / --host-decode, and reads
      * fetched by id from a file with array columns -- is inflated by the host threads as before. */
-    b5_aux_field_t *tab = NULL;
-    const int64_t n_tab = b5_aux_fields(f, &tab);
-    for (int64_t k = 0; k < n_tab; k++) {
-        if (tab[k].is_array) P.n_aux_arrays++;
-        else P.aux_fixed += tab[k].elem_bytes;
-    }
-    if (n_tab > 0) {
-        P.aux_tab = (sgk_aux_field_t *)malloc(sizeof(sgk_aux_field_t) * (size_t)n_tab);
-        if (!P.aux_tab) die_mem();
-        for (int64_t k = 0; k < n_tab; k++) {
-            P.aux_tab[k].elem_bytes = tab[k].elem_bytes;
-            P.aux_tab[k].is_array = tab[k].is_array;
-        }
-    }
-    free(tab);
-    P.n_aux = n_tab > 0 ? (uint32_t)n_tab : 0;
-    P.aux_slack = aux_slack;
-    P.zrec = !f->text && !host_inflate && !host_decode && (f->record_press == 1 || f->record_press == 2) && f->signal_press == 1 && n_tab >= 0 &&
-             (argc - optind - 1 == 0 || P.n_aux_arrays == 0);
+    P.zrec = pipe_zrec_setup(&P, aux_slack) && !host_inflate && !host_decode && (argc - optind - 1 == 0 || P.n_aux_arrays == 0);
     /* ... in batches of 128 M samples: the inflate kernel is a wavefront per record and takes ~35 ms however many records
      * it has (up to the ~4 800 the GPU holds at once), so a batch should bring a thousand of them (1e10 samples of `stat`:
      * 5.2 s with the 16 M-sample batches of the host path, 1.7 s with 128 M, profiles/r05_cli_steady.json) */
@@ -1367,6 +1378,9 @@ static int cmain(int argc, char *argv[], const char *mode_s) {
  * and always writes zlib + svb-zd); records carry the same fields, auxiliary data included, with the quantised
  * signal -- quantised and re-encoded (svb-zd) on the GPU, deflated on the host thread pool, or with --gpu-deflate
  * assembled and deflated on the GPU as well (Z_RLE-like streams of csrc/deflate_kernels.hip: other bytes, same records).
+ * With --gpu-inflate (which implies --gpu-deflate) the records of a file the other subtools would send to the GPU as
+ * they sit in the file go there for qts too: only their heads are inflated here, k_qts_assemble takes head and tail of
+ * every record from where k_inflate / k_zstd left it, and the records stay on the GPU from file to file.
  * A text SLOW5 file is written back as a text SLOW5 file (both through slow5lib by extension in the reference,
  * src/qts.c:101-108): the header as it stands, every line with its four doubles re-printed as slow5lib prints them
  * (b5_s5_qts_head), the quantised column written on the GPU between the line's head and its auxiliary columns
@@ -1377,6 +1391,8 @@ static struct option qts_long_options[] = {
     {"gpus", required_argument, 0, 0},      {"batch-samples", required_argument, 0, 0}, {"threads", required_argument, 0, 't'},
     {"gpu-text", no_argument, 0, 0}, /* accepted, changes nothing: qts writes records, not rows */
     {"gpu-deflate", no_argument, 0, 0}, /* records assembled and deflated on the GPU (k_qts_assemble, k_deflate) */
+    {"gpu-inflate", no_argument, 0, 0}, /* ... and inflated there too: they stay on the GPU from file to file (implies --gpu-deflate) */
+    {"aux-slack", required_argument, 0, 0}, /* test option, as in cmain: room per array column of a zlib record sent to the GPU */
     {0, 0, 0, 0}};
 
 static int qtsmain(int argc, char *argv[]) {
@@ -1384,7 +1400,8 @@ static int qtsmain(int argc, char *argv[]) {
     int longindex = 0, c;
     FILE *fp_help = stderr;
     char *out_fn = NULL;
-    int b = 1, n_gpus = 1, nthreads = 0, gpu_deflate = 0;
+    int b = 1, n_gpus = 1, nthreads = 0, gpu_deflate = 0, gpu_inflate = 0, batch_set = 0;
+    uint64_t aux_slack = 256;
     const char *method = "round";
     uint64_t batch_samples = 16ull << 20; /* small batches: the buffers of a job are cheap to set up, the host stages overlap sooner */
     while ((c = getopt_long(argc, argv, optstring, qts_long_options, &longindex)) >= 0) {
@@ -1409,8 +1426,14 @@ static int qtsmain(int argc, char *argv[]) {
             n_gpus = atoi(optarg);
         } else if (c == 0 && longindex == 7) {
             batch_samples = strtoull(optarg, NULL, 10);
+            batch_set = 1;
         } else if (c == 0 && longindex == 10) {
             gpu_deflate = 1;
+        } else if (c == 0 && longindex == 11) {
+            gpu_inflate = gpu_deflate = 1;
+        } else if (c == 0 && longindex == 12) {
+            aux_slack = strtoull(optarg, NULL, 10);
+            if (aux_slack > (1ull << 20)) aux_slack = 1ull << 20;
         }
     }
     if (argc - optind != 1 || fp_help == stdout) {
@@ -1503,6 +1526,13 @@ static int qtsmain(int argc, char *argv[]) {
     P.q_method = q_method;
     P.gpu_deflate = gpu_deflate && f->record_press != 0;   /* (uncompressed records: nothing to deflate, the flag changes nothing) */
     P.q_text = f->text;   /* lines out: no record sizes and no end-of-file marker */
+    /* --gpu-inflate: the records go to the GPU as they sit in the file, under cmain's conditions for that (qts has no
+     * read-id mode); on any other file the option is --gpu-deflate alone.  Then in batches of 64 M samples unless
+     * --batch-samples says otherwise: the inflate kernel wants several hundred records in flight, and the 128 M of the
+     * other subtools cost more in growing the record and stream buffers than they gain (profiles/qts_gpu_inflate.md:
+     * 0.34 s at 64 M against 0.39 - 0.75 s at 128 M and 0.39 - 0.46 s at 16 M on 4e8 samples). */
+    if (gpu_inflate) P.zrec = pipe_zrec_setup(&P, aux_slack);
+    if (P.zrec && !batch_set) batch_samples = 64ull << 20;
     P.out_fp = out;
     P.limit_bytes = f->text ? batch_samples * 4 : batch_samples;   /* (on-disk bytes: four to five per sample in a text file) */
     run_pipeline(&P, n_gpus, t_init);
