@@ -373,8 +373,10 @@ void sgk_ent_finish(const sgk_ent_hist_t *hist, uint16_t *over_raw, uint16_t *ov
  * sits in the record.  blobs: device buffer, readable up to its size rounded up to a multiple of 4
  * bytes (the kernel uses aligned 4-byte loads); blob_offsets/blob_lengths: byte offset and byte length
  * of each read's blob (the length INCLUDES the 4-byte count); samples/offsets/lengths as in
- * sgk_batch_t (lengths[r] must equal the blob's count); status[r]: 0 ok, 1 count mismatch,
- * 2 truncated / inconsistent blob (the read's samples are then undefined). */
+ * sgk_batch_t (lengths[r] must equal the blob's count); status[r]: 0 ok, 1 count mismatch (or fewer
+ * than 4 bytes: no count word), 2 truncated / inconsistent blob: fewer bytes than 4 + ceil(count / 4),
+ * data shorter than the keys promise, or data bytes left over (the read's samples are then undefined;
+ * where 1 and 2 both apply either may be reported). */
 int sgk_svbzd_decode(const uint8_t *blobs, const uint64_t *blob_offsets, const uint32_t *blob_lengths,
                      uint32_t n_reads, int16_t *samples, const uint64_t *offsets, const uint32_t *lengths,
                      uint32_t *status, void *stream);

@@ -39,7 +39,7 @@ __global__ __launch_bounds__(64) void k_svbzd_decode(SvbArgs a) {
     const uint32_t nkeys = (count + 3) / 4;
     uint32_t st = 0;
     if (blen < 4 || count != a.lengths[r]) st = 1;
-    if ((uint64_t)4 + nkeys > blen) st = 2;
+    if (blen >= 4 && (uint64_t)4 + nkeys > blen) st = 2;  // (without a count word nothing says how many keys: status 1)
     if (st) {
         if (l == 0) a.status[r] = st;
         return;

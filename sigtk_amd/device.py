@@ -46,15 +46,19 @@ class DeviceReads:
         return int(self.lengths_host.astype(np.int64).sum())
 
 
-def alloc_reads(lengths: np.ndarray, device: torch.device, align: int = 64) -> DeviceReads:
-    """Lay out reads of the given lengths with every read starting on an `align`-sample boundary."""
+def alloc_reads(lengths: np.ndarray, device: torch.device, align: int = 64, leads=None) -> DeviceReads:
+    """Lay out reads of the given lengths with every read starting on an `align`-sample boundary, or, with `leads`,
+    leads[r] samples behind it (the padding grows with the lead: reads never overlap)."""
     lengths = np.asarray(lengths, dtype=np.int64)
     n = lengths.size
-    padded = (lengths + align - 1) // align * align
+    lead = np.zeros(n, dtype=np.int64) if leads is None else np.asarray(leads, dtype=np.int64)
+    assert lead.size == n and (n == 0 or int(lead.min()) >= 0)
+    padded = (lengths + lead + align - 1) // align * align
     # 64 samples of head room and tail room: the event fast path reads a little outside each read
     offsets = np.full(n, 256, dtype=np.int64)
     if n > 1:
         offsets[1:] += np.cumsum(padded[:-1])
+    offsets += lead
     n_samples = ((int(padded.sum()) if n else 0) + 320 + 7) // 8 * 8   # the ABI wants a multiple of 8
     return DeviceReads(
         samples=torch.zeros(n_samples, dtype=torch.int16, device=device),
@@ -262,23 +266,33 @@ def pa(b: DeviceReads, out: torch.Tensor) -> None:
 
 # ---------------------------------------------------------------------- svb-zd decode (device API)
 
-def svbzd_decode(blobs, counts, device: torch.device):
-    """Decode svb-zd signal blobs (bytes objects) on the device.
+def svbzd_decode(blobs, counts, device: torch.device, blob_leads=None, sample_leads=None, fill=None):
+    """Decode svb-zd signal blobs (bytes objects) on the device.  Blob r starts on a 16-byte boundary of the blob buffer,
+    or blob_leads[r] (0 - 15) bytes behind one, and the bytes between the blobs are then 0xC3, not 0; read r starts
+    sample_leads[r] samples behind its aligned slot (alloc_reads); fill: the int16 the sample arena holds before the launch.
     -> (DeviceReads with the decoded samples and zeroed scaling, status tensor [n_reads] int32)"""
     L = api.load_library()
     n = len(blobs)
     blens = np.array([len(b) for b in blobs], dtype=np.uint32)
+    lead = np.zeros(n, dtype=np.int64) if blob_leads is None else np.asarray(blob_leads, dtype=np.int64)
+    assert lead.size == n and (n == 0 or (0 <= int(lead.min()) and int(lead.max()) <= 15))
     boffs = np.zeros(n, dtype=np.int64)
-    if n > 1:
-        boffs[1:] = np.cumsum((blens[:-1].astype(np.int64) + 15) // 16 * 16)  # 16-byte aligned blob starts
-    total = int(boffs[-1] + blens[-1]) if n else 0
-    host = np.zeros(max(total + 16, 16), dtype=np.uint8)
+    pos = 0
+    for i in range(n):
+        boffs[i] = (pos + 15) // 16 * 16 + int(lead[i])   # blob starts: 16-byte aligned + lead
+        pos = int(boffs[i]) + int(blens[i])
+    total = pos
+    # (at least 4 readable bytes behind the last blob: the kernel's aligned dword loads end past it)
+    host = np.full(max(total + 16, 16), 0 if blob_leads is None else 0xC3, dtype=np.uint8)
     for i, b in enumerate(blobs):
         host[int(boffs[i]):int(boffs[i]) + len(b)] = np.frombuffer(b, dtype=np.uint8)
     d_blobs = torch.from_numpy(host).to(device)
+    assert _ptr(d_blobs) % 16 == 0
     d_boffs = torch.from_numpy(boffs).to(device)
     d_blens = torch.from_numpy(blens.astype(np.int32)).to(device)
-    reads = alloc_reads(np.asarray(counts, dtype=np.int64), device)
+    reads = alloc_reads(np.asarray(counts, dtype=np.int64), device, leads=sample_leads)
+    if fill is not None:
+        reads.samples.fill_(int(np.int16(fill)))
     status = torch.full((max(n, 1),), -1, dtype=torch.int32, device=device)
     api.check(L.sgk_svbzd_decode(_ptr(d_blobs), _ptr(d_boffs), _ptr(d_blens), n, _ptr(reads.samples),
                                  _ptr(reads.offsets), _ptr(reads.lengths), _ptr(status), _stream_ptr()),
@@ -387,8 +401,12 @@ def qts(b: DeviceReads, bits: int, method: int) -> None:
                         int(method), _stream_ptr()), "sgk_qts")
 
 
-def svbzd_encode(b: DeviceReads):
-    """sgk_svbzd_size + sgk_svbzd_encode -> list of blobs (bytes), one per read"""
+def svbzd_encode(b: DeviceReads, blob_leads=None, fill: int = 0, with_gaps: bool = False):
+    """sgk_svbzd_size + sgk_svbzd_encode -> list of blobs (bytes), one per read.  Blob r starts on an 8-byte boundary of
+    the output buffer, or with blob_leads (each 0, 4, 8 or 12) blob_leads[r] bytes behind a 16-byte boundary; the buffer
+    is pre-filled with `fill`.  with_gaps: -> (blobs, gaps, lengths): gaps[0] the bytes in front of the first blob,
+    gaps[r + 1] those between the end of blob r and the start of the next (the end of the buffer, 16 bytes or more, for
+    the last), which no blob may write; lengths: what sgk_svbzd_size reported"""
     L = api.load_library()
     dev = b.samples.device
     n = b.n_reads
@@ -398,14 +416,30 @@ def svbzd_encode(b: DeviceReads):
     torch.cuda.synchronize()
     lens = blens[:n].cpu().numpy().astype(np.int64)
     offs = np.zeros(n + 1, dtype=np.int64)
-    np.cumsum((lens + 7) // 8 * 8, out=offs[1:])
-    blobs = torch.zeros(max(int(offs[-1]), 8), dtype=torch.uint8, device=dev)
+    if blob_leads is None:
+        np.cumsum((lens + 7) // 8 * 8, out=offs[1:])
+    else:
+        lead = np.asarray(blob_leads, dtype=np.int64)
+        assert lead.size == n and all(int(v) in (0, 4, 8, 12) for v in lead)
+        pos = 0
+        for r in range(n):
+            offs[r] = (pos + 15) // 16 * 16 + int(lead[r])
+            pos = int(offs[r]) + int(lens[r])
+        offs[n] = pos
+    size = max(int(offs[-1]), 8) + (16 if with_gaps else 0)
+    blobs = torch.full((size,), int(fill), dtype=torch.uint8, device=dev)
+    assert _ptr(blobs) % 16 == 0
     d_offs = torch.from_numpy(offs[:n].copy() if n else np.zeros(1, dtype=np.int64)).to(dev)
     api.check(L.sgk_svbzd_encode(_ptr(b.samples), _ptr(b.offsets), _ptr(b.lengths), n, _ptr(blobs), _ptr(d_offs),
                                  _ptr(blens), _stream_ptr()), "sgk_svbzd_encode")
     torch.cuda.synchronize()
     host = blobs.cpu().numpy()
-    return [host[int(offs[r]):int(offs[r]) + int(lens[r])].tobytes() for r in range(n)]
+    out = [host[int(offs[r]):int(offs[r]) + int(lens[r])].tobytes() for r in range(n)]
+    if with_gaps:
+        ends = [0] + [int(offs[r]) + int(lens[r]) for r in range(n)]
+        starts = [int(offs[r]) for r in range(n)] + [size]
+        return out, [host[e:s].tobytes() for e, s in zip(ends, starts)], lens
+    return out
 
 
 def inflate_input_offsets(streams, leads=None):

@@ -11,12 +11,12 @@ pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
-def _load(arrays):
+def _load(arrays, sample_leads=None):
     import torch
     from sigtk_amd import device
     dev = torch.device("cuda", 0)
     lens = np.array([a.size for a in arrays], dtype=np.int64)
-    b = device.alloc_reads(lens, dev)
+    b = device.alloc_reads(lens, dev, leads=sample_leads)
     host = np.full(b.n_samples, 12345, dtype=np.int16)   # gaps are arbitrary data
     for r, a in enumerate(arrays):
         o = int(b.offsets_host[r]); host[o:o + a.size] = a
@@ -50,15 +50,17 @@ def test_encoder_all_code_lengths_ragged_and_empty(gpu):
 
 
 @pytest.mark.parametrize("method,name", [(0, "floor"), (1, "round"), (2, "fill-ones")])
-@pytest.mark.parametrize("bits", [1, 2, 5])
+@pytest.mark.parametrize("bits", [1, 2, 5, 8, 15])
 def test_quantisers_match_qts_c(gpu, method, name, bits):
-    """src/qts.c:126-142 on int16 (int arithmetic, truncated back to int16 on assignment)"""
+    """src/qts.c:126-142 on int16 (int arithmetic, truncated back to int16 on assignment); bits 8: the most the
+    reference's command line takes, 15: the most sgk_qts takes.  The reads lie at odd sample offsets, the longest has
+    seven slabs of 8192 samples, 16385 has three, and the short and empty reads skip the slabs they do not reach"""
     import torch
     from sigtk_amd import device
     rs = np.random.RandomState(method * 10 + bits)
-    arrays = [rs.randint(-32768, 32767, size=n).astype(np.int16) for n in (1, 100, 8191, 8192, 8193, 50000)]
+    arrays = [rs.randint(-32768, 32767, size=n).astype(np.int16) for n in (1, 100, 8191, 8192, 8193, 50000, 0, 16385)]
     arrays.append(np.array([32767, 32766, -32768, -1, 0, 1], dtype=np.int16))               # wrap-around at the top
-    b = _load(arrays)
+    b = _load(arrays, sample_leads=[1, 3, 5, 7, 9, 63, 11, 13, 15])
     device.qts(b, bits, method)
     torch.cuda.synchronize()
     host = b.samples.cpu().numpy()
@@ -74,8 +76,9 @@ def test_quantisers_match_qts_c(gpu, method, name, bits):
             e = np.where(lsb < (1 << (bits - 1)), x & ~mask, (x & ~mask) + (1 << bits))
         e = e.astype(np.int16)      # C: int -> int16_t assignment wraps
         o = int(b.offsets_host[r])
-        assert np.array_equal(host[o:o + a.size], e), (name, bits, r)
-    assert host[0] == 12345        # nothing outside the reads was touched
+        assert o % 2 == 1 and np.array_equal(host[o:o + a.size], e), (name, bits, r)
+        host[o:o + a.size] = 12345
+    assert host[0] == 12345 and (host == 12345).all()        # nothing outside the reads was touched
 
 
 @pytest.mark.parametrize("svb_in,svb_out", [(False, True), (True, True), (True, False)])
