@@ -151,7 +151,8 @@ def build_cli_asan(force: bool = False, verbose: bool = False) -> str:
 
 def build_tools(force: bool = False, verbose: bool = False) -> None:
     """the stand-alone programs of tools/: HIP (issue-rate microbenchmark, hardware accuracy check of v_rsq_f32, the
-    certified square root on the GPU: with the library's numerics flags) and host (sqrt_check: the same form against sqrtf)"""
+    certified square root on the GPU: with the library's numerics flags) and host (sqrt_check: the same form against sqrtf;
+    long_cold_check: the long detector's bound formed from the f32 sums of the window's halves)"""
     tdir = os.path.join(ROOT, "tools")
     math_h = os.path.join(CSRC, "tstat_math.h")
     numerics = ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]
@@ -166,12 +167,13 @@ def build_tools(force: bool = False, verbose: bool = False) -> None:
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         subprocess.check_call(cmd)
-    src, exe = os.path.join(tdir, "sqrt_check.cpp"), os.path.join(tdir, "sqrt_check")
-    if os.path.exists(src) and (force or not _newer(exe, [src, math_h])):
-        cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-pthread", "-o", exe, src]
-        if verbose:
-            print(" ".join(cmd), file=sys.stderr)
-        subprocess.check_call(cmd)
+    for name in ("sqrt_check", "long_cold_check"):
+        src, exe = os.path.join(tdir, name + ".cpp"), os.path.join(tdir, name)
+        if os.path.exists(src) and (force or not _newer(exe, [src, math_h])):
+            cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-pthread", "-o", exe, src]
+            if verbose:
+                print(" ".join(cmd), file=sys.stderr)
+            subprocess.check_call(cmd)
 
 
 if __name__ == "__main__":

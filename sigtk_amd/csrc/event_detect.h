@@ -40,6 +40,13 @@ struct LzCfg {
 };
 static_assert(LzCfg<3>::NP >= 8 && LzCfg<7>::NP >= 16, "prefix ring holds P(i) .. P(i+W2+1)");
 
+// Which kernels take the leading-edge form of the fast pass (LazyPass<.., LEAD>), as bits: 1 k_event<3, *> (shipped),
+// 2 k_event<7, *>, 4 k_event_multi<3, *>.  The others are switches for listings and A/B builds (tools/build_variant.sh
+// <tag> -DSGK_EVENT_LEAD=<bits>; 0: the trailing form everywhere); profiles/event_leading_window.md has what they showed.
+#ifndef SGK_EVENT_LEAD
+#define SGK_EVENT_LEAD 1
+#endif
+
 constexpr int LZ_NONE = -(1 << 29);   // "no mask" / far in the past (block-relative positions drift by -16 per block)
 constexpr int LZ_NREC = 8;            // hot long-detector runs a lane can record per pass (more: read -> exact fallback)
 constexpr int LZ_RING_WORDS = 16;     // per-lane bitmap ring: 512 positions
@@ -246,13 +253,26 @@ __device__ __forceinline__ bool lane_of(lmask_t m) { return __builtin_amdgcn_inv
 // straight from global memory one block ahead.  A wave touches 64 different 128-byte lines per load instruction;
 // each line is consumed over 4 consecutive blocks and stays in L2 meanwhile, so HBM traffic remains one pass over
 // the samples and there are no barriers or cooperative loads in the loop.
-template <int W1, typename T, bool FLAGGED>
+//
+// LEAD (a template choice: k_event<3, *> takes it; it costs the other kernels registers they do not have): the short
+// window is formed at the LEADING edge.  Step i forms the sums of window position p = i + W1, c = P(i+W2) - P(i+W1):
+// their floats go into a ring (ss / sqs) and are the B side of index p, W1 steps later; the A side made of c goes into
+// the A ring, twice as deep, and is the A side of index p + W1.  The long window of index i is the short windows i
+// and i + W1: its estimates come from their four floats (sgk_lside_halves) -- two f64 subtractions and two conversions
+// per index less than with b2 = P(i+W2) - P(i), and P(i) .. P(i+W1-1) need not stay in the prefix ring.  Every sum is
+// exact and every float the same RN32 of it, so the short statistic is bit for bit what the trailing form computes.
+template <int W1, typename T, bool FLAGGED, bool LEAD = false>
 struct LazyPass {
+    static_assert(!(LEAD && FLAGGED), "the fallback keeps its domain checks and TwoSum form");
     using C = LzCfg<W1>;
     static constexpr int W2 = C::W2, R = C::R, NP = C::NP, NA = C::NA, NL = C::NL, H1 = C::H1;
+    static constexpr int NA2 = LEAD ? 2 * NA : NA;   // LEAD: an A side waits 2 * W1 steps for its index
+    static constexpr int NS = LEAD ? NA : 1;         // LEAD: ring of the short windows' f32 sums, > W1
+    static_assert(NA2 > (LEAD ? 2 : 1) * W1 && (!LEAD || NS > W1) && R % NA2 == 0, "ring depths");
     // rings
     double Ps[NP], Pq[NP];        // running prefix sums of x and of fl(x*x); slot of P(k) = k mod NP
-    SgkARole ar[NA];              // short A side of window position p at slot p mod NA
+    SgkARole ar[NA2];             // short A side of window position p at slot p mod NA2
+    float ss[NS], sqs[NS];        // LEAD: RN32 of the short window sums of position p at slot p mod NS
     SgkLSide ls[NL];              // long-window estimates of window position p at slot p mod NL
     float t1[4];                  // t-statistics of the current quad
     lmask_t nk[4];                // lanes whose t-statistic of the quad's k-th index is not certified
@@ -310,6 +330,22 @@ struct LazyPass {
         // P(i+W2+1) = P(i+W2) + x[i+W2]; it replaces P(i-1)
         Ps[(U + W2 + 1) % NP] = Ps[(U + W2) % NP] + (double)xn;
         Pq[(U + W2 + 1) % NP] = Pq[(U + W2) % NP] + (double)xqn;
+        if constexpr (LEAD) {
+            // the short window at position p = i + W1
+            const double c = Ps[(U + W2) % NP] - Ps[(U + W1) % NP], cq = Pq[(U + W2) % NP] - Pq[(U + W1) % NP];
+            const float s_p = (float)c, sq_p = (float)cq;
+            const float s_i = ss[U % NS], sq_i = sqs[U % NS];  // ... and at position i, formed W1 steps ago
+            ss[(U + W1) % NS] = s_p;
+            sqs[(U + W1) % NS] = sq_p;
+            bool cv_ok, tail_ok;
+            t1[U & 3] = sgk_tstat_try_ab<W1>(s_i, sq_i, ar[(U + NA2 - W1) % NA2], cv_ok, tail_ok);
+            nk[U & 3] = ~(__ballot(cv_ok) & __ballot(tail_ok));
+            ar[(U + W1) % NA2] = sgk_arole<W1, true>(c, cq);
+            const SgkLSide lb = sgk_lside_halves<W2>(s_i, sq_i, s_p, sq_p);  // long window at position i: bound only
+            hc[U & 3] = ~__ballot(sgk_long_cold<W2>(ls[(U + NL - W2) % NL], lb));
+            ls[U % NL] = lb;
+            return;
+        }
         const double p0 = Ps[U % NP], q0 = Pq[U % NP];
         const double b1 = Ps[(U + W1) % NP] - p0, b1q = Pq[(U + W1) % NP] - q0;
         const double b2 = Ps[(U + W2) % NP] - p0, b2q = Pq[(U + W2) % NP] - q0;
@@ -538,6 +574,33 @@ struct LazyPass {
         (init_step<Ks>(ps, pq, w, hs, hq), ...);
     }
 
+    // LEAD: the same prefix sums; short windows at the positions [i_begin - W2, i_begin + W1): f32 sums of those from
+    // i_begin on, A sides of those from i_begin - W1 on, and the long estimates of [i_begin - W2, i_begin) from pairs
+    // of them, as every later step forms them (what a pass decides at an index does not depend on where it began)
+    __device__ __forceinline__ void init_lead(const float (&w)[2 * W2]) {
+        double hs[2 * W2 + 1], hq[2 * W2 + 1];  // P(o + k)
+        hs[0] = 0.0;
+        hq[0] = 0.0;
+#pragma unroll
+        for (int k = 0; k < 2 * W2; ++k) {
+            hs[k + 1] = hs[k] + (double)w[k];
+            hq[k + 1] = hq[k] + (double)(w[k] * w[k]);
+        }
+#pragma unroll
+        for (int k = W2; k <= 2 * W2; ++k) { Ps[(k - W2) % NP] = hs[k]; Pq[(k - W2) % NP] = hq[k]; }  // P(i_begin + k - W2)
+        float sf[W2 + W1], sqf[W2 + W1];  // short window position p = o + j
+#pragma unroll
+        for (int j = 0; j < W2 + W1; ++j) {
+            const double c = hs[j + W1] - hs[j], cq = hq[j + W1] - hq[j];
+            sf[j] = (float)c;
+            sqf[j] = (float)cq;
+            if (j >= W1) ar[(j - W2 + NA2) % NA2] = sgk_arole<W1, true>(c, cq);
+            if (j >= W2) { ss[(j - W2) % NS] = sf[j]; sqs[(j - W2) % NS] = sqf[j]; }
+        }
+#pragma unroll
+        for (int j = 0; j < W2; ++j) ls[(j - W2 + NL) % NL] = sgk_lside_halves<W2>(sf[j], sqf[j], sf[j + W1], sqf[j + W1]);
+    }
+
     template <int... Qs>
     __device__ __forceinline__ void block(std::integer_sequence<int, Qs...>) {
         (quad<4 * Qs>(), ...);
@@ -570,10 +633,10 @@ __device__ __forceinline__ void lz_flush(uint32_t *ring, unsigned long long *bm,
 //   steps  : indices every lane runs (wave-uniform: warm-up + chunk length)
 //   active : whether this lane runs in this pass
 // Writes the lane's bitmap words, its hot-run records and (speculative pass) snap.init / snap.at_e.
-template <int W1, typename T, bool FLAGGED>
+template <int W1, typename T, bool FLAGGED, bool LEAD = false>
 __device__ __forceinline__ void pass_lazy(const ReadCtx<T> &rc, bool given, int lead, int steps, bool active, int s,
                                           int e, LzLds *L, const RepairCtx *rep, bool by_progress = false) {
-    using LP = LazyPass<W1, T, FLAGGED>;
+    using LP = LazyPass<W1, T, FLAGGED, LEAD>;
     constexpr int W2 = LP::W2, R = LP::R;
     if (!__any(active)) return;
     const int l = lane_id();
@@ -609,13 +672,19 @@ __device__ __forceinline__ void pass_lazy(const ReadCtx<T> &rc, bool given, int 
         }
 #pragma unroll
         for (int k = 0; k < LP::NP; ++k) { f.Ps[k] = 0.0; f.Pq[k] = 0.0; }
-        f.init_rings(w, std::make_integer_sequence<int, 2 * W2>{});
+        if constexpr (LEAD) f.init_lead(w);
+        else f.init_rings(w, std::make_integer_sequence<int, 2 * W2>{});
         // The statistic is defined as 0 at the read's first W1 indices (events.c:332-338): their A side is a window
         // position in front of the read.  Lane 0 marks those ring entries (NaN): the evaluation cannot be certified
-        // and the exact path returns the 0.
+        // and the exact path returns the 0.  (LEAD: the ring also holds the positions 0 .. W1-1, which are real.)
         if (i_begin == 0) {
+            if constexpr (LEAD) {
 #pragma unroll
-            for (int k = 0; k < LP::NA; ++k) f.ar[k].va = __builtin_nan("");
+                for (int k = 1; k <= W1; ++k) f.ar[LP::NA2 - k].va = __builtin_nan("");
+            } else {
+#pragma unroll
+                for (int k = 0; k < LP::NA; ++k) f.ar[k].va = __builtin_nan("");
+            }
         }
     }
     // leading samples of the first block: x[i_begin + W2 .. +16)
@@ -840,7 +909,8 @@ __device__ void replay_long_runs(const ReadCtx<T> &rc, LzLds *L, const RepairCtx
 //
 // MULTI (k_event_multi): the wave holds 64 / lanes reads, `lanes` consecutive lanes each (rc, b and the return code are
 // per lane; a = 0, mode 0, no seg): a short read on all 64 lanes spends more steps on warm-ups than on its samples.
-template <int W1, typename T, bool FLAGGED, bool MULTI = false>
+// LEAD: the form of the fast pass (LazyPass).
+template <int W1, typename T, bool FLAGGED, bool MULTI = false, bool LEAD = false>
 __device__ __forceinline__ int detect_span(const ReadCtx<T> &rc, EvHeader *hdr, LzLds *L, const RepairCtx *rep,
                                            const int a, const int b, const int mode, const int lead_override,
                                            SegState *seg, const int lanes = 64) {
@@ -908,8 +978,8 @@ __device__ __forceinline__ int detect_span(const ReadCtx<T> &rc, EvHeader *hdr, 
     const int l = lane_id();
     const uint32_t pol = FLAGGED ? 0u : prio_policy(rc.dev);
     for (int iter = 0; iter < 66; ++iter) {
-        pass_lazy<W1, T, FLAGGED>(rc, first ? (mode == 2 && c == 0) : true, first ? lead_c : 0, first ? TT : Kmax, run, s, e,
-                                  L, rep, first && (pol == 1u || pol == 2u));
+        pass_lazy<W1, T, FLAGGED, LEAD>(rc, first ? (mode == 2 && c == 0) : true, first ? lead_c : 0, first ? TT : Kmax, run,
+                                        s, e, L, rep, first && (pol == 1u || pol == 2u));
         __syncthreads();
         // chunk c is right iff it started (at s) from the state chunk c-1 ended with
         const LzSnapState pe = L->snap.at_e[c > 0 ? l - 1 : l];

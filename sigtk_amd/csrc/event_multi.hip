@@ -23,8 +23,9 @@ __global__ __launch_bounds__(64, (W1 == 3 ? DET_WAVES_DNA : DET_WAVES_RNA)) void
     // (with segments shorter than multi_max -- tests -- a read can be short and long at once: the segments have it)
     const bool mine = has && !(a.max_segs && rc.n >= (int64_t)a.long_min);  // (no tail split in a batch with packed reads)
     if (!mine) rc.n = 0;
-    const int rcode = detect_span<W1, T, false, true>(rc, a.hdr, &L.lz, nullptr, 0, (int)rc.n, 0, a.lead_override, nullptr,
-                                                      lanes);
+    constexpr bool MULTI_LEAD = W1 == 3 && ((SGK_EVENT_LEAD) & 4) != 0;  // (off in the shipped build, event_detect.h)
+    const int rcode = detect_span<W1, T, false, true, MULTI_LEAD>(rc, a.hdr, &L.lz, nullptr, 0, (int)rc.n, 0,
+                                                                  a.lead_override, nullptr, lanes);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __syncthreads();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");

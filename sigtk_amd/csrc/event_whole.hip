@@ -4,6 +4,10 @@
 
 namespace sgk {
 
+// (the DNA preset's instances take the leading-edge form of the fast pass: SGK_EVENT_LEAD, event_detect.h)
+template <int W1>
+constexpr bool EV_LEAD = ((SGK_EVENT_LEAD) & (W1 == 3 ? 1 : 2)) != 0;
+
 template <int W1, typename T>
 __global__ __launch_bounds__(64, (W1 == 3 ? DET_WAVES_DNA : DET_WAVES_RNA)) void k_event(EvArgs a) {
     __shared__ EventLds L;
@@ -21,10 +25,10 @@ __global__ __launch_bounds__(64, (W1 == 3 ? DET_WAVES_DNA : DET_WAVES_RNA)) void
     unsigned long long t0 = 0ull, t1 = 0ull;
     if (a.dev & SGK_DEV_TRACE) t0 = wall_clock64();
     int rcode = 0;
-    if (!(a.dev & SGK_DEV_NO_DETECT)) rcode = detect_span<W1, T, false>(rc, a.hdr, &L.lz, nullptr, 0, (int)rc.n, 0, a.lead_override, nullptr);
+    if (!(a.dev & SGK_DEV_NO_DETECT)) rcode = detect_span<W1, T, false, false, EV_LEAD<W1>>(rc, a.hdr, &L.lz, nullptr, 0, (int)rc.n, 0, a.lead_override, nullptr);
     if (a.dev & SGK_DEV_TRACE) t1 = wall_clock64();
 #else
-    const int rcode = detect_span<W1, T, false>(rc, a.hdr, &L.lz, nullptr, 0, (int)rc.n, 0, a.lead_override, nullptr);
+    const int rcode = detect_span<W1, T, false, false, EV_LEAD<W1>>(rc, a.hdr, &L.lz, nullptr, 0, (int)rc.n, 0, a.lead_override, nullptr);
 #endif
     // the bitmap words of every lane (and the replay's atomics) are complete before any lane of this workgroup reads
     // them back.  Workgroup scope: the wave's own CU only -- an agent-scope release / acquire pair here writes back and

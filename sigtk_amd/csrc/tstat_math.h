@@ -256,10 +256,10 @@ SGK_TM SgkARole sgk_arole(double S, double Sq) {
 // (The two conditions of the certificate come back separately: a wave forms its mask as
 // __ballot(cv_ok) & __ballot(tail_ok), two compares and one scalar AND.  ANDed as bools in front of one ballot, the
 // second compare's mask went through a vector 0/1 and back: v_cndmask 0, 1 + v_cmp_ne 0 per index.)
+// (B side as its two floats, RN32 of the exact sums: the leading-edge form of LazyPass converts a window's sums once,
+// when the window is formed, and rings them; every operation below and its rounding are the same either way)
 template <int W>
-SGK_TM float sgk_tstat_try_ab(double S, double Sq, const SgkARole &a, bool &cv_ok, bool &tail_ok) {
-    const float sum2 = (float)S;
-    const float sumsq2 = (float)Sq;
+SGK_TM float sgk_tstat_try_ab(float sum2, float sumsq2, const SgkARole &a, bool &cv_ok, bool &tail_ok) {
     const float mean2 = sgk_div_f32<W>(sum2);
     const float m2sq = mean2 * mean2;
     const float q2 = sgk_div_f32<W>(sumsq2);
@@ -270,6 +270,10 @@ SGK_TM float sgk_tstat_try_ab(double S, double Sq, const SgkARole &a, bool &cv_o
     const float delta = mean2 - a.mean1;
     const float cvw = sgk_div_f32<W>(cv);
     return sgk_tail_f32(delta, cvw, tail_ok);
+}
+template <int W>
+SGK_TM float sgk_tstat_try_ab(double S, double Sq, const SgkARole &a, bool &cv_ok, bool &tail_ok) {
+    return sgk_tstat_try_ab<W>((float)S, (float)Sq, a, cv_ok, tail_ok);
 }
 template <int W>
 SGK_TM float sgk_tstat_try_ab(double S, double Sq, const SgkARole &a, bool &ok) {
@@ -392,6 +396,35 @@ SGK_TM SgkLSide sgk_lside(double S, double Sq) {
     SgkLSide s;
     s.m = (float)S;
     s.q = (float)Sq * (float)W;
+    s.v = fmaf(-s.m, s.m, s.q);
+    return s;
+}
+// The same estimates from the f32 sums of the window's two halves (W = 2 * W1; s1 = RN32(S1), sq1 = RN32(Sq1), ...:
+// what the short statistic of the leading-edge form has converted anyway, event_detect.h: LazyPass<.., LEAD>) -- no
+// f64 subtraction and no conversion of its own:
+//   m' = RN(s1 + s2),  q' = RN(RN(sq1 + sq2) * w),  v' = RN(q' - m'*m') (FMA).
+// What changes against the accounting above, with T = |S1| + |S2| (u = 2^-24):
+//   q': three roundings of non-negative terms instead of two: one more u q'.
+//   m': |m' - S| <= u|S1| + u|S2| + u|m'| <= 2.01u T, which is NOT bounded by u|S| when the halves have opposite signs
+//       (pA values may be negative).  It is bounded through the sums of squares: S1^2 <= (w/2) sum x^2 (Cauchy-Schwarz)
+//       and fl(x*x) >= (1-u) x*x, so T^2 <= 2 (S1^2 + S2^2) <= w Sq / (1-u) <= q' (1 + 5u):  T <= sqrt(q') (1 + 2.5u),
+//       and |S| <= T, |m'| <= T (1+u)^2 likewise.
+//   variance: |m'^2 - S^2| = |m' - S| |m' + S| <= 2.01u T (2 + 2.01u) T <= 4.04u q', where m = RN32(S) gave 2.01u q: with
+//       q' that is 3.1u q' more per side, 20.5u (qA+qB) + u V in all against the slack of 2^-19 = 32u.
+//   delta: |SB - SA| <= |mB' - mA'| + e,  e = 2.01u (TA + TB) <= 2.01u (1 + 2.5u) sqrt(2 (qA'+qB')) <= 2.87u sqrt(Qs).
+//       The 2^-20 (|mA|+|mB|) term keeps covering what it covered (the reference's roundings of its means, relative to
+//       |S| <= |m'| + 2.01u T: second order); e is charged to the other side.  Dub <= |mA'| + |mB'| + 2^-20 (..) <=
+//       1.415 sqrt(Qs), so (Dub + e)^2 <= Dub^2 + 2 * 1.415 * 2.87u Qs + e^2 <= Dub^2 + 8.2u Qs, and times
+//       w (1 + 2^-16) that is at most 8.2 w / 81 = 1.42 (w = 14; 0.61 for w = 6) in units of the right-hand side's
+//       81 u Qs: 21.9u (qA+qB) of the 32u.  The constants of sgk_long_cold stand as they are.
+// The two forms may be mixed in one test (each side's error is priced on its own).  tools/long_cold_check.cpp runs
+// this form on 10^9 window pairs per w -- same-sign, mixed-sign, constant, with steps, steered to a statistic of ~9 --
+// against sgk_tstat_ref: no violation (profiles/event_leading_window.md).
+template <int W>
+SGK_TM SgkLSide sgk_lside_halves(float s1, float sq1, float s2, float sq2) {
+    SgkLSide s;
+    s.m = s1 + s2;
+    s.q = (sq1 + sq2) * (float)W;
     s.v = fmaf(-s.m, s.m, s.q);
     return s;
 }
