@@ -47,6 +47,14 @@ static_assert(LzCfg<3>::NP >= 8 && LzCfg<7>::NP >= 16, "prefix ring holds P(i) .
 #define SGK_EVENT_LEAD 1
 #endif
 
+// Which passes keep the lazy long detector's bookkeeping as a mask history (LazyPass::BOOK, below), as bits: 1 the passes
+// on the leading-edge form (k_event<3, *>, shipped), 2 the other unflagged passes (k_event<7, *>, k_event_multi,
+// k_event_seg), 4 the fallback's.  0 is the form with lm / r0 in vector registers and a compare per index
+// (tools/build_variant.sh <tag> -DSGK_EVENT_BOOK=0); profiles/event_bookkeeping.md has the listings.
+#ifndef SGK_EVENT_BOOK
+#define SGK_EVENT_BOOK 1
+#endif
+
 constexpr int LZ_NONE = -(1 << 29);   // "no mask" / far in the past (block-relative positions drift by -16 per block)
 constexpr int LZ_NREC = 8;            // hot long-detector runs a lane can record per pass (more: read -> exact fallback)
 constexpr int LZ_RING_WORDS = 16;     // per-lane bitmap ring: 512 positions
@@ -269,6 +277,9 @@ struct LazyPass {
     static constexpr int NA2 = LEAD ? 2 * NA : NA;   // LEAD: an A side waits 2 * W1 steps for its index
     static constexpr int NS = LEAD ? NA : 1;         // LEAD: ring of the short windows' f32 sums, > W1
     static_assert(NA2 > (LEAD ? 2 : 1) * W1 && (!LEAD || NS > W1) && R % NA2 == 0, "ring depths");
+    // BOOK: the long detector's mask as a history of lane masks, its run start as one register (see moff / rs)
+    static constexpr bool BOOK = ((SGK_EVENT_BOOK) & (FLAGGED ? 4 : (LEAD ? 1 : 2))) != 0;
+    static constexpr int NM = W1 - H1;   // an emission masks the long detector at its own index and at the NM - 1 behind it
     // rings
     double Ps[NP], Pq[NP];        // running prefix sums of x and of fl(x*x); slot of P(k) = k mod NP
     SgkARole ar[NA2];             // short A side of window position p at slot p mod NA2
@@ -286,6 +297,13 @@ struct LazyPass {
     uint32_t bw;                  // bitmap word (32 positions) that holds position j - H1 - 1, the usual emitted peak
     // lazy long detector
     int lm, r0;                   // short peak position at the last reset (masked while i <= lm + W1); last reset
+    // BOOK, instead of lm and r0.  An emission is the last reset of its peak and masks the long detector up to
+    // peak_pos + W1.  The usual emission's peak lies exactly H1 + 1 indices back: it masks this index and the next
+    // NM - 1, the same in every lane, so "masked" is a short history of emission masks on the scalar unit and the first
+    // index behind reset and mask is the constant u + NM.  The rare emission (an older peak) sits behind a branch and
+    // forms both from sp there; its mask ends at least one index earlier.
+    lmask_t moff[NM - 1];         // moff[k]: lanes an earlier emission masks at the k-th index from the current one
+    int rs;                       // max(r0, lm + W1 + 1): where the long detector's current run starts (block-relative)
     lmask_t hot;
     int nrec;
     // geometry
@@ -418,18 +436,39 @@ struct LazyPass {
         // the usual emitted peak was set exactly H1+1 indices ago: its position is the same in every lane, and so
         // is its bit in the lane's current bitmap word
         const uint32_t bit = 1u << ((jb + u - H1 - 1) & 31);
+        // BOOK: lanes whose long detector is masked at this index (off) and at the following ones (nx), see moff
+        lmask_t off = 0ull, nx[NM - 1];
         if (SLOW && oldpeak) {
             // some lane holds a peak older than the bitmap ring reaches (or one from before the pass)
             if (lane_of(em)) {
                 lz_emit_slow(ring, bm, flushed, i_begin, s, e, jb + sp, jb + u);
-                lm = sp;
-                r0 = u;
+                if constexpr (BOOK) {
+                    rs = max(u, sp + W1 + 1);
+                } else {
+                    lm = sp;
+                    r0 = u;
+                }
+            }
+            if constexpr (BOOK) {
+                off = moff[0];
+#pragma unroll
+                for (int k = 0; k < NM - 1; ++k) nx[k] = k + 1 < NM - 1 ? moff[k + 1] : 0ull;
+                book_mask_from_sp<NM - 1>(em, u, off, nx);
             }
         } else {
-            if (lane_of(em)) {
-                bw |= bit;
-                lm = sp;
-                r0 = u;
+            if constexpr (BOOK) {
+                if (lane_of(em)) bw |= bit;
+                rs = lane_of(em) ? u + NM : rs;
+                const lmask_t eusual = em & hist[H1];
+                off = moff[0] | eusual;
+#pragma unroll
+                for (int k = 0; k < NM - 1; ++k) nx[k] = k + 1 < NM - 1 ? (moff[k + 1] | eusual) : eusual;
+            } else {
+                if (lane_of(em)) {
+                    bw |= bit;
+                    lm = sp;
+                    r0 = u;
+                }
             }
             const lmask_t erare = em & ~hist[H1];
             if (erare != 0ull) {
@@ -438,7 +477,10 @@ struct LazyPass {
                     const int p = jb + sp, own = s - i_begin;
                     if (p >= own) atomicOr(&ring[(p >> 5) & (LZ_RING_WORDS - 1)], 1u << (p & 31));
                     else if (jb >= own) ring[LZ_PRE] = (uint32_t)(i_begin + p);  // inherited, see lz_emit_slow
+                    if constexpr (BOOK) rs = max(u, sp + W1 + 1);
                 }
+                // (sp <= u - H1 - 2: masked up to index u + NM - 2 at the most)
+                if constexpr (BOOK) book_mask_from_sp<NM - 2>(erare, u, off, nx);
             }
         }
         sv = lane_of(upd) ? v : sv;
@@ -459,11 +501,35 @@ struct LazyPass {
         // peak's last reset (its emission); resets in between leave nothing behind
         const lmask_t rec = dom & hot;
         if (rec != 0ull) {
-            if (lane_of(rec)) nrec = lz_record(runs, nrec, ib + max(r0, lm + W1 + 1), ib + u, s, e, n);
+            if (lane_of(rec)) nrec = lz_record(runs, nrec, ib + run_start(), ib + u, s, e, n);
         }
-        lmask_t on = __ballot(lm < u - W1);
+        lmask_t on;
+        if constexpr (BOOK) {
+            on = ~off;
+#pragma unroll
+            for (int k = 0; k < NM - 1; ++k) {
+                // a frozen lane's mask does not age, like its hist[]
+                if constexpr (SLOW) moff[k] = (nx[k] & live) | (moff[k] & ~live);
+                else moff[k] = nx[k];
+            }
+        } else {
+            on = __ballot(lm < u - W1);
+        }
         if constexpr (SLOW) on &= live;
         hot = (hot & ~dom) | (on & hck & (~dom | em));
+    }
+    // first index (block-relative) of the long detector's current run: behind its last reset and behind the mask
+    __device__ __forceinline__ int run_start() const {
+        if constexpr (BOOK) return rs;
+        else return max(r0, lm + W1 + 1);
+    }
+    // BOOK: lanes `m` emitted a peak at sp that need not lie H1 + 1 indices back: their mask reaches up to sp + W1
+    // (KN: how many of the following indices it can reach)
+    template <int KN>
+    __device__ __forceinline__ void book_mask_from_sp(const lmask_t m, const int u, lmask_t &off, lmask_t (&nx)[NM - 1]) const {
+        off |= m & __ballot(sp + W1 >= u);
+#pragma unroll
+        for (int k = 0; k < KN; ++k) nx[k] |= m & __ballot(sp + W1 >= u + k + 1);
     }
     // the bitmap word moves on when position j - H1 - 1 enters the next 32-position span
     __device__ __forceinline__ void bw_advance() {
@@ -699,6 +765,9 @@ __device__ __forceinline__ void pass_lazy(const ReadCtx<T> &rc, bool given, int 
     f.bw = 0u;
     f.lm = LZ_NONE;
     f.r0 = 0;  // the (pseudo) reset a speculative pass starts from; index 0 for lane 0
+    f.rs = 0;
+#pragma unroll
+    for (int k = 0; k < LP::NM - 1; ++k) f.moff[k] = 0ull;
     if (__any(given)) {
         LzSnapState st = L->snap.st0[l];
         if (!given) { st.sp = -1; st.sv = FLT_MAX; st.lm = LZ_NONE; st.r0 = i_begin; st.bits = 0u; }  // fresh
@@ -712,6 +781,12 @@ __device__ __forceinline__ void pass_lazy(const ReadCtx<T> &rc, bool given, int 
 #pragma unroll
         for (int k = 0; k <= LP::H1; ++k) f.hist[k] = __ballot((st.bits & 1u) && st.sp == i_begin - 1 - k);
         f.r0 = st.r0 - i_begin;
+        if constexpr (LP::BOOK) {
+            const int mt = st.lm == LZ_NONE ? LZ_NONE : st.lm - i_begin;  // masked_to, below NM - 1: its emission lies behind
+            f.rs = max(st.r0 - i_begin, mt + 1);
+#pragma unroll
+            for (int k = 0; k < LP::NM - 1; ++k) f.moff[k] = __ballot(mt >= k);
+        }
     }
     f.nrec = 0;
     f.done = ~__ballot(active);
@@ -738,12 +813,15 @@ __device__ __forceinline__ void pass_lazy(const ReadCtx<T> &rc, bool given, int 
         const bool ip = lane_of(f.inpk);
         st.sv = f.sv;
         st.sp = ip ? ib + f.sp : -1;
-        st.lm = (f.lm + W1 < 0) ? LZ_NONE : ib + f.lm + W1;  // normalised when it no longer masks
+        // normalised when it no longer masks.  (BOOK: at a block's start every emission lies behind, so a run start in
+        // front -- rs > 0 -- is the mask's end + 1, and one behind says that nothing masks)
+        if constexpr (LP::BOOK) st.lm = (f.rs - 1 < 0) ? LZ_NONE : ib + f.rs - 1;
+        else st.lm = (f.lm + W1 < 0) ? LZ_NONE : ib + f.lm + W1;
         // what the long detector's current run STARTS with: the first index behind the last reset that is not masked.
         // (The reset index alone is not enough once the mask is normalised away: a lane that takes this state over
         // would replay a hot run from the reset, through indices the mask hid from the reference's long detector --
         // found by the soak with a 16-sample warm-up, tests/golden/soak_seed41_*.npz.)
-        st.r0 = ib + max(f.r0, f.lm + W1 + 1);
+        st.r0 = ib + f.run_start();
         st.bits = (ip ? 1u : 0u) | ((ip && lane_of(f.val)) ? 2u : 0u) | ((ip && lane_of(f.strong)) ? 4u : 0u) |
                   (lane_of(f.hot) ? 8u : 0u);
         return st;
@@ -787,8 +865,12 @@ __device__ __forceinline__ void pass_lazy(const ReadCtx<T> &rc, bool given, int 
         f.cur = nxt;
         // rebase the block-relative positions
         f.sp -= R;
-        f.lm = f.lm < LZ_NONE ? LZ_NONE : f.lm - R;
-        f.r0 -= R;
+        if constexpr (LP::BOOK) {
+            f.rs -= R;
+        } else {
+            f.lm = f.lm < LZ_NONE ? LZ_NONE : f.lm - R;
+            f.r0 -= R;
+        }
         if constexpr (FLAGGED) f.dirty = f.dirty < -(1 << 20) ? f.dirty : f.dirty - R;
         jb += R;
         if (jb == q1) __builtin_amdgcn_s_setprio(2);
@@ -806,7 +888,7 @@ __device__ __forceinline__ void pass_lazy(const ReadCtx<T> &rc, bool given, int 
             // recorded HERE: the lane may step on (other lanes of the wave have more to do, and in k_event_multi their
             // reads are longer) through whatever lies behind the read, and its run bookkeeping with it
             if ((reach & f.hot) != 0ull) {
-                if (lane_of(reach & f.hot) && e == n) f.nrec = lz_record(f.runs, f.nrec, nb + max(f.r0, f.lm + W1 + 1), n, s, e, n);
+                if (lane_of(reach & f.hot) && e == n) f.nrec = lz_record(f.runs, f.nrec, nb + f.run_start(), n, s, e, n);
             }
             f.done |= reach;
             // ... and it steps on without the exact redo of uncertified statistics: whatever it decides from here on
@@ -882,9 +964,11 @@ __device__ inline void replay_run(const ReadCtx<T> &rc, const RepairCtx *rep, bo
 }
 // ... over the recorded hot runs of the wave's lanes.  bits_lo: first index of the span this wave owns (a run that
 // began in front of it leaves its peaks in front of the span to whoever replays the span's cross runs)
+// (`inline`, as above: out of line -- where k_event<3, short> with the mask-history bookkeeping had it -- the read's
+// context has to live in scratch for it)
 template <int W1, typename T, bool FLAGGED>
-__device__ void replay_long_runs(const ReadCtx<T> &rc, LzLds *L, const RepairCtx *rep, bool active, int bits_lo,
-                                 EvHeader *hdr) {
+__device__ inline void replay_long_runs(const ReadCtx<T> &rc, LzLds *L, const RepairCtx *rep, bool active, int bits_lo,
+                                        EvHeader *hdr) {
     const int l = lane_id();
     const int nrec = active ? L->nrec[l] : 0;
     for (int k = 0; k < LZ_NREC; ++k) {

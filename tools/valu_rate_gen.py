@@ -105,6 +105,43 @@ tests.append(("mix_cvt_fma_f64", "v_cvt_f64_f32 %8, %0\\n v_fma_f64 %9, %9, %17,
 tests.append(("add_f32_x7_ds_write_b64", "v_add_f32 %0, %0, %16\\n v_add_f32 %1, %1, %16\\n v_add_f32 %2, %2, %16\\n ds_write_b64 %18, %8\\n v_add_f32 %4, %4, %16\\n v_add_f32 %5, %5, %16\\n v_add_f32 %6, %6, %16\\n v_add_f32 %7, %7, %16\\n ", 7))
 tests.append(("add_f64_x7_ds_write_b128", "v_add_f64 %8, %8, %17\\n v_add_f64 %9, %9, %17\\n v_add_f64 %10, %10, %17\\n ds_write_b64 %18, %8\\n v_add_f64 %12, %12, %17\\n v_add_f64 %13, %13, %17\\n v_add_f64 %14, %14, %17\\n v_add_f64 %15, %15, %17\\n ", 7))
 
+# ---- "keep or take" under a lane mask (profiles/event_bookkeeping.md): the select against plain instructions in a region
+# of narrowed exec.  A body is 4 regions (x 8 per iteration); its cost in cycles is 8 x the first column, per region a
+# quarter of that.  The mask is set in the body (half of the lower lanes); exec is whole again behind every region.
+MASK = "s_mov_b64 s[22:23], 0x0f0f0f0f\\n "
+REGION_OPS = ["v_mov_b32 %{r}, %16", "v_or_b32 %{r2}, %{r2}, %16", "v_mov_b32 %{r3}, %16"]
+def region(i, nv, salu):
+    ops = [op.format(r=i, r2=(i + 1) % 4, r3=(i + 2) % 4) for op in REGION_OPS[:nv]]
+    s = "s_and_saveexec_b64 s[20:21], s[22:23]\\n "
+    for op in ops:
+        s += op + "\\n " + ("s_and_b64 s[24:25], s[26:27], s[26:27]\\n " if salu else "")
+    return s + "s_mov_b64 exec, s[20:21]\\n "
+for nv in (1, 2, 3):
+    for gap in (0, 1):
+        for salu in (0, 1):
+            name = "exec_region_%dvalu%s%s" % (nv, "_gap_add" if gap else "", "_salu_1to1" if salu else "")
+            body = MASK
+            for i in range(4):
+                body += region(i, nv, salu)
+                if gap:   # independent vector work between the regions
+                    body += "v_add_f32 %%%d, %%%d, %%16\\n " % (4 + i, 4 + i) + ("s_and_b64 s[24:25], s[26:27], s[26:27]\\n " if salu else "")
+            tests.append((name, body, 4 * (nv + gap)))
+# the selects those regions would replace: 4 x nv of them, with the same gap and scalar load
+for nv in (1, 2, 3):
+    for gap in (0, 1):
+        for salu in (0, 1):
+            name = "select_%dvalu%s%s" % (nv, "_gap_add" if gap else "", "_salu_1to1" if salu else "")
+            body = MASK
+            for i in range(4):
+                for k in range(nv):
+                    body += "v_cndmask_b32 %%%d, %%%d, %%16, s[22:23]\\n " % ((i + k) % 4, (i + k) % 4) + ("s_and_b64 s[24:25], s[26:27], s[26:27]\\n " if salu else "")
+                if gap:
+                    body += "v_add_f32 %%%d, %%%d, %%16\\n " % (4 + i, 4 + i) + ("s_and_b64 s[24:25], s[26:27], s[26:27]\\n " if salu else "")
+            tests.append((name, body, 4 * (nv + gap)))
+T("v_addc_co_u32_vcc", "v_addc_co_u32 {d}, vcc, {d}, {d}, vcc")
+T("v_addc_co_u32_e64_sgpr", "v_addc_co_u32_e64 {d}, s[20:21], {d}, {d}, s[22:23]")
+tests.append(("v_addc_co_u32_e64_salu_1to1", "".join("v_addc_co_u32_e64 %%%d, s[20:21], %%%d, %%%d, s[22:23]\\n s_and_b64 s[24:25], s[26:27], s[26:27]\\n " % (i, i, i) for i in range(4)), 4))
+
 out = []
 for name, body, valu in tests:
     out.append('DEFINE_KERNEL(%s, "%s")' % (name, body))

@@ -81,6 +81,33 @@ DEFINE_KERNEL(mix_add_f32_add_f64, "v_add_f32 %0, %0, %16\n v_add_f64 %8, %8, %1
 DEFINE_KERNEL(mix_cvt_fma_f64, "v_cvt_f64_f32 %8, %0\n v_fma_f64 %9, %9, %17, %17\n v_cvt_f32_f64 %1, %10\n v_fma_f64 %11, %11, %17, %17\n v_cvt_f64_f32 %12, %2\n v_fma_f64 %13, %13, %17, %17\n v_cvt_f32_f64 %3, %14\n v_fma_f64 %15, %15, %17, %17\n ")
 DEFINE_KERNEL(add_f32_x7_ds_write_b64, "v_add_f32 %0, %0, %16\n v_add_f32 %1, %1, %16\n v_add_f32 %2, %2, %16\n ds_write_b64 %18, %8\n v_add_f32 %4, %4, %16\n v_add_f32 %5, %5, %16\n v_add_f32 %6, %6, %16\n v_add_f32 %7, %7, %16\n ")
 DEFINE_KERNEL(add_f64_x7_ds_write_b128, "v_add_f64 %8, %8, %17\n v_add_f64 %9, %9, %17\n v_add_f64 %10, %10, %17\n ds_write_b64 %18, %8\n v_add_f64 %12, %12, %17\n v_add_f64 %13, %13, %17\n v_add_f64 %14, %14, %17\n v_add_f64 %15, %15, %17\n ")
+DEFINE_KERNEL(exec_region_1valu, "s_mov_b64 s[22:23], 0x0f0f0f0f\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %0, %16\n s_mov_b64 exec, s[20:21]\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %1, %16\n s_mov_b64 exec, s[20:21]\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %2, %16\n s_mov_b64 exec, s[20:21]\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %3, %16\n s_mov_b64 exec, s[20:21]\n ")
+DEFINE_KERNEL(exec_region_1valu_salu_1to1, "s_mov_b64 s[22:23], 0x0f0f0f0f\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %0, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_mov_b64 exec, s[20:21]\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %1, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_mov_b64 exec, s[20:21]\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %2, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_mov_b64 exec, s[20:21]\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %3, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_mov_b64 exec, s[20:21]\n ")
+DEFINE_KERNEL(exec_region_1valu_gap_add, "s_mov_b64 s[22:23], 0x0f0f0f0f\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %0, %16\n s_mov_b64 exec, s[20:21]\n v_add_f32 %4, %4, %16\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %1, %16\n s_mov_b64 exec, s[20:21]\n v_add_f32 %5, %5, %16\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %2, %16\n s_mov_b64 exec, s[20:21]\n v_add_f32 %6, %6, %16\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %3, %16\n s_mov_b64 exec, s[20:21]\n v_add_f32 %7, %7, %16\n ")
+DEFINE_KERNEL(exec_region_1valu_gap_add_salu_1to1, "s_mov_b64 s[22:23], 0x0f0f0f0f\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %0, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_mov_b64 exec, s[20:21]\n v_add_f32 %4, %4, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %1, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_mov_b64 exec, s[20:21]\n v_add_f32 %5, %5, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %2, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_mov_b64 exec, s[20:21]\n v_add_f32 %6, %6, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %3, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_mov_b64 exec, s[20:21]\n v_add_f32 %7, %7, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n ")
+DEFINE_KERNEL(exec_region_2valu, "s_mov_b64 s[22:23], 0x0f0f0f0f\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %0, %16\n v_or_b32 %1, %1, %16\n s_mov_b64 exec, s[20:21]\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %1, %16\n v_or_b32 %2, %2, %16\n s_mov_b64 exec, s[20:21]\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %2, %16\n v_or_b32 %3, %3, %16\n s_mov_b64 exec, s[20:21]\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %3, %16\n v_or_b32 %0, %0, %16\n s_mov_b64 exec, s[20:21]\n ")
+DEFINE_KERNEL(exec_region_2valu_salu_1to1, "s_mov_b64 s[22:23], 0x0f0f0f0f\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %0, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_or_b32 %1, %1, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_mov_b64 exec, s[20:21]\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %1, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_or_b32 %2, %2, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_mov_b64 exec, s[20:21]\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %2, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_or_b32 %3, %3, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_mov_b64 exec, s[20:21]\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %3, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_or_b32 %0, %0, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_mov_b64 exec, s[20:21]\n ")
+DEFINE_KERNEL(exec_region_2valu_gap_add, "s_mov_b64 s[22:23], 0x0f0f0f0f\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %0, %16\n v_or_b32 %1, %1, %16\n s_mov_b64 exec, s[20:21]\n v_add_f32 %4, %4, %16\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %1, %16\n v_or_b32 %2, %2, %16\n s_mov_b64 exec, s[20:21]\n v_add_f32 %5, %5, %16\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %2, %16\n v_or_b32 %3, %3, %16\n s_mov_b64 exec, s[20:21]\n v_add_f32 %6, %6, %16\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %3, %16\n v_or_b32 %0, %0, %16\n s_mov_b64 exec, s[20:21]\n v_add_f32 %7, %7, %16\n ")
+DEFINE_KERNEL(exec_region_2valu_gap_add_salu_1to1, "s_mov_b64 s[22:23], 0x0f0f0f0f\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %0, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_or_b32 %1, %1, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_mov_b64 exec, s[20:21]\n v_add_f32 %4, %4, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %1, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_or_b32 %2, %2, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_mov_b64 exec, s[20:21]\n v_add_f32 %5, %5, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %2, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_or_b32 %3, %3, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_mov_b64 exec, s[20:21]\n v_add_f32 %6, %6, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %3, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_or_b32 %0, %0, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_mov_b64 exec, s[20:21]\n v_add_f32 %7, %7, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n ")
+DEFINE_KERNEL(exec_region_3valu, "s_mov_b64 s[22:23], 0x0f0f0f0f\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %0, %16\n v_or_b32 %1, %1, %16\n v_mov_b32 %2, %16\n s_mov_b64 exec, s[20:21]\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %1, %16\n v_or_b32 %2, %2, %16\n v_mov_b32 %3, %16\n s_mov_b64 exec, s[20:21]\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %2, %16\n v_or_b32 %3, %3, %16\n v_mov_b32 %0, %16\n s_mov_b64 exec, s[20:21]\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %3, %16\n v_or_b32 %0, %0, %16\n v_mov_b32 %1, %16\n s_mov_b64 exec, s[20:21]\n ")
+DEFINE_KERNEL(exec_region_3valu_salu_1to1, "s_mov_b64 s[22:23], 0x0f0f0f0f\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %0, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_or_b32 %1, %1, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_mov_b32 %2, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_mov_b64 exec, s[20:21]\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %1, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_or_b32 %2, %2, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_mov_b32 %3, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_mov_b64 exec, s[20:21]\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %2, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_or_b32 %3, %3, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_mov_b32 %0, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_mov_b64 exec, s[20:21]\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %3, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_or_b32 %0, %0, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_mov_b32 %1, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_mov_b64 exec, s[20:21]\n ")
+DEFINE_KERNEL(exec_region_3valu_gap_add, "s_mov_b64 s[22:23], 0x0f0f0f0f\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %0, %16\n v_or_b32 %1, %1, %16\n v_mov_b32 %2, %16\n s_mov_b64 exec, s[20:21]\n v_add_f32 %4, %4, %16\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %1, %16\n v_or_b32 %2, %2, %16\n v_mov_b32 %3, %16\n s_mov_b64 exec, s[20:21]\n v_add_f32 %5, %5, %16\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %2, %16\n v_or_b32 %3, %3, %16\n v_mov_b32 %0, %16\n s_mov_b64 exec, s[20:21]\n v_add_f32 %6, %6, %16\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %3, %16\n v_or_b32 %0, %0, %16\n v_mov_b32 %1, %16\n s_mov_b64 exec, s[20:21]\n v_add_f32 %7, %7, %16\n ")
+DEFINE_KERNEL(exec_region_3valu_gap_add_salu_1to1, "s_mov_b64 s[22:23], 0x0f0f0f0f\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %0, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_or_b32 %1, %1, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_mov_b32 %2, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_mov_b64 exec, s[20:21]\n v_add_f32 %4, %4, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %1, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_or_b32 %2, %2, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_mov_b32 %3, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_mov_b64 exec, s[20:21]\n v_add_f32 %5, %5, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %2, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_or_b32 %3, %3, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_mov_b32 %0, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_mov_b64 exec, s[20:21]\n v_add_f32 %6, %6, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_and_saveexec_b64 s[20:21], s[22:23]\n v_mov_b32 %3, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_or_b32 %0, %0, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_mov_b32 %1, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n s_mov_b64 exec, s[20:21]\n v_add_f32 %7, %7, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n ")
+DEFINE_KERNEL(select_1valu, "s_mov_b64 s[22:23], 0x0f0f0f0f\n v_cndmask_b32 %0, %0, %16, s[22:23]\n v_cndmask_b32 %1, %1, %16, s[22:23]\n v_cndmask_b32 %2, %2, %16, s[22:23]\n v_cndmask_b32 %3, %3, %16, s[22:23]\n ")
+DEFINE_KERNEL(select_1valu_salu_1to1, "s_mov_b64 s[22:23], 0x0f0f0f0f\n v_cndmask_b32 %0, %0, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %1, %1, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %2, %2, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %3, %3, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n ")
+DEFINE_KERNEL(select_1valu_gap_add, "s_mov_b64 s[22:23], 0x0f0f0f0f\n v_cndmask_b32 %0, %0, %16, s[22:23]\n v_add_f32 %4, %4, %16\n v_cndmask_b32 %1, %1, %16, s[22:23]\n v_add_f32 %5, %5, %16\n v_cndmask_b32 %2, %2, %16, s[22:23]\n v_add_f32 %6, %6, %16\n v_cndmask_b32 %3, %3, %16, s[22:23]\n v_add_f32 %7, %7, %16\n ")
+DEFINE_KERNEL(select_1valu_gap_add_salu_1to1, "s_mov_b64 s[22:23], 0x0f0f0f0f\n v_cndmask_b32 %0, %0, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_add_f32 %4, %4, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %1, %1, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_add_f32 %5, %5, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %2, %2, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_add_f32 %6, %6, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %3, %3, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_add_f32 %7, %7, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n ")
+DEFINE_KERNEL(select_2valu, "s_mov_b64 s[22:23], 0x0f0f0f0f\n v_cndmask_b32 %0, %0, %16, s[22:23]\n v_cndmask_b32 %1, %1, %16, s[22:23]\n v_cndmask_b32 %1, %1, %16, s[22:23]\n v_cndmask_b32 %2, %2, %16, s[22:23]\n v_cndmask_b32 %2, %2, %16, s[22:23]\n v_cndmask_b32 %3, %3, %16, s[22:23]\n v_cndmask_b32 %3, %3, %16, s[22:23]\n v_cndmask_b32 %0, %0, %16, s[22:23]\n ")
+DEFINE_KERNEL(select_2valu_salu_1to1, "s_mov_b64 s[22:23], 0x0f0f0f0f\n v_cndmask_b32 %0, %0, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %1, %1, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %1, %1, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %2, %2, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %2, %2, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %3, %3, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %3, %3, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %0, %0, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n ")
+DEFINE_KERNEL(select_2valu_gap_add, "s_mov_b64 s[22:23], 0x0f0f0f0f\n v_cndmask_b32 %0, %0, %16, s[22:23]\n v_cndmask_b32 %1, %1, %16, s[22:23]\n v_add_f32 %4, %4, %16\n v_cndmask_b32 %1, %1, %16, s[22:23]\n v_cndmask_b32 %2, %2, %16, s[22:23]\n v_add_f32 %5, %5, %16\n v_cndmask_b32 %2, %2, %16, s[22:23]\n v_cndmask_b32 %3, %3, %16, s[22:23]\n v_add_f32 %6, %6, %16\n v_cndmask_b32 %3, %3, %16, s[22:23]\n v_cndmask_b32 %0, %0, %16, s[22:23]\n v_add_f32 %7, %7, %16\n ")
+DEFINE_KERNEL(select_2valu_gap_add_salu_1to1, "s_mov_b64 s[22:23], 0x0f0f0f0f\n v_cndmask_b32 %0, %0, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %1, %1, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_add_f32 %4, %4, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %1, %1, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %2, %2, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_add_f32 %5, %5, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %2, %2, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %3, %3, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_add_f32 %6, %6, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %3, %3, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %0, %0, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_add_f32 %7, %7, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n ")
+DEFINE_KERNEL(select_3valu, "s_mov_b64 s[22:23], 0x0f0f0f0f\n v_cndmask_b32 %0, %0, %16, s[22:23]\n v_cndmask_b32 %1, %1, %16, s[22:23]\n v_cndmask_b32 %2, %2, %16, s[22:23]\n v_cndmask_b32 %1, %1, %16, s[22:23]\n v_cndmask_b32 %2, %2, %16, s[22:23]\n v_cndmask_b32 %3, %3, %16, s[22:23]\n v_cndmask_b32 %2, %2, %16, s[22:23]\n v_cndmask_b32 %3, %3, %16, s[22:23]\n v_cndmask_b32 %0, %0, %16, s[22:23]\n v_cndmask_b32 %3, %3, %16, s[22:23]\n v_cndmask_b32 %0, %0, %16, s[22:23]\n v_cndmask_b32 %1, %1, %16, s[22:23]\n ")
+DEFINE_KERNEL(select_3valu_salu_1to1, "s_mov_b64 s[22:23], 0x0f0f0f0f\n v_cndmask_b32 %0, %0, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %1, %1, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %2, %2, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %1, %1, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %2, %2, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %3, %3, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %2, %2, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %3, %3, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %0, %0, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %3, %3, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %0, %0, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %1, %1, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n ")
+DEFINE_KERNEL(select_3valu_gap_add, "s_mov_b64 s[22:23], 0x0f0f0f0f\n v_cndmask_b32 %0, %0, %16, s[22:23]\n v_cndmask_b32 %1, %1, %16, s[22:23]\n v_cndmask_b32 %2, %2, %16, s[22:23]\n v_add_f32 %4, %4, %16\n v_cndmask_b32 %1, %1, %16, s[22:23]\n v_cndmask_b32 %2, %2, %16, s[22:23]\n v_cndmask_b32 %3, %3, %16, s[22:23]\n v_add_f32 %5, %5, %16\n v_cndmask_b32 %2, %2, %16, s[22:23]\n v_cndmask_b32 %3, %3, %16, s[22:23]\n v_cndmask_b32 %0, %0, %16, s[22:23]\n v_add_f32 %6, %6, %16\n v_cndmask_b32 %3, %3, %16, s[22:23]\n v_cndmask_b32 %0, %0, %16, s[22:23]\n v_cndmask_b32 %1, %1, %16, s[22:23]\n v_add_f32 %7, %7, %16\n ")
+DEFINE_KERNEL(select_3valu_gap_add_salu_1to1, "s_mov_b64 s[22:23], 0x0f0f0f0f\n v_cndmask_b32 %0, %0, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %1, %1, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %2, %2, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_add_f32 %4, %4, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %1, %1, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %2, %2, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %3, %3, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_add_f32 %5, %5, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %2, %2, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %3, %3, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %0, %0, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_add_f32 %6, %6, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %3, %3, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %0, %0, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_cndmask_b32 %1, %1, %16, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_add_f32 %7, %7, %16\n s_and_b64 s[24:25], s[26:27], s[26:27]\n ")
+DEFINE_KERNEL(v_addc_co_u32_vcc, "v_addc_co_u32 %0, vcc, %0, %0, vcc\n v_addc_co_u32 %1, vcc, %1, %1, vcc\n v_addc_co_u32 %2, vcc, %2, %2, vcc\n v_addc_co_u32 %3, vcc, %3, %3, vcc\n v_addc_co_u32 %4, vcc, %4, %4, vcc\n v_addc_co_u32 %5, vcc, %5, %5, vcc\n v_addc_co_u32 %6, vcc, %6, %6, vcc\n v_addc_co_u32 %7, vcc, %7, %7, vcc\n ")
+DEFINE_KERNEL(v_addc_co_u32_e64_sgpr, "v_addc_co_u32_e64 %0, s[20:21], %0, %0, s[22:23]\n v_addc_co_u32_e64 %1, s[20:21], %1, %1, s[22:23]\n v_addc_co_u32_e64 %2, s[20:21], %2, %2, s[22:23]\n v_addc_co_u32_e64 %3, s[20:21], %3, %3, s[22:23]\n v_addc_co_u32_e64 %4, s[20:21], %4, %4, s[22:23]\n v_addc_co_u32_e64 %5, s[20:21], %5, %5, s[22:23]\n v_addc_co_u32_e64 %6, s[20:21], %6, %6, s[22:23]\n v_addc_co_u32_e64 %7, s[20:21], %7, %7, s[22:23]\n ")
+DEFINE_KERNEL(v_addc_co_u32_e64_salu_1to1, "v_addc_co_u32_e64 %0, s[20:21], %0, %0, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_addc_co_u32_e64 %1, s[20:21], %1, %1, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_addc_co_u32_e64 %2, s[20:21], %2, %2, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n v_addc_co_u32_e64 %3, s[20:21], %3, %3, s[22:23]\n s_and_b64 s[24:25], s[26:27], s[26:27]\n ")
 static const Test tests[] = {
     {"v_add_f32", k_v_add_f32, 8},
     {"v_add_f32_dep", k_v_add_f32_dep, 8},
@@ -165,4 +192,31 @@ static const Test tests[] = {
     {"mix_cvt_fma_f64", k_mix_cvt_fma_f64, 8},
     {"add_f32_x7_ds_write_b64", k_add_f32_x7_ds_write_b64, 7},
     {"add_f64_x7_ds_write_b128", k_add_f64_x7_ds_write_b128, 7},
+    {"exec_region_1valu", k_exec_region_1valu, 4},
+    {"exec_region_1valu_salu_1to1", k_exec_region_1valu_salu_1to1, 4},
+    {"exec_region_1valu_gap_add", k_exec_region_1valu_gap_add, 8},
+    {"exec_region_1valu_gap_add_salu_1to1", k_exec_region_1valu_gap_add_salu_1to1, 8},
+    {"exec_region_2valu", k_exec_region_2valu, 8},
+    {"exec_region_2valu_salu_1to1", k_exec_region_2valu_salu_1to1, 8},
+    {"exec_region_2valu_gap_add", k_exec_region_2valu_gap_add, 12},
+    {"exec_region_2valu_gap_add_salu_1to1", k_exec_region_2valu_gap_add_salu_1to1, 12},
+    {"exec_region_3valu", k_exec_region_3valu, 12},
+    {"exec_region_3valu_salu_1to1", k_exec_region_3valu_salu_1to1, 12},
+    {"exec_region_3valu_gap_add", k_exec_region_3valu_gap_add, 16},
+    {"exec_region_3valu_gap_add_salu_1to1", k_exec_region_3valu_gap_add_salu_1to1, 16},
+    {"select_1valu", k_select_1valu, 4},
+    {"select_1valu_salu_1to1", k_select_1valu_salu_1to1, 4},
+    {"select_1valu_gap_add", k_select_1valu_gap_add, 8},
+    {"select_1valu_gap_add_salu_1to1", k_select_1valu_gap_add_salu_1to1, 8},
+    {"select_2valu", k_select_2valu, 8},
+    {"select_2valu_salu_1to1", k_select_2valu_salu_1to1, 8},
+    {"select_2valu_gap_add", k_select_2valu_gap_add, 12},
+    {"select_2valu_gap_add_salu_1to1", k_select_2valu_gap_add_salu_1to1, 12},
+    {"select_3valu", k_select_3valu, 12},
+    {"select_3valu_salu_1to1", k_select_3valu_salu_1to1, 12},
+    {"select_3valu_gap_add", k_select_3valu_gap_add, 16},
+    {"select_3valu_gap_add_salu_1to1", k_select_3valu_gap_add_salu_1to1, 16},
+    {"v_addc_co_u32_vcc", k_v_addc_co_u32_vcc, 8},
+    {"v_addc_co_u32_e64_sgpr", k_v_addc_co_u32_e64_sgpr, 8},
+    {"v_addc_co_u32_e64_salu_1to1", k_v_addc_co_u32_e64_salu_1to1, 4},
 };
