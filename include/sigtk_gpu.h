@@ -77,7 +77,8 @@ extern "C" {
  *        sgk_deflate, sgk_deflate_bound, sgk_deflate_block_bytes, sgk_job_set_record_frames and SGK_QTS_RECORDS with the
  *        qts_record* fields at the end of sgk_job_output_t (`qts --gpu-deflate`: records deflated on the GPU);
  *        sgk_slow5_text_* and SGK_SIGNAL_TEXT as input and output format of sgk_job_submit_qts (`qts` on text SLOW5);
- *        SGK_QTS_ZREC_FRAMES (`qts --gpu-inflate`: the frames of the record mode taken from the records inflated on the GPU). */
+ *        SGK_QTS_ZREC_FRAMES (`qts --gpu-inflate`: the frames of the record mode taken from the records inflated on the GPU);
+ *        sgk_sigraw_unit_samples, sgk_sigraw_gather and sgk_job_begin_zrec_signal (compressed records around an uncompressed signal). */
 #define SGK_VERSION_STRING "0.2.3"
 
 /* ---- error codes --------------------------------------------------------------- */
@@ -472,6 +473,26 @@ typedef struct sgk_aux_field {
 int sgk_zrec_tail_check(const uint8_t *inflated, const uint64_t *rec_offsets, const uint32_t *rec_lengths,
                         const uint32_t *tail_offsets, uint32_t n, const sgk_aux_field_t *fields /* host */,
                         uint32_t n_fields, uint32_t *status, void *stream);
+
+/* ---- the uncompressed signal of an inflated BLOW5 record, moved into the sample arena (additive to 0.2.3) -- */
+/* A record of a file with signal_press 0 holds its samples as plain little-endian int16 behind its head.
+ * sgk_sigraw_gather moves them, for n_reads records, to where sgk_batch_t wants them.  records: 16-byte aligned device
+ * buffer (else SGK_ERR_ALIGN, as for samples); record r is rec_lengths[r] bytes at records + rec_offsets[r], at any byte alignment; its signal is lengths[r]
+ * samples at sig_offsets[r] inside the record, at any residue of 16.  The kernel loads aligned 16-byte words and never
+ * reads outside [rec_offsets[r] rounded down to 16, rec_offsets[r] + rec_lengths[r] rounded up to 16): pad the buffer by
+ * 16 bytes at both ends.  samples (16-byte aligned) / offsets / lengths as in sgk_batch_t; offsets[r] must be a multiple
+ * of 8 samples, as sgk_job_begin lays them out.  Exactly samples[offsets[r] .. offsets[r] + lengths[r]) is written: the
+ * arena's padding keeps its bytes.  max_read_len (>= every lengths[r]) and n_samples (the arena's size, or 0 when not
+ * known) size the launch as in sgk_batch_t; a wrong value costs time only.  Work is dealt out in units of
+ * sgk_sigraw_unit_samples() samples over all reads, so one long read spreads over the device.  The call only enqueues.
+ * status[r]: 0 moved; 1 when sig_offsets[r] + 2 * lengths[r] > rec_lengths[r] (the read's own range is then undefined,
+ * nothing else is touched); 2 when rec_status is given and rec_status[r] != 0 -- that record did not inflate, its
+ * rec_lengths[r] may be garbage, nothing of it is read and nothing is written. */
+uint32_t sgk_sigraw_unit_samples(void); /* host arithmetic, no GPU */
+int sgk_sigraw_gather(const uint8_t *records, const uint64_t *rec_offsets, const uint32_t *rec_lengths,
+                      const uint32_t *sig_offsets, const uint32_t *rec_status /* may be NULL */, uint32_t n_reads,
+                      int16_t *samples, const uint64_t *offsets, const uint32_t *lengths, uint32_t max_read_len,
+                      uint64_t n_samples, uint32_t *status, void *stream);
 
 /* ---- qts: quantise the raw signal (src/qts.c:27-43, :126-142) and re-encode it ------ */
 #define SGK_QTS_FLOOR 0     /* (raw >> b) << b                                       */
@@ -875,6 +896,19 @@ int sgk_job_begin_zrec_format(sgk_job_t *job, uint32_t n_reads, int record_forma
 int sgk_job_begin_zrec_aux(sgk_job_t *job, uint32_t n_reads, int record_format, const uint32_t *lengths,
                            const uint32_t *rec_bytes, const uint32_t *sig_offset, const uint32_t *sig_bytes,
                            const uint32_t *rec_room, const sgk_aux_field_t *fields, uint32_t n_fields, sgk_job_input_t *in);
+/* sgk_job_begin_zrec_aux with the signal's own format named (additive to 0.2.3).  SGK_SIGNAL_SVBZD is exactly
+ * sgk_job_begin_zrec_aux.  SGK_SIGNAL_INT16: the records' signal is not compressed (signal_press 0: what slow5tools
+ * wrote before svb-zd, every `-s none` file) -- lengths[r] little-endian int16 samples at sig_offset[r] of the inflated
+ * record; SGK_ERR_ARG unless sig_bytes[r] == 2 * lengths[r] for every r.  The job inflates the records and moves the
+ * samples with sgk_sigraw_gather; what every record inflated to is always checked with sgk_zrec_tail_check (n_fields 0:
+ * the record must end exactly at its signal), so a record that inflates cleanly but is shorter than its signal is
+ * reported.  decode_status[r]: 0x100 | / 0x200 | the inflate status first, then 0x400 | the tail status, else
+ * sgk_sigraw_gather's.  Any other signal_format: SGK_ERR_ARG.  Every sgk_job_submit tool and sgk_job_submit_qts work on
+ * such a batch as on any staged one; SGK_QTS_ZREC_FRAMES stays SGK_ERR_ARG for it. */
+int sgk_job_begin_zrec_signal(sgk_job_t *job, uint32_t n_reads, int record_format, int signal_format,
+                              const uint32_t *lengths, const uint32_t *rec_bytes, const uint32_t *sig_offset,
+                              const uint32_t *sig_bytes, const uint32_t *rec_room, const sgk_aux_field_t *fields,
+                              uint32_t n_fields, sgk_job_input_t *in);
 /* may be called again after sgk_job_wait to run another tool over the same staged batch */
 int sgk_job_submit(sgk_job_t *job, int tool, int rna, int pore, int flags);
 /* qts over the staged batch (any input format; text input with bare SGK_SIGNAL_INT16 samples out, without
@@ -896,7 +930,7 @@ int sgk_job_set_record_frames(sgk_job_t *job, const uint8_t *bytes, const uint32
                               const uint32_t *head_lengths /* n */);
 /* Record mode without staged frames (additive to 0.2.3): or'ed into out_signal_format together with SGK_QTS_RECORDS, for a
  * batch begun with sgk_job_begin_zrec / _format / _aux and SGK_SIGNAL_SVBZD out (anything else: SGK_ERR_ARG, as is a
- * sig_offset below 8).  Record r's frame is read where the record was inflated on the device: its head is bytes
+ * sig_offset below 8, and a batch begun with sgk_job_begin_zrec_signal and SGK_SIGNAL_INT16). Record r's frame is read where the record was inflated on the device: its head is bytes
  * [0, sig_offset[r] - 8), its tail bytes [sig_offset[r] + sig_bytes[r], what the record inflated to); no
  * sgk_job_set_record_frames is needed and the records never leave the device between the file's bytes and the new zlib
  * streams.  A record that did not inflate, or whose auxiliary fields do not fill it, is not read from: its

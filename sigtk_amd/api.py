@@ -19,6 +19,7 @@ LIB_PATH = os.path.join(PKG, "libsigtk_gpu.so")
 LIB_PATH = os.environ.get("SIGTK_AMD_LIB", LIB_PATH)
 
 SGK_OK = 0
+SGK_ERR_ARG = -1
 SGK_ERR_NODEVICE = -3
 SGK_ERR_WORKSPACE = -4
 SGK_ERR_CAPACITY = -5
@@ -272,7 +273,7 @@ PREFIX_DTYPE = np.dtype([("adapt_x", "<i4"), ("adapt_y", "<i4"), ("polya_x", "<i
 #: every symbol include/sigtk_gpu.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "sgk_strerror", "sgk_version", "sgk_last_hip_error", "sgk_device_count", "sgk_set_device",
-    "sgk_pa", "sgk_event_workspace_bytes", "sgk_event", "sgk_event_pa", "sgk_event_status", "sgk_event_plan", "sgk_event_plan_opt", "sgk_job_long_declined", "sgk_inflate", "sgk_deflate", "sgk_deflate_bound", "sgk_deflate_block_bytes", "sgk_job_set_record_frames", "sgk_job_begin_zrec", "sgk_zstd_decompress", "sgk_job_begin_zrec_format", "sgk_zrec_tail_check", "sgk_job_begin_zrec_aux", "sgk_pipeline", "sgk_stat_lane_rules",
+    "sgk_pa", "sgk_event_workspace_bytes", "sgk_event", "sgk_event_pa", "sgk_event_status", "sgk_event_plan", "sgk_event_plan_opt", "sgk_job_long_declined", "sgk_inflate", "sgk_deflate", "sgk_deflate_bound", "sgk_deflate_block_bytes", "sgk_job_set_record_frames", "sgk_job_begin_zrec", "sgk_zstd_decompress", "sgk_job_begin_zrec_format", "sgk_zrec_tail_check", "sgk_job_begin_zrec_aux", "sgk_sigraw_unit_samples", "sgk_sigraw_gather", "sgk_job_begin_zrec_signal", "sgk_pipeline", "sgk_stat_lane_rules",
     "sgk_event_workspace_bytes_opt", "sgk_event_opt", "sgk_event_pa_opt", "sgk_event_host_opt",
     "sgk_stat_workspace_bytes", "sgk_stat", "sgk_stat_pa", "sgk_jnn_workspace_bytes", "sgk_jnn",
     "sgk_prefix_workspace_bytes", "sgk_prefix", "sgk_stat_opt", "sgk_stat_long_status", "sgk_stat_plan", "sgk_stat_pa_opt", "sgk_jnn_opt", "sgk_prefix_opt",
@@ -450,6 +451,11 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.sgk_job_begin_zrec_format.argtypes = [C.c_void_p, C.c_uint32, C.c_int] + [C.c_void_p] * 5 + [C.POINTER(JobInput)]
     L.sgk_job_begin_zrec_aux.argtypes = [C.c_void_p, C.c_uint32, C.c_int] + [C.c_void_p] * 5 + \
         [C.POINTER(AuxField), C.c_uint32, C.POINTER(JobInput)]
+    L.sgk_job_begin_zrec_signal.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_int] + [C.c_void_p] * 5 + \
+        [C.POINTER(AuxField), C.c_uint32, C.POINTER(JobInput)]
+    L.sgk_sigraw_unit_samples.restype = C.c_uint32
+    L.sgk_sigraw_unit_samples.argtypes = []
+    L.sgk_sigraw_gather.argtypes = [C.c_void_p] * 5 + [C.c_uint32] + [C.c_void_p] * 3 + [C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
     L.sgk_zrec_tail_check.argtypes = [C.c_void_p] * 4 + [C.c_uint32, C.POINTER(AuxField), C.c_uint32, C.c_void_p, C.c_void_p]
     L.sgk_job_text.argtypes = [C.c_void_p, C.POINTER(JobText)]
     L.sgk_text_workspace_bytes.restype = C.c_size_t
@@ -799,18 +805,26 @@ class Job:
             self.set_ids(ids)
 
     def stage_zrec(self, records, lengths, sig_offset, sig_bytes, rec_room, dig, off, rng, ids=None, record_format=RECORD_ZLIB,
-                   aux=None):
+                   aux=None, signal_format=SIGNAL_SVBZD):
         """sgk_job_begin_zrec_format: `records` are compressed BLOW5 records (bytes; record_format RECORD_ZLIB: zlib
         streams, RECORD_ZSTD: zstd frames) with an svb-zd signal blob at sig_offset[r] (sig_bytes[r] long) of the
         decompressed record, which is rec_room[r] bytes at most.  With aux (the file's auxiliary columns: AuxField
         objects or (elem_bytes, is_array) pairs, [] for none) sgk_job_begin_zrec_aux: rec_room is an upper bound and
-        the fields behind the signal must fill what the record inflated to exactly (decode_status 0x400 | status)"""
+        the fields behind the signal must fill what the record inflated to exactly (decode_status 0x400 | status).
+        signal_format SIGNAL_INT16 (sgk_job_begin_zrec_signal): the signal is plain int16 samples, sig_bytes[r] must be
+        2 * lengths[r], and the fields are always checked (aux None counts as [])"""
         n = len(records)
         u32 = lambda x: np.ascontiguousarray(x, dtype=np.uint32)
         lengths, sig_offset, sig_bytes, rec_room = u32(lengths), u32(sig_offset), u32(sig_bytes), u32(rec_room)
         rbytes = u32([len(b) for b in records])
         jin = JobInput()
-        if aux is not None:
+        if signal_format != SIGNAL_SVBZD:
+            aux = [] if aux is None else aux
+            check(self.L.sgk_job_begin_zrec_signal(self.h, n, int(record_format), int(signal_format), lengths.ctypes.data,
+                                                   rbytes.ctypes.data, sig_offset.ctypes.data, sig_bytes.ctypes.data,
+                                                   rec_room.ctypes.data, aux_table(aux), len(aux), C.byref(jin)),
+                  "sgk_job_begin_zrec_signal")
+        elif aux is not None:
             check(self.L.sgk_job_begin_zrec_aux(self.h, n, int(record_format), lengths.ctypes.data, rbytes.ctypes.data,
                                                 sig_offset.ctypes.data, sig_bytes.ctypes.data, rec_room.ctypes.data,
                                                 aux_table(aux), len(aux), C.byref(jin)), "sgk_job_begin_zrec_aux")

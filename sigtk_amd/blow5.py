@@ -109,7 +109,9 @@ def svb_zd_encode(raw: np.ndarray) -> bytes:
 # --------------------------------------------------------------------------- reader
 
 
-def read_blow5(path: str) -> Blow5:
+def read_blow5(path: str, zstd_decompress=None) -> Blow5:
+    """zstd_decompress: a callable frame bytes -> record bytes, for files with zstd records (this module has no zstd
+    decoder of its own; without one such a file is refused)"""
     with open(path, "rb") as fh:
         buf = fh.read()
     if buf[:6] != MAGIC:
@@ -125,7 +127,7 @@ def read_blow5(path: str) -> Blow5:
         if line.startswith("@"):
             parts = line[1:].split("\t")
             out.attrs[parts[0]] = parts[1:]
-    if record_press not in (0, 1):
+    if record_press not in (0, 1) and not (record_press == 2 and zstd_decompress is not None):
         raise ValueError("record compression %d not supported (zstd?)" % record_press)
     pos = 68 + hsize
     end = len(buf)
@@ -140,6 +142,8 @@ def read_blow5(path: str) -> Blow5:
         pos += size
         if record_press == 1:
             rec = zlib.decompress(rec)
+        elif record_press == 2:
+            rec = zstd_decompress(bytes(rec))
         (idl,) = struct.unpack_from("<H", rec, 0)
         rid = rec[2 : 2 + idl].decode("ascii")
         p = 2 + idl

@@ -124,6 +124,11 @@ struct sgk_job {
     uint32_t n_aux = 0, aux_cap = 0;
     GrowPin h_toffs, h_tstat;
     GrowDev d_toffs, d_tstat;
+    // sgk_job_begin_zrec_signal with SGK_SIGNAL_INT16: the signal of the inflated records is plain samples, moved into
+    // d_samples by k_sigraw_gather from sig_offset[r] of every record (h_sigo)
+    bool raw_sig = false;
+    GrowPin h_sigo;
+    GrowDev d_sigo;
     ~sgk_job() { free(aux_fields); }
     bool long_fetched = false;        // stat / jnn / prefix: the long-read header of the call is on its way to h_long
     uint32_t long_declined = 0;       // ... long reads the long path declined (n_timeouts of sgk_long_status_t), after wait
@@ -271,6 +276,25 @@ int sgk_job_begin_zrec_aux(sgk_job_t *j, uint32_t n_reads, int record_format, co
     return SGK_OK;
 }
 
+int sgk_job_begin_zrec_signal(sgk_job_t *j, uint32_t n_reads, int record_format, int signal_format, const uint32_t *lengths,
+                              const uint32_t *rec_bytes, const uint32_t *sig_offset, const uint32_t *sig_bytes,
+                              const uint32_t *rec_room, const sgk_aux_field_t *fields, uint32_t n_fields, sgk_job_input_t *in) {
+    if (signal_format == SGK_SIGNAL_SVBZD)
+        return sgk_job_begin_zrec_aux(j, n_reads, record_format, lengths, rec_bytes, sig_offset, sig_bytes, rec_room, fields,
+                                      n_fields, in);
+    if (signal_format != SGK_SIGNAL_INT16) return SGK_ERR_ARG;
+    if (n_reads && (!lengths || !sig_offset || !sig_bytes)) return SGK_ERR_ARG;
+    for (size_t r = 0; r < n_reads; ++r)
+        if ((uint64_t)sig_bytes[r] != 2ull * lengths[r]) return SGK_ERR_ARG;
+    int rc = sgk_job_begin_zrec_aux(j, n_reads, record_format, lengths, rec_bytes, sig_offset, sig_bytes, rec_room, fields,
+                                    n_fields, in);
+    if (rc != SGK_OK) return rc;
+    if ((rc = j->h_sigo.ensure((n_reads ? (size_t)n_reads : 1) * 4)) != SGK_OK) return rc;
+    if (n_reads) memcpy(j->h_sigo.p, sig_offset, (size_t)n_reads * 4);
+    j->raw_sig = true;
+    return SGK_OK;
+}
+
 static int job_begin(sgk_job_t *j, uint32_t n_reads, const uint32_t *lengths, int signal_format, const uint32_t *blob_bytes,
                      const uint32_t *sig_offset, const uint32_t *sig_bytes, const uint32_t *rec_room, sgk_job_input_t *in) {
     if (!j || !in || (n_reads && !lengths)) return SGK_ERR_ARG;
@@ -302,6 +326,7 @@ static int job_begin(sgk_job_t *j, uint32_t n_reads, const uint32_t *lengths, in
     j->n_samples = o + 64;
     j->fmt = signal_format;
     j->aux = false;
+    j->raw_sig = false;
     j->blob_bytes = 0;
     memset(in, 0, sizeof *in);
     if (signal_format == SGK_SIGNAL_SVBZD || signal_format == SGK_SIGNAL_ZREC || signal_format == SGK_SIGNAL_TEXT) {
@@ -436,9 +461,19 @@ static int job_upload(sgk_job_t *j, sgk_batch_t *view) {
         if (rc != SGK_OK) return rc;
         // (a record that did not inflate leaves whatever it leaves: its blob then fails the decoder's own checks or
         // decodes to garbage nobody reads -- sgk_job_wait refuses the batch on the inflate status)
-        rc = sgk_svbzd_decode(j->d_inflated.as<uint8_t>(), j->d_soffs.as<uint64_t>(), j->d_slens.as<uint32_t>(), j->n_reads,
-                              j->d_samples.as<int16_t>(), j->d_offsets.as<uint64_t>(), j->d_lengths.as<uint32_t>(),
-                              j->d_dstat.as<uint32_t>(), st);
+        if (j->raw_sig) {
+            // plain samples: moved out of what each record inflated to (a record shorter than its signal: status 1 here
+            // and from k_zrec_tail below; one that did not inflate is not read)
+            if ((rc = h2d(j->d_sigo, j->h_sigo, nr * 4, st)) != SGK_OK) return rc;
+            rc = sgk_sigraw_gather(j->d_inflated.as<uint8_t>(), j->d_ioffs.as<uint64_t>(), j->d_ilens.as<uint32_t>(),
+                                   j->d_sigo.as<uint32_t>(), j->d_istat.as<uint32_t>(), j->n_reads, j->d_samples.as<int16_t>(),
+                                   j->d_offsets.as<uint64_t>(), j->d_lengths.as<uint32_t>(), j->max_len, j->n_samples,
+                                   j->d_dstat.as<uint32_t>(), st);
+        } else {
+            rc = sgk_svbzd_decode(j->d_inflated.as<uint8_t>(), j->d_soffs.as<uint64_t>(), j->d_slens.as<uint32_t>(),
+                                  j->n_reads, j->d_samples.as<int16_t>(), j->d_offsets.as<uint64_t>(),
+                                  j->d_lengths.as<uint32_t>(), j->d_dstat.as<uint32_t>(), st);
+        }
         if (rc != SGK_OK) return rc;
         if ((rc = d2h(j->h_dstat, j->d_dstat, nr * 4, st)) != SGK_OK) return rc;
         if ((rc = d2h(j->h_istat, j->d_istat, nr * 4, st)) != SGK_OK) return rc;
@@ -894,12 +929,13 @@ static int job_qts_records(sgk_job_t *j, const sgk_batch_t &view, bool svb, bool
 int sgk_job_submit_qts(sgk_job_t *j, int bits, int method, int out_fmt_flags) {
     if (!j || !j->begun || j->submitted) return SGK_ERR_ARG;
     const bool records = (out_fmt_flags & SGK_QTS_RECORDS) != 0;
-    // SGK_QTS_ZREC_FRAMES: the frames are the records where they were inflated -- records of a ZREC batch (svb-zd by
-    // definition) only; j->flags keeps the other bits, as every reader of it expects
+    // SGK_QTS_ZREC_FRAMES: the frames are the records where they were inflated -- records of a ZREC batch with an svb-zd
+    // signal only (one begun with SGK_SIGNAL_INT16 by sgk_job_begin_zrec_signal is refused: its len_raw_signal is a
+    // sample count); j->flags keeps the other bits, as every reader of it expects
     const bool zrec_frames = (out_fmt_flags & SGK_QTS_ZREC_FRAMES) != 0;
     out_fmt_flags &= ~SGK_QTS_ZREC_FRAMES;
     const int out_fmt = out_fmt_flags & ~SGK_QTS_RECORDS;
-    if (zrec_frames && (!records || j->fmt != SGK_SIGNAL_ZREC || out_fmt != SGK_SIGNAL_SVBZD)) return SGK_ERR_ARG;
+    if (zrec_frames && (!records || j->fmt != SGK_SIGNAL_ZREC || j->raw_sig || out_fmt != SGK_SIGNAL_SVBZD)) return SGK_ERR_ARG;
     if (out_fmt != SGK_SIGNAL_INT16 && out_fmt != SGK_SIGNAL_SVBZD && out_fmt != SGK_SIGNAL_TEXT) return SGK_ERR_ARG;
     // text in, bare int16 samples out stays refused (tests/test_gpu_slow5_cli.py pins it): that is the decoder alone,
     // and no record of either container holds uncompressed samples next to text ones

@@ -614,6 +614,35 @@ def zrec_tail_check(inflated: torch.Tensor, rec_offsets: torch.Tensor, rec_lengt
     return status
 
 
+def sigraw_unit_samples() -> int:
+    """sgk_sigraw_unit_samples: the samples one work unit of sigraw_gather moves (host arithmetic)"""
+    return int(api.load_library().sgk_sigraw_unit_samples())
+
+
+def sigraw_gather(records: torch.Tensor, rec_offsets: torch.Tensor, rec_lengths: torch.Tensor, sig_offsets: torch.Tensor,
+                  samples: torch.Tensor, offsets: torch.Tensor, lengths: torch.Tensor, max_read_len: int,
+                  rec_status: Optional[torch.Tensor] = None, n_samples: Optional[int] = None,
+                  status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sgk_sigraw_gather over torch buffers on one device: records uint8 (16-byte aligned, readable to the next multiple
+    of 16 behind every record); rec_offsets / offsets int64 (uint64 bits); rec_lengths / sig_offsets / lengths / rec_status
+    int32 (uint32 bits), one entry per read; samples int16, written in place at offsets[r] (multiples of 8).  n_samples
+    defaults to the arena's size.  -> status, int32 per read (enqueued on the current stream, not synchronised)"""
+    L = api.load_library()
+    n = int(rec_offsets.numel())
+    assert records.dtype == torch.uint8 and samples.dtype == torch.int16
+    assert rec_offsets.dtype == torch.int64 and offsets.dtype == torch.int64
+    for t in (rec_lengths, sig_offsets, lengths) + ((rec_status,) if rec_status is not None else ()):
+        assert t.dtype == torch.int32 and int(t.numel()) == n
+    assert int(offsets.numel()) == n
+    if status is None:
+        status = torch.full((max(n, 1),), -1, dtype=torch.int32, device=records.device)
+    api.check(L.sgk_sigraw_gather(_ptr(records), _ptr(rec_offsets), _ptr(rec_lengths), _ptr(sig_offsets), _ptr(rec_status), n,
+                                  _ptr(samples), _ptr(offsets), _ptr(lengths), int(max_read_len),
+                                  int(samples.numel()) if n_samples is None else int(n_samples), _ptr(status), _stream_ptr()),
+              "sgk_sigraw_gather")
+    return status
+
+
 # ---------------------------------------------------------------------- TSV rows written on the device (sgk_text_*)
 
 class TextWriter:

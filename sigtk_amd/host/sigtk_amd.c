@@ -377,7 +377,7 @@ typedef struct {
     int mode, nthreads, host_decode;
     int gpu_text;        /* --gpu-text (pa / event, whole-file mode): the rows come from the GPU as text */
     uint64_t text_bytes; /* ... their bytes over PCIe */
-    int zrec;            /* records go to the GPU as they sit in the file (zlib / zstd records, svb-zd signal, auxiliary columns of known types) */
+    int zrec;            /* records go to the GPU as they sit in the file (zlib / zstd records, svb-zd or uncompressed signal, auxiliary columns of known types) */
     sgk_aux_field_t *aux_tab; /* ... those columns, in header order */
     uint32_t n_aux, n_aux_arrays; /* ... how many, and how many of them are arrays (u64 count + elements) */
     uint64_t aux_fixed;  /* ... the bytes of the others */
@@ -611,7 +611,8 @@ static void batch_launch(pipe_t *P, batch_t *b) {
     b->sigtext = P->f->text && !P->host_decode;
     b->zrec = P->zrec;
     int rc;
-    if (b->zrec) rc = sgk_job_begin_zrec_aux(b->job, b->n, P->f->record_press == 2 ? SGK_RECORD_ZSTD : SGK_RECORD_ZLIB, b->lengths, b->blob_bytes, b->sig_off, b->sig_len, b->room, P->aux_tab, P->n_aux, &b->in);
+    /* (signal_press 0: the inflated records hold plain samples, moved into the sample arena on the GPU) */
+    if (b->zrec) rc = sgk_job_begin_zrec_signal(b->job, b->n, P->f->record_press == 2 ? SGK_RECORD_ZSTD : SGK_RECORD_ZLIB, P->f->signal_press == 1 ? SGK_SIGNAL_SVBZD : SGK_SIGNAL_INT16, b->lengths, b->blob_bytes, b->sig_off, b->sig_len, b->room, P->aux_tab, P->n_aux, &b->in);
     else rc = sgk_job_begin(b->job, b->n, b->lengths, b->sigtext ? SGK_SIGNAL_TEXT : (b->svb ? SGK_SIGNAL_SVBZD : SGK_SIGNAL_INT16), b->blob_bytes, &b->in);
     if (rc != SGK_OK) gpu_fail("sgk_job_begin", rc);
     if ((P->gpu_deflate && !b->zrec) || P->q_text) batch_frames(b, P->q_text);
@@ -867,8 +868,8 @@ static void row_qts(sbuf_t *o, const batch_t *b, const sgk_job_output_t *out, ui
 
 /* A zrec batch of a zlib file with array columns came back with nothing but 0x108: records that inflate to more than
  * their room, i.e. an array longer than the slack (or a broken record, which then gets the host path's error).  The
- * batch's records are still where the reader put them: inflate and parse them on the host, stage their svb-zd blobs,
- * submit and wait again -- in the writer, so the file's order is kept. */
+ * batch's records are still where the reader put them: inflate and parse them on the host, stage their svb-zd blobs (or
+ * their samples, when the signal is not compressed), submit and wait again -- in the writer, so the file's order is kept. */
 static int batch_redo_host(pipe_t *P, batch_t *b, pool_t *pool) {
     lctx_t c = {P, b, 0};
     pfor(pool, b->n, load_parse, &c);
@@ -881,8 +882,8 @@ static int batch_redo_host(pipe_t *P, batch_t *b, pool_t *pool) {
         b->blob_bytes[i] = (uint32_t)b->recs[i].v.signal_bytes;
     }
     b->zrec = 0;
-    b->svb = 1;
-    int rc = sgk_job_begin(b->job, b->n, b->lengths, SGK_SIGNAL_SVBZD, b->blob_bytes, &b->in);
+    b->svb = P->f->signal_press == 1;
+    int rc = sgk_job_begin(b->job, b->n, b->lengths, b->svb ? SGK_SIGNAL_SVBZD : SGK_SIGNAL_INT16, b->blob_bytes, &b->in);
     if (rc != SGK_OK) gpu_fail("sgk_job_begin", rc);
     if (P->gpu_deflate) batch_frames(b, 0);   /* qts --gpu-inflate: the frames from the host's inflated records after all */
     pfor(pool, b->n, load_stage, &c);
@@ -1194,7 +1195,7 @@ static struct option long_options[] = {
 /* What a pipeline needs to send the records of P->f to the GPU as they sit in the file (cmain, qts --gpu-inflate): the
  * header's auxiliary columns as sgk_job_begin_zrec_aux takes them, how many are arrays, the bytes of the others, the slack
  * per array (load_parse makes every record's room from these).  Returns whether the file is one of those: BLOW5 with zlib
- * or zstd records around an svb-zd signal and a type line of known types only -- the caller adds its own conditions. */
+ * or zstd records and a type line of known types only -- the caller adds its own conditions, the signal's among them. */
 static int pipe_zrec_setup(pipe_t *P, uint64_t aux_slack) {
     const b5_file_t *f = P->f;
     b5_aux_field_t *tab = NULL;
@@ -1214,7 +1215,7 @@ static int pipe_zrec_setup(pipe_t *P, uint64_t aux_slack) {
     free(tab);
     P->n_aux = n_tab > 0 ? (uint32_t)n_tab : 0;
     P->aux_slack = aux_slack;
-    return !f->text && (f->record_press == 1 || f->record_press == 2) && f->signal_press == 1 && n_tab >= 0;
+    return !f->text && (f->record_press == 1 || f->record_press == 2) && n_tab >= 0;
 }
 
 static int cmain(int argc, char *argv[], const char *mode_s) {
@@ -1348,11 +1349,12 @@ static int cmain(int argc, char *argv[], const char *mode_s) {
     P.mode = mode;
     P.nthreads = nthreads;
     P.host_decode = host_decode;
-    /* Records go to the GPU as they sit in the file when they are zlib streams or zstd frames around an svb-zd signal and the
-     * header's type line names only types this reader knows, arrays included (the GPU then checks every record's auxiliary
-     * fields against that table, sgk_job_begin_zrec_aux); everything else -- and --host-inflate / --host-decode, and reads
-     * fetched by id from a file with array columns -- is inflated by the host threads as before. */
-    P.zrec = pipe_zrec_setup(&P, aux_slack) && !host_inflate && !host_decode && (argc - optind - 1 == 0 || P.n_aux_arrays == 0);
+    /* Records go to the GPU as they sit in the file when they are zlib streams or zstd frames around an svb-zd or an
+     * uncompressed signal (signal_press 1 or 0: sgk_job_begin_zrec_signal) and the header's type line names only types
+     * this reader knows, arrays included (the GPU then checks every record's auxiliary fields against that table);
+     * everything else -- and --host-inflate / --host-decode, and reads fetched by id from a file with array columns -- is
+     * inflated by the host threads as before. */
+    P.zrec = pipe_zrec_setup(&P, aux_slack) && (f->signal_press == 0 || f->signal_press == 1) && !host_inflate && !host_decode && (argc - optind - 1 == 0 || P.n_aux_arrays == 0);
     /* ... in batches of 128 M samples: the inflate kernel is a wavefront per record and takes ~35 ms however many records
      * it has (up to the ~4 800 the GPU holds at once), so a batch should bring a thousand of them (1e10 samples of `stat`:
      * 5.2 s with the 16 M-sample batches of the host path, 1.7 s with 128 M, profiles/r05_cli_steady.json) */
@@ -1531,7 +1533,7 @@ static int qtsmain(int argc, char *argv[]) {
      * --batch-samples says otherwise: the inflate kernel wants several hundred records in flight, and the 128 M of the
      * other subtools cost more in growing the record and stream buffers than they gain (profiles/qts_gpu_inflate.md:
      * 0.34 s at 64 M against 0.39 - 0.75 s at 128 M and 0.39 - 0.46 s at 16 M on 4e8 samples). */
-    if (gpu_inflate) P.zrec = pipe_zrec_setup(&P, aux_slack);
+    if (gpu_inflate) P.zrec = pipe_zrec_setup(&P, aux_slack) && f->signal_press == 1;   /* (an uncompressed signal: --gpu-deflate alone) */
     if (P.zrec && !batch_set) batch_samples = 64ull << 20;
     P.out_fp = out;
     P.limit_bytes = f->text ? batch_samples * 4 : batch_samples;   /* (on-disk bytes: four to five per sample in a text file) */

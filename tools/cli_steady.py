@@ -16,7 +16,8 @@ body it prints for the base file -- which is compared, byte for byte, with the r
 1e9 samples, ~10 GB of pa text; the base file's whole output is held in memory once).  `--extra --gpu-text` runs the rows
 through the device-side writer; the JSON records it ("cli_extra", "gpu_text") and the text bytes the CLI reports.
 `--aux` writes the base file with the six auxiliary columns of an ONT file (channel_number is a `char*`), as MinKNOW and
-`slow5tools f2s` do; the JSON then carries the CLI's own count of the records it decompressed on the GPU."""
+`slow5tools f2s` do; the JSON then carries the CLI's own count of the records it decompressed on the GPU.
+`--signal-press 0` writes it with the signal not compressed (plain int16 inside the zlib records: `slow5tools -s none`)."""
 import argparse
 import hashlib
 import json
@@ -86,8 +87,9 @@ def main():
     ap.add_argument("--runs", type=int, default=2)
     ap.add_argument("--extra", default="", help="extra CLI arguments, e.g. '--batch-samples 64000000'")
     ap.add_argument("--aux", action="store_true", help="write the base file with ONT's six auxiliary columns")
+    ap.add_argument("--signal-press", type=int, default=1, choices=(0, 1), help="1: svb-zd signal (default); 0: plain int16")
     a = ap.parse_args()
-    tag = "aux_" if a.aux else ""
+    tag = ("aux_" if a.aux else "") + ("" if a.signal_press == 1 else "sp0_")
     base = os.path.join(a.dir, "steady_%sbase_%d.blow5" % (tag, a.base_reads))
     big = os.path.join(a.dir, "steady_%sbig_%d_x%d.blow5" % (tag, a.base_reads, a.copies))
     t0 = time.perf_counter()
@@ -95,13 +97,13 @@ def main():
         reads, dig, off, rng = api.synth_reads_host(a.base_reads, a.read_len, 77, 0)
         recs = [blow5.Read("synth-%08d" % i, 0, float(dig[i]), float(off[i]), float(rng[i]), 4000.0, reads[i],
                            aux=ont_aux(i) if a.aux else None) for i in range(a.base_reads)]
-        blow5.write_blow5(base, recs, {"experiment_type": "genomic_dna", "sequencing_kit": "sqk-lsk109"},
+        blow5.write_blow5(base, recs, {"experiment_type": "genomic_dna", "sequencing_kit": "sqk-lsk109"}, 1, a.signal_press,
                           aux_types=ONT_AUX if a.aux else None)
     if not os.path.exists(big):
         replicate(base, big, a.copies)
     out = {"base_file_mb": round(os.path.getsize(base) / 1e6, 1), "big_file_mb": round(os.path.getsize(big) / 1e6, 1),
            "copies": a.copies, "reads": a.base_reads * a.copies, "samples": a.base_reads * a.copies * a.read_len,
-           "aux_columns": a.aux, "host_cpus": os.cpu_count(), "made_in_s": round(time.perf_counter() - t0, 1), "cli_extra": a.extra,
+           "aux_columns": a.aux, "signal_press": a.signal_press, "host_cpus": os.cpu_count(), "made_in_s": round(time.perf_counter() - t0, 1), "cli_extra": a.extra,
            "gpu_text": "--gpu-text" in a.extra.split(), "tools": {}}
     env = dict(os.environ, SGK_CLI_TIMING="1")
     targ = (["-t", str(a.threads)] if a.threads else []) + (["--gpus", str(a.gpus)] if a.gpus != 1 else []) + a.extra.split()
