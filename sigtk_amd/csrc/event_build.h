@@ -57,13 +57,35 @@ constexpr int BREC = 576;
 struct __attribute__((aligned(16))) BuildRec {
     double S, S2;
 };
-struct BuildLds {
+// NPT: lane prefixes kept.  The carrying builder (SGK_BUILD_CARRY below) keeps 128: the tile's 64 behind 64 zeros, the
+// entries that the leftover records of the previous tile look up (their prefix is folded in already).
+template <int NPT>
+struct BuildLdsT {
     BuildRec rec[BREC];
-    double pt[64];
-    double pt2[64];
-    uint16_t p[BREC];  // tile-relative sample index of the boundary
+    double pt[NPT];
+    double pt2[NPT];
+    uint16_t p[BREC];  // tile-relative sample index of the boundary (carrying builder: + 2048; a leftover's is below 2048)
 };
+typedef BuildLdsT<64> BuildLds;
+typedef BuildLdsT<128> BuildLdsCarry;
 static_assert(sizeof(BuildLds) <= 11776, "builder LDS budget: 13 waves per CU");
+// 12 workgroups of k_event<3, *> (3 waves per SIMD) share the CU's 160 KB: 13 653 bytes each, 13 312 in whole 512-byte
+// blocks.  (The kernels' LDS is the union with the detector's LzLds, 12 544 bytes: the zeros fit under it.)
+static_assert(sizeof(BuildLdsCarry) <= 13312, "carrying builder LDS budget: 12 workgroups per CU");
+
+// The builder's form per kernel (tools/build_variant.sh <tag> -DSGK_BUILD_CARRY=<bits>; 0: every tile runs
+// ceil(records / 64) rounds and starts again): 1 k_event<3, *>, 2 the other unflagged kernels (k_event<7, *>,
+// k_event_seg, k_event_multi).  In the carrying form a tile runs its full rounds only and leaves the records that remain
+// in LDS for the next tile's; profiles/event_rounds.md has what each form showed.
+#ifndef SGK_BUILD_CARRY
+#define SGK_BUILD_CARRY 1
+#endif
+
+// value of lane l-1, lane 0 receives lane 63's (wave rotate right by one lane, DPP wave_ror:1; every lane has a source)
+__device__ __forceinline__ int wave_ror1_i(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x13C, 0xf, 0xf, true); }
+__device__ __forceinline__ double wave_ror1_d(double v) {
+    return __hiloint2double(wave_ror1_i(__double2hiint(v)), wave_ror1_i(__double2loint(v)));
+}
 
 typedef short sgk_s2 __attribute__((ext_vector_type(2)));
 
@@ -87,9 +109,9 @@ struct TileRegs {
         }
     }
 };
-template <typename T, bool FULL>
+template <typename T, bool FULL, typename LDS>
 __device__ __forceinline__ void build_walk(const TileRegs<T> &buf, uint32_t bits, int nvalid, const Scale &sc, int l,
-                                           int excl, BuildLds *L, double &S, double &S2, uint32_t &mnb,
+                                           int excl, LDS *L, double &S, double &S2, uint32_t &mnb,
                                            uint32_t &mxb) {
     // (LDS addresses as 32-bit offsets: what ds_write takes)
     typedef __attribute__((address_space(3))) char *LdsBytes;
@@ -133,8 +155,18 @@ __device__ __forceinline__ void build_walk(const TileRegs<T> &buf, uint32_t bits
 // boundaries in front give (cnt_before); extremes and flags go to st, the read's verdict is chain_segment's.  In front
 // of the segment the bitmap words are another wave's: the only boundaries the walk knows there are the one it starts
 // at (prev_p) and the ones this segment owns (pre: peaks that were pending at the seam).
-template <typename T, bool SEG = false>
-__device__ __forceinline__ void build_read(const EvArgs &a, const ReadCtx<T> &rc, uint32_t r, BuildLds *L, bool declined,
+//
+// CARRY (SGK_BUILD_CARRY): a round emits one event per lane, so the records of a tile that do not fill a round -- 19 of 64
+// lanes on average on DNA reads -- wait in LDS for the next tile's instead of taking a round of their own.  They are
+// moved to the front of the record arrays with their lane prefix folded in and rebased to the next tile's start (exact
+// under the guard, like the carry), and their position falls below 2048, where the look-up of the lane prefix finds
+// zeros.  The next tile's walk writes behind them.  Only a read's (a segment's) last tile runs a partial round -- and a
+// tile that ends with fewer than 64 records, some of them leftovers already: a leftover is never older than one tile,
+// which is what its 16-bit position and the 64 zeros can express.  With full rounds lane 0's previous boundary is lane
+// 63's of the round before: a wave rotate by one lane, no v_readlane.
+template <typename T, bool SEG = false, bool CARRY = false>
+__device__ __forceinline__ void build_read(const EvArgs &a, const ReadCtx<T> &rc, uint32_t r,
+                           BuildLdsT<CARRY ? 128 : 64> *L, bool declined,
                            int64_t seg_a = 0, int64_t seg_b = 0, SegState *st = nullptr, uint32_t cnt_before = 0,
                            int prev_p = -1, const int *pre = nullptr, int n_pre = 0) {
     const int64_t n = rc.n;
@@ -172,6 +204,12 @@ __device__ __forceinline__ void build_read(const EvArgs &a, const ReadCtx<T> &rc
         }
     }
     double Gprev = 0.0, G2prev = 0.0;  // prefix sums at the previous boundary, relative to the current tile start
+    // CARRY: prevp / Gprev / G2prev are lane 0's (the only lane that takes them); m records wait in front of L->rec
+    int m = 0;
+    if constexpr (CARRY) {
+        L->pt[l] = 0.0;
+        L->pt2[l] = 0.0;
+    }
     // exactness guard inputs: int16 reads track the extremes of the RAW samples (packed 16-bit min / max, two samples
     // per instruction); pA reads the extremes of the float bit patterns
     uint32_t mnb = 0xffffffffu, mxb = 0u;
@@ -267,13 +305,16 @@ __device__ __forceinline__ void build_read(const EvArgs &a, const ReadCtx<T> &rc
         // walk: lane-relative prefix sums, boundary records.  A tile with more than BREC boundaries is not recorded:
         // its read is redone by the fallback.
         double S = 0.0, S2 = 0.0;
-        if (total > BREC) dense = true;
-        const uint32_t wbits = total > BREC ? 0u : bits;
-        if (full) build_walk<T, true>(buf, wbits, nvalid, rc.sc, l, excl, L, S, S2, mnb, mxb);
-        else build_walk<T, false>(buf, wbits, nvalid, rc.sc, l, excl, L, S, S2, mnb, mxb);
+        // (CARRY: the leftovers count: total + m; the records go behind them, positions and lane prefixes 64 lanes up)
+        const bool toomany = CARRY ? total + m > BREC : total > BREC;
+        if (toomany) dense = true;
+        const uint32_t wbits = toomany ? 0u : bits;
+        const int wl = CARRY ? l + 64 : l, wexcl = CARRY ? excl + m : excl;
+        if (full) build_walk<T, true>(buf, wbits, nvalid, rc.sc, wl, wexcl, L, S, S2, mnb, mxb);
+        else build_walk<T, false>(buf, wbits, nvalid, rc.sc, wl, wexcl, L, S, S2, mnb, mxb);
         const double inS = wave_incl_scan_d(S), inS2 = wave_incl_scan_d(S2);
-        L->pt[l] = inS - S;
-        L->pt2[l] = inS2 - S2;
+        L->pt[wl] = inS - S;
+        L->pt2[wl] = inS2 - S2;
         const double tileS = wave_last_d(inS), tileS2 = wave_last_d(inS2);
         __syncthreads();
         // The next tile's samples and bitmap word were requested before the walk and have long arrived: say so HERE,
@@ -282,9 +323,9 @@ __device__ __forceinline__ void build_read(const EvArgs &a, const ReadCtx<T> &rc
         // acknowledged by memory.  (vmcnt(0), expcnt / lgkmcnt untouched)
         __builtin_amdgcn_s_waitcnt(0x0F70);
 #ifdef SGK_DEV
-        const int tot = (total > BREC || (a.dev & SGK_DEV_NO_ROUNDS)) ? 0 : total;
+        const int tot = (toomany || (a.dev & SGK_DEV_NO_ROUNDS)) ? 0 : total + m;
 #else
-        const int tot = total > BREC ? 0 : total;
+        const int tot = toomany ? 0 : total + m;
 #endif
         // one event per lane per round.  Prefix sums are kept relative to the tile start (exact under the guard, so
         // no absolute base is needed); the previous boundary of lane l is lane l-1's record, lane 0 takes the
@@ -308,6 +349,61 @@ __device__ __forceinline__ void build_read(const EvArgs &a, const ReadCtx<T> &rc
             rec_at(64, pr1, S1, S21);
             pt0 = L->pt[pr0 / BT];
             pt20 = L->pt2[pr0 / BT];
+        }
+        if constexpr (CARRY) {
+            // positions carry + 2048 (a leftover's, relative to the tile before, is below it)
+            const uint32_t tbm = (uint32_t)tb - (uint32_t)(64 * BT);
+            const bool partial = tb + 64 * BT >= bit_hi || (m > 0 && tot < 64);
+            const int nfull = tot & ~63, mleft = tot - nfull;
+            // A round leaves position and sums of the next one's records behind ({p, G, G2}: formed where the look-ups
+            // it issued at its start have arrived), so the look-ups themselves are not handed from round to round.
+            uint32_t p = tbm + pr0;
+            double G = pt0 + S0, G2 = pt20 + S20;
+            for (int k0 = 0; k0 < nfull; k0 += 64) {
+                pt1 = L->pt[pr1 / BT];            // round k0 + 64
+                pt21 = L->pt2[pr1 / BT];
+                rec_at(k0 + 128, pr2, Sn, S2n);   // round k0 + 128
+                const uint32_t k = (uint32_t)(k0 + l);
+                const uint32_t pp = (uint32_t)wave_shr1_i((int)p, (int)prevp);
+                const double Gp = wave_shr1_d(G, Gprev), G2p = wave_shr1_d(G2, G2prev);
+                if (!SEG || rank + k != skip_rank) store_event_fast(eo, rank + k, pp, p, G - Gp, G2 - G2p, overflow);
+                prevp = (uint32_t)wave_ror1_i((int)p);
+                Gprev = wave_ror1_d(G);
+                G2prev = wave_ror1_d(G2);
+                p = tbm + pr1;
+                G = pt1 + S1;
+                G2 = pt21 + S21;
+                pr1 = pr2; S1 = Sn; S21 = S2n;
+            }
+            // what is left (fewer than 64 records) is what the last round left behind
+            if (partial) {
+                if (mleft > 0) {
+                    const uint32_t k = (uint32_t)(nfull + l);
+                    const uint32_t pp = (uint32_t)wave_shr1_i((int)p, (int)prevp);
+                    const double Gp = wave_shr1_d(G, Gprev), G2p = wave_shr1_d(G2, G2prev);
+                    if (l < mleft && (!SEG || rank + k != skip_rank))
+                        store_event_fast(eo, rank + k, pp, p, G - Gp, G2 - G2p, overflow);
+                    prevp = (uint32_t)__builtin_amdgcn_readlane((int)p, mleft - 1);
+                    Gprev = readlane_d(G, mleft - 1);
+                    G2prev = readlane_d(G2, mleft - 1);
+                }
+                rank += (uint32_t)tot;
+                m = 0;
+            } else {
+                if (l < mleft) {
+                    BuildRec left;
+                    left.S = G - tileS;
+                    left.S2 = G2 - tileS2;
+                    L->rec[l] = left;
+                    L->p[l] = (uint16_t)(p - (uint32_t)tb);
+                }
+                rank += (uint32_t)nfull;
+                m = mleft;
+            }
+            Gprev = Gprev - tileS;
+            G2prev = G2prev - tileS2;
+            __syncthreads();
+            continue;
         }
         for (int k0 = 0; k0 < tot; k0 += 64) {
             pt1 = L->pt[pr1 / BT];            // round k0 + 64
@@ -391,6 +487,12 @@ __device__ __forceinline__ void build_read(const EvArgs &a, const ReadCtx<T> &rc
 union EventLds {
     LzLds lz;
     BuildLds b;
+    BuildLdsCarry bc;
 };
+template <bool CARRY>
+__device__ __forceinline__ BuildLdsT<CARRY ? 128 : 64> *build_lds(EventLds *L) {
+    if constexpr (CARRY) return &L->bc;
+    else return &L->b;
+}
 
 }  // namespace sgk

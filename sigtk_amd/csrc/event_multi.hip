@@ -29,13 +29,14 @@ __global__ __launch_bounds__(64, (W1 == 3 ? DET_WAVES_DNA : DET_WAVES_RNA)) void
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __syncthreads();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    constexpr bool MULTI_CARRY = ((SGK_BUILD_CARRY) & 2) != 0;  // (off in the shipped build, event_build.h)
     for (int g = 0; g < G; ++g) {
         if (w0 + (uint32_t)g >= nshort) break;
         const uint32_t rg = (uint32_t)__builtin_amdgcn_readlane((int)r, g * lanes);
         const int code = __builtin_amdgcn_readlane(rcode, g * lanes);
         if (!__builtin_amdgcn_readlane((int)mine, g * lanes)) continue;
         const ReadCtx<T> rcg = make_ctx<T>(a, rg);
-        build_read<T>(a, rcg, rg, &L.b, code != 0);
+        build_read<T, false, MULTI_CARRY>(a, rcg, rg, build_lds<MULTI_CARRY>(&L), code != 0);
         __syncthreads();
     }
 }

@@ -201,7 +201,8 @@ __device__ __forceinline__ void chain_segment(const EvArgs &a, uint32_t bx, Even
     if (a.dev & SGK_DEV_TRACE) tt2 = wall_clock64();
 #endif
     if (!declined) {
-        build_read<T, true>(a, rc, r, &L->b, false, sa, sb, st, prev_cum, prev_last, st->pre, n_pre);
+        constexpr bool SEG_CARRY = ((SGK_BUILD_CARRY) & 2) != 0;  // (off in the shipped build, event_build.h)
+        build_read<T, true, SEG_CARRY>(a, rc, r, build_lds<SEG_CARRY>(L), false, sa, sb, st, prev_cum, prev_last, st->pre, n_pre);
         __syncthreads();
 #ifdef SGK_DEV
         if ((a.dev & SGK_DEV_TRACE) && l == 0) {   // (segments: start, detector end, seam + publish end | builder end in the top bits)

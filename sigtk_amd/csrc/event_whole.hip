@@ -8,6 +8,10 @@ namespace sgk {
 template <int W1>
 constexpr bool EV_LEAD = ((SGK_EVENT_LEAD) & (W1 == 3 ? 1 : 2)) != 0;
 
+// (and the carrying form of the builder: SGK_BUILD_CARRY, event_build.h)
+template <int W1>
+constexpr bool EV_CARRY = ((SGK_BUILD_CARRY) & (W1 == 3 ? 1 : 2)) != 0;
+
 template <int W1, typename T>
 __global__ __launch_bounds__(64, (W1 == 3 ? DET_WAVES_DNA : DET_WAVES_RNA)) void k_event(EvArgs a) {
     __shared__ EventLds L;
@@ -37,7 +41,7 @@ __global__ __launch_bounds__(64, (W1 == 3 ? DET_WAVES_DNA : DET_WAVES_RNA)) void
     __syncthreads();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 #ifdef SGK_DEV
-    if (!(a.dev & SGK_DEV_NO_BUILD)) build_read<T>(a, rc, r, &L.b, rcode != 0);
+    if (!(a.dev & SGK_DEV_NO_BUILD)) build_read<T, false, EV_CARRY<W1>>(a, rc, r, build_lds<EV_CARRY<W1>>(&L), rcode != 0);
     if ((a.dev & SGK_DEV_TRACE) && lane_id() == 0) {
         unsigned hw, xcc;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
@@ -49,7 +53,7 @@ __global__ __launch_bounds__(64, (W1 == 3 ? DET_WAVES_DNA : DET_WAVES_RNA)) void
         tr[3] = ((unsigned long long)xcc << 32) | hw;
     }
 #else
-    build_read<T>(a, rc, r, &L.b, rcode != 0);
+    build_read<T, false, EV_CARRY<W1>>(a, rc, r, build_lds<EV_CARRY<W1>>(&L), rcode != 0);
 #endif
 }
 
