@@ -230,6 +230,54 @@ int sgk_event_plan(uint32_t n_reads, uint64_t n_samples, uint32_t max_read_len, 
  * Returns SGK_ERR_CAPACITY if any read overflowed its slots. */
 int sgk_event_status(const void *workspace, sgk_event_status_t *out, void *stream);
 
+/* ---- event with caller-supplied detector parameters (additive to 0.2.3) --------------------------------------------
+ * The five numbers of detector_param (src/events.c:35-41) that sgk_event fixes to one of two presets by `rna`.  For a
+ * read of n samples the events are, bit for bit, those of the reference's own steps with these numbers: pA, the
+ * sequential double prefix sums (events.c:293-303), compute_tstat with window_length1 and with window_length2
+ * (:315-364), short_long_peak_detector (:371-443), create_event between consecutive peaks (:457-504).  Where the
+ * reference is undefined sgk_event's definitions hold: no peak gives one event [0,n), an empty read none, a window with
+ * n < 2w an all-zero statistic.  pA input with NaN or infinite samples (sgk_event_pa_param): the bits of NaN fields are
+ * undefined.
+ *   Domain: 2 <= window_length1, window_length2 <= SGK_EVENT_W_MAX, in any relation to each other -- except that a
+ *   window_length2 of 2 or 3 must equal window_length1 (see Capacity); threshold1, threshold2, peak_height finite and
+ *   >= 0 (FLT_MAX: "never"); flags holds known bits only.  Anything else is SGK_ERR_ARG and nothing is launched.
+ *   Capacity: over this domain peak positions are strictly increasing and at least 3 apart, so sgk_event_slots_for(n)
+ *   bounds the events of a read as it does for the presets (DESIGN.md 3.16 has the argument, tests/
+ *   test_event_params_cpu.py checks it).  The excluded corner is where that fails: with window_length2 < 4 the long
+ *   detector emits as soon as i - pos > 1, which can be the index at which a short peak opens -- two peaks 2 apart.
+ *   A slot range smaller than a read's events behaves as in sgk_event: the surplus is dropped, n_events[r] holds the
+ *   true count and sgk_event_status returns SGK_ERR_CAPACITY.
+ *   Routing: parameters that equal a preset bit for bit, without SGK_EVENT_PARAMS_GENERIC, take sgk_event_opt's kernels
+ *   through sgk_event_opt's launch (same results, same time, same status fields, workspace as sgk_event_workspace_bytes_opt).
+ *   Everything else takes the generic kernel k_event_param: one wavefront per read of any length, reads dispatched
+ *   longest first; of `opt` only `warmup` applies there (results do not depend on it); of the status it fills
+ *   n_rerun_passes, n_capacity_overflow and n_events_total, the rest are zero.
+ *   Workspace of the generic kernel: 64 + 4 n_reads + 512 bytes (rounded up to 64) + B x S, where
+ *   B = min(n_reads, 1024) persistent workgroups and S = 16 (max_read_len + 1) + 8 (max_read_len / 64 + 2) bytes rounded
+ *   up to 64 (two prefix arrays and a peak bitmap for the longest read); B is lowered (never below 1) to keep B x S under
+ *   2 GiB.  It does not grow with n_samples.  sgk_event_workspace_bytes_param is the single source of truth; a smaller
+ *   workspace gives SGK_ERR_WORKSPACE and nothing is written. */
+#define SGK_EVENT_W_MAX 64
+#define SGK_EVENT_PARAMS_GENERIC 1u /* flags: take the generic kernel even for a preset (tests, measurements) */
+typedef struct sgk_event_params {
+    uint32_t window_length1, window_length2;
+    float threshold1, threshold2, peak_height;
+    uint32_t flags, reserved[2];
+} sgk_event_params_t; /* 32 bytes */
+/* host only: the preset sgk_event uses for `rna` (0: 3 / 6 / 1.4 / 9.0 / 0.2, else 7 / 14 / 2.5 / 9.0 / 1.0), flags 0 */
+int sgk_event_params_preset(int rna, sgk_event_params_t *out);
+/* host only: SGK_OK when `p` lies in the domain above, else SGK_ERR_ARG */
+int sgk_event_params_check(const sgk_event_params_t *p);
+size_t sgk_event_workspace_bytes_param(uint32_t n_reads, uint64_t n_samples, uint32_t max_read_len,
+                                       const sgk_event_options_t *opt, const sgk_event_params_t *p);
+int sgk_event_param(const sgk_batch_t *batch, const sgk_event_params_t *p, const uint64_t *ev_slots,
+                    sgk_event_rec_t *events, uint32_t *n_events, void *workspace, size_t workspace_bytes, void *stream,
+                    const sgk_event_options_t *opt);
+int sgk_event_pa_param(const float *pa, const uint64_t *offsets, const uint32_t *lengths, uint32_t n_reads,
+                       uint32_t max_read_len, uint64_t n_samples, const sgk_event_params_t *p, const uint64_t *ev_slots,
+                       sgk_event_rec_t *events, uint32_t *n_events, void *workspace, size_t workspace_bytes, void *stream,
+                       const sgk_event_options_t *opt);
+
 /* ---- stat: per-read mean/std/median of raw and pA (src/stat.h, src/cfunc.c:126-159) */
 typedef struct sgk_stat_rec {
     float raw_mean, pa_mean, raw_std, pa_std;
@@ -863,6 +911,9 @@ typedef struct sgk_job_output {
 int sgk_job_create(int device, sgk_job_t **out);
 /* the options the job's submits use from now on (copied; null = defaults) */
 int sgk_job_set_options(sgk_job_t *job, const sgk_event_options_t *event_opt, const sgk_stat_options_t *stat_opt);
+/* Detector parameters of the job's SGK_TOOL_EVENT submits (copied; every submit flag and input format; `rna` is then
+ * ignored by them).  NULL: back to the presets by `rna`.  SGK_ERR_ARG when sgk_event_params_check refuses them. */
+int sgk_job_set_event_params(sgk_job_t *job, const sgk_event_params_t *params);
 void sgk_job_destroy(sgk_job_t *job);
 int sgk_job_device(const sgk_job_t *job);
 /* lengths[r]: samples of read r; blob_bytes[r] (SGK_SIGNAL_SVBZD, SGK_SIGNAL_TEXT): byte length of its blob / text column */
@@ -976,6 +1027,8 @@ float *sgk_signal_in_picoamps(const int16_t *raw, uint64_t len_raw_signal, doubl
                               double offset, double range);
 /* event_table getevents(size_t nsample, float *rawptr, int8_t rna) (src/events.c:553) */
 sgk_event_table sgk_getevents(size_t nsample, float *rawptr, int8_t rna);
+/* ... with the caller's own detector_param in place of the two presets (an empty table when they are out of domain) */
+sgk_event_table sgk_getevents_param(size_t nsample, float *rawptr, const sgk_event_params_t *params);
 
 /* jnn_pair_t, jnn_param_t, jnnv2_param_t exactly as src/jnn.h:13-16, 18-27, 74-81 */
 typedef struct {

@@ -63,6 +63,40 @@ class EventOptions(C.Structure):   # sgk_event_options_t (all zero = the default
                 ("reserved", C.c_uint32 * 2)]
 
 
+SGK_EVENT_W_MAX = 64
+SGK_EVENT_PARAMS_GENERIC = 1
+#: read length per step of the generic event kernel's chunk length (GENERIC_CHUNK_SAMPLES, csrc/event_generic.h): a read
+#: of n samples runs in 64 chunks of 64 * ceil(n / EVENT_GENERIC_CHUNK_SAMPLES) samples.  tests/test_event_params_cpu.py
+#: reads the header and compares.
+EVENT_GENERIC_CHUNK_SAMPLES = 4096
+
+
+class EventParams(C.Structure):   # sgk_event_params_t: detector_param of src/events.c:35-41
+    _fields_ = [("window_length1", C.c_uint32), ("window_length2", C.c_uint32), ("threshold1", C.c_float),
+                ("threshold2", C.c_float), ("peak_height", C.c_float), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 2)]
+
+    @classmethod
+    def preset(cls, rna: int) -> "EventParams":
+        p = cls()
+        check(load_library().sgk_event_params_preset(int(rna), C.byref(p)), "sgk_event_params_preset")
+        return p
+
+    def check(self) -> None:
+        """Raises when the parameters are outside the library's domain (sgk_event_params_check)."""
+        check(load_library().sgk_event_params_check(C.byref(self)), "sgk_event_params_check")
+
+    def generic(self) -> "EventParams":
+        """A copy that takes the generic kernel even when it equals a preset."""
+        q = EventParams.from_buffer_copy(bytes(self))
+        q.flags |= SGK_EVENT_PARAMS_GENERIC
+        return q
+
+    def astuple(self):
+        return (int(self.window_length1), int(self.window_length2), float(self.threshold1), float(self.threshold2),
+                float(self.peak_height))
+
+
 class StatOptions(C.Structure):   # sgk_stat_options_t
     _fields_ = [("kernels", C.c_int32), ("long_min", C.c_int32), ("debug_fault", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -282,6 +316,8 @@ ABI_SYMBOLS = [
     "sgk_profile_enable", "sgk_profile_reset", "sgk_profile_read",
     "sgk_event_host", "sgk_events_host_free", "sgk_pa_host", "sgk_stat_host", "sgk_jnn_host",
     "sgk_segs_host_free", "sgk_prefix_host", "sgk_signal_in_picoamps", "sgk_getevents",
+    "sgk_event_params_preset", "sgk_event_params_check", "sgk_event_workspace_bytes_param", "sgk_event_param",
+    "sgk_event_pa_param", "sgk_job_set_event_params", "sgk_getevents_param",
     "sgk_job_create", "sgk_job_destroy", "sgk_job_device", "sgk_job_begin", "sgk_job_submit", "sgk_job_submit_qts",
     "sgk_job_wait",
     "sgk_job_output",
@@ -393,6 +429,16 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.sgk_event_workspace_bytes_opt.argtypes = [C.c_uint32, C.c_uint64, C.c_uint32, OE]
     L.sgk_event_opt.argtypes = L.sgk_event.argtypes + [OE]
     L.sgk_event_pa_opt.argtypes = L.sgk_event_pa.argtypes + [OE]
+    if not (old_ok and not hasattr(L, "sgk_event_param")):   # (an A/B build from before the detector parameters)
+        OP = C.POINTER(EventParams)
+        L.sgk_event_params_preset.argtypes = [C.c_int, OP]
+        L.sgk_event_params_check.argtypes = [OP]
+        L.sgk_event_workspace_bytes_param.restype = C.c_size_t
+        L.sgk_event_workspace_bytes_param.argtypes = [C.c_uint32, C.c_uint64, C.c_uint32, OE, OP]
+        L.sgk_event_param.argtypes = [C.POINTER(Batch), OP] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p, OE]
+        L.sgk_event_pa_param.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, OP] + \
+            [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p, OE]
+        L.sgk_job_set_event_params.argtypes = [C.c_void_p, OP]
     if not (old_ok and not hasattr(L, "sgk_event_plan_opt")):
         L.sgk_event_plan_opt.argtypes = [C.c_uint32, C.c_uint64, C.c_uint32, C.c_int, OE, C.POINTER(EventPlan)]
         L.sgk_event_plan_opt.restype = C.c_int
@@ -777,6 +823,11 @@ class Job:
         are NOW: the job keeps a copy)"""
         check(self.L.sgk_job_set_options(self.h, C.byref(event_opt if event_opt is not None else EVENT_OPTIONS),
                                          C.byref(stat_opt if stat_opt is not None else STAT_OPTIONS)), "sgk_job_set_options")
+
+    def set_event_params(self, params: "EventParams" = None):
+        """detector parameters of the job's SGK_TOOL_EVENT submits from now on (copied); None: the presets by `rna`"""
+        check(self.L.sgk_job_set_event_params(self.h, C.byref(params) if params is not None else None),
+              "sgk_job_set_event_params")
 
     def close(self):
         if self.h:

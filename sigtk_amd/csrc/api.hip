@@ -380,6 +380,92 @@ static int run_event(const void *samples, bool float_input, const uint64_t *offs
     return launch_event(a, rna, float_input, w.n_fb_blocks, static_cast<hipStream_t>(stream));
 }
 
+// ---------------------------------------------------------------- caller-supplied detector parameters
+// Workspace of k_event_param: header, dispatch order, and per persistent workgroup the prefix arrays and the bitmap of
+// the longest read.  Nothing here depends on the batch's total samples.
+EvParamWorkspace event_param_workspace_layout(uint32_t n_reads, uint32_t max_read_len) {
+    EvParamWorkspace w;
+    const uint64_t nr = n_reads ? n_reads : 1;
+    size_t o = 0;
+    w.off_hdr = o;    o += sizeof(EvHeader);
+    w.off_order = o;  o += round_up(nr * 4 + 128 * 4, 64);
+    w.off_scratch = o;
+    const uint64_t L = max_read_len;
+    w.scratch_stride = round_up(2 * (L + 1) + (L / 64 + 2), 8);  // in doubles: 64-byte multiples
+    const size_t per_block = (size_t)w.scratch_stride * sizeof(double);
+    uint64_t nb = nr < PARAM_MAX_BLOCKS ? nr : PARAM_MAX_BLOCKS;
+    const uint64_t budget = PARAM_SCRATCH_BUDGET / per_block;
+    if (nb > budget) nb = budget ? budget : 1;
+    w.n_blocks = (uint32_t)nb;
+    w.total = o + (size_t)nb * per_block;
+    return w;
+}
+
+static bool params_equal_preset(const sgk_event_params_t *p, int rna) {
+    sgk_event_params_t q;
+    sgk_event_params_preset(rna, &q);
+    return p->window_length1 == q.window_length1 && p->window_length2 == q.window_length2 &&
+           memcmp(&p->threshold1, &q.threshold1, 4) == 0 && memcmp(&p->threshold2, &q.threshold2, 4) == 0 &&
+           memcmp(&p->peak_height, &q.peak_height, 4) == 0;
+}
+// -1: the generic kernel; 0 / 1: the preset's own kernels (sgk_event_opt with this rna)
+static int params_route(const sgk_event_params_t *p) {
+    if (p->flags & SGK_EVENT_PARAMS_GENERIC) return -1;
+    if (params_equal_preset(p, 0)) return 0;
+    if (params_equal_preset(p, 1)) return 1;
+    return -1;
+}
+
+static int run_event_param(const void *samples, bool float_input, const uint64_t *offsets, const uint32_t *lengths,
+                           const double *dig, const double *off, const double *rng, uint32_t n_reads,
+                           uint32_t max_read_len, uint64_t n_samples, const sgk_event_params_t *p,
+                           const uint64_t *ev_slots, sgk_event_rec_t *events, uint32_t *n_events, void *ws,
+                           size_t ws_bytes, void *stream, const sgk_event_options_t *opt) {
+    if (sgk_event_params_check(p) != SGK_OK) return SGK_ERR_ARG;
+    const int route = params_route(p);
+    if (route >= 0)
+        return run_event(samples, float_input, offsets, lengths, dig, off, rng, n_reads, max_read_len, n_samples, route,
+                         ev_slots, events, n_events, ws, ws_bytes, stream, opt);
+    if (n_reads == 0) return SGK_OK;
+    if (!samples || !offsets || !lengths || !ev_slots || !events || !n_events || !ws) return SGK_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(samples) & 15u) return SGK_ERR_ALIGN;
+    if (reinterpret_cast<uintptr_t>(events) & 15u) return SGK_ERR_ALIGN;
+    if (reinterpret_cast<uintptr_t>(ws) & 63u) return SGK_ERR_ALIGN;
+    const EvParamWorkspace w = event_param_workspace_layout(n_reads, max_read_len);
+    if (w.total > ws_bytes) return SGK_ERR_WORKSPACE;
+    char *base = static_cast<char *>(ws);
+    EvArgs a;
+    memset(&a, 0, sizeof a);
+    a.samples = samples;
+    a.offsets = offsets;
+    a.lengths = lengths;
+    a.dig = dig;
+    a.off = off;
+    a.rng = rng;
+    a.n_reads = n_reads;
+    a.n_alloc = n_samples;
+    a.ev_slots = ev_slots;
+    a.events = events;
+    a.n_events = n_events;
+    a.hdr = reinterpret_cast<EvHeader *>(base + w.off_hdr);
+    // longest first only pays when lengths differ
+    a.order = ((uint64_t)max_read_len * n_reads > n_samples + n_samples / 4) ? reinterpret_cast<uint32_t *>(base + w.off_order) : nullptr;
+    a.scratch = reinterpret_cast<double *>(base + w.off_scratch);
+    a.scratch_stride = w.scratch_stride;
+    EvParamArgs pa;
+    pa.w1 = p->window_length1;
+    pa.w2 = p->window_length2;
+    pa.thr1 = p->threshold1;
+    pa.thr2 = p->threshold2;
+    pa.ph = p->peak_height;
+    // the warm-up scales with the windows (a statistic looks w samples back); results do not depend on it
+    const uint32_t wmax = pa.w1 > pa.w2 ? pa.w1 : pa.w2;
+    const EvSegConfig sc = event_config(opt);
+    pa.lead = sc.lead_override > 0 ? sc.lead_override : (int)(4 * wmax < 64 ? 64 : 4 * wmax);
+    pa.max_read_len = max_read_len;
+    return launch_event_param(a, pa, float_input, w.n_blocks, static_cast<hipStream_t>(stream));
+}
+
 }  // namespace sgk
 
 using namespace sgk;
@@ -532,6 +618,53 @@ int sgk_pipeline(const sgk_batch_t *b, int rna, const uint64_t *ev_slots, sgk_ev
                      b->n_samples, rna, ev_slots, events, n_events, event_ws, event_ws_bytes, stream, event_opt);
 }
 
+// ---------------------------------------------------------------- event with caller-supplied parameters
+int sgk_event_params_preset(int rna, sgk_event_params_t *out) {
+    if (!out) return SGK_ERR_ARG;
+    memset(out, 0, sizeof *out);
+    out->window_length1 = rna ? 7u : 3u;
+    out->window_length2 = rna ? 14u : 6u;
+    out->threshold1 = rna ? 2.5f : 1.4f;
+    out->threshold2 = 9.0f;
+    out->peak_height = rna ? 1.0f : 0.2f;
+    return SGK_OK;
+}
+int sgk_event_params_check(const sgk_event_params_t *p) {
+    if (!p) return SGK_ERR_ARG;
+    if (p->window_length1 < 2 || p->window_length1 > SGK_EVENT_W_MAX) return SGK_ERR_ARG;
+    if (p->window_length2 < 2 || p->window_length2 > SGK_EVENT_W_MAX) return SGK_ERR_ARG;
+    // a long window under 4 lets the long detector emit a peak two samples in front of a short peak that opens at the
+    // emitting index (i - pos > w2 / 2 = 1): peaks 2 apart, which sgk_event_slots_for does not cover.  Equal windows
+    // see the same statistic and cannot do that.
+    if (p->window_length2 < 4 && p->window_length2 != p->window_length1) return SGK_ERR_ARG;
+    const float f[3] = {p->threshold1, p->threshold2, p->peak_height};
+    for (int k = 0; k < 3; ++k)
+        if (!(f[k] >= 0.0f) || !(f[k] <= FLT_MAX)) return SGK_ERR_ARG;  // NaN fails both comparisons
+    if (p->flags & ~SGK_EVENT_PARAMS_GENERIC) return SGK_ERR_ARG;
+    return SGK_OK;
+}
+size_t sgk_event_workspace_bytes_param(uint32_t n_reads, uint64_t n_samples, uint32_t max_read_len,
+                                       const sgk_event_options_t *opt, const sgk_event_params_t *p) {
+    if (sgk_event_params_check(p) != SGK_OK) return 0;
+    if (params_route(p) >= 0) return sgk_event_workspace_bytes_opt(n_reads, n_samples, max_read_len, opt);
+    return event_param_workspace_layout(n_reads, max_read_len).total;
+}
+int sgk_event_param(const sgk_batch_t *b, const sgk_event_params_t *p, const uint64_t *ev_slots, sgk_event_rec_t *events,
+                    uint32_t *n_events, void *ws, size_t ws_bytes, void *stream, const sgk_event_options_t *opt) {
+    if (sgk_event_params_check(p) != SGK_OK) return SGK_ERR_ARG;
+    const int rc = check_batch(b);
+    if (rc != SGK_OK) return rc;
+    return run_event_param(b->samples, false, b->offsets, b->lengths, b->digitisation, b->offset, b->range, b->n_reads,
+                           b->max_read_len, b->n_samples, p, ev_slots, events, n_events, ws, ws_bytes, stream, opt);
+}
+int sgk_event_pa_param(const float *pa, const uint64_t *offsets, const uint32_t *lengths, uint32_t n_reads,
+                       uint32_t max_read_len, uint64_t n_samples, const sgk_event_params_t *p, const uint64_t *ev_slots,
+                       sgk_event_rec_t *events, uint32_t *n_events, void *ws, size_t ws_bytes, void *stream,
+                       const sgk_event_options_t *opt) {
+    return run_event_param(pa, true, offsets, lengths, nullptr, nullptr, nullptr, n_reads, max_read_len, n_samples, p,
+                           ev_slots, events, n_events, ws, ws_bytes, stream, opt);
+}
+
 int sgk_event_status(const void *ws, sgk_event_status_t *out, void *stream) {
     if (!ws || !out) return SGK_ERR_ARG;
     EvHeader h;
@@ -626,7 +759,8 @@ int sgk_pa_host(const sgk_host_batch_t *hb, float *pa_out) {
 
 // shared tail of sgk_event_host / sgk_getevents: run on an uploaded batch view (raw or pA input)
 static int event_collect(const void *d_samples, bool float_input, const DeviceBatch &db, const sgk_batch_t *view,
-                         int rna, sgk_events_host_t *out, const sgk_event_options_t *opt = nullptr) {
+                         int rna, sgk_events_host_t *out, const sgk_event_options_t *opt = nullptr,
+                         const sgk_event_params_t *params = nullptr) {
     const uint32_t nr = (uint32_t)db.lengths.size();
     memset(out, 0, sizeof *out);
     out->n_reads = nr;
@@ -640,10 +774,18 @@ static int event_collect(const void *d_samples, bool float_input, const DeviceBa
     if ((rc = d_slots.alloc((nr + 1) * sizeof(uint64_t))) != SGK_OK) return rc;
     if ((rc = d_ev.alloc(nslots * sizeof(sgk_event_rec_t))) != SGK_OK) return rc;
     if ((rc = d_nev.alloc((size_t)nr * 4)) != SGK_OK) return rc;
-    const size_t wsb = sgk_event_workspace_bytes_opt(nr, db.n_samples, db.max_len, opt);
+    const size_t wsb = params ? sgk_event_workspace_bytes_param(nr, db.n_samples, db.max_len, opt, params)
+                              : sgk_event_workspace_bytes_opt(nr, db.n_samples, db.max_len, opt);
     if ((rc = d_ws.alloc(wsb)) != SGK_OK) return rc;
     SGK_HIP_TRY(hipMemcpy(d_slots.p, slots.data(), (nr + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-    if (float_input)
+    if (params && float_input)
+        rc = sgk_event_pa_param(static_cast<const float *>(d_samples), view->offsets, view->lengths, nr, db.max_len,
+                                db.n_samples, params, d_slots.as<uint64_t>(), d_ev.as<sgk_event_rec_t>(),
+                                d_nev.as<uint32_t>(), d_ws.p, wsb, nullptr, opt);
+    else if (params)
+        rc = sgk_event_param(view, params, d_slots.as<uint64_t>(), d_ev.as<sgk_event_rec_t>(), d_nev.as<uint32_t>(),
+                             d_ws.p, wsb, nullptr, opt);
+    else if (float_input)
         rc = sgk_event_pa_opt(static_cast<const float *>(d_samples), view->offsets, view->lengths, nr, db.max_len,
                               db.n_samples, rna, d_slots.as<uint64_t>(), d_ev.as<sgk_event_rec_t>(), d_nev.as<uint32_t>(),
                               d_ws.p, wsb, nullptr, opt);
@@ -722,9 +864,10 @@ float *sgk_signal_in_picoamps(const int16_t *raw, uint64_t n, double digitisatio
     return out;
 }
 
-sgk_event_table sgk_getevents(size_t nsample, float *rawptr, int8_t rna) {
+static sgk_event_table getevents_impl(size_t nsample, float *rawptr, int rna, const sgk_event_params_t *params) {
     sgk_event_table et;
     memset(&et, 0, sizeof et);
+    if (params && sgk_event_params_check(params) != SGK_OK) return et;
     if (!rawptr || nsample == 0 || nsample > 0x7fffffffull || sgk_device_count() <= 0) return et;
     DeviceBatch db;  // only offsets/lengths bookkeeping is used here
     db.offsets.assign(1, 256);  // head/tail room for the event fast path
@@ -744,7 +887,7 @@ sgk_event_table sgk_getevents(size_t nsample, float *rawptr, int8_t rna) {
     view.offsets = d_o.as<uint64_t>();
     view.lengths = d_l.as<uint32_t>();
     sgk_events_host_t ev;
-    if (event_collect(d_pa.p, true, db, &view, rna, &ev) != SGK_OK) {
+    if (event_collect(d_pa.p, true, db, &view, rna, &ev, nullptr, params) != SGK_OK) {
         sgk_events_host_free(&ev);
         return et;
     }
@@ -763,6 +906,15 @@ sgk_event_table sgk_getevents(size_t nsample, float *rawptr, int8_t rna) {
     }
     sgk_events_host_free(&ev);
     return et;
+}
+sgk_event_table sgk_getevents(size_t nsample, float *rawptr, int8_t rna) {
+    return getevents_impl(nsample, rawptr, rna, nullptr);
+}
+sgk_event_table sgk_getevents_param(size_t nsample, float *rawptr, const sgk_event_params_t *params) {
+    sgk_event_table et;
+    memset(&et, 0, sizeof et);
+    if (!params) return et;
+    return getevents_impl(nsample, rawptr, 0, params);
 }
 
 }  // extern "C"

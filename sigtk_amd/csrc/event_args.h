@@ -151,6 +151,29 @@ EvWorkspace event_workspace_layout(const EvSegConfig &c, uint32_t n_reads, uint6
 
 int launch_event(const EvArgs &a, int rna, bool float_input, uint32_t n_fb_blocks, hipStream_t st);  // event_launch.hip
 
+// ---- caller-supplied detector parameters (k_event_param, event_param.hip) ----------------------------------------
+// What the generic kernel takes beside EvArgs, of which it uses the batch, the arena, hdr, order (null: batch order) and
+// scratch / scratch_stride: workgroup b owns scratch[b * scratch_stride ..): P (max_read_len + 1 doubles), P2 (the
+// same), then the bitmap of one read (max_read_len / 64 + 2 words).
+struct EvParamArgs {
+    uint32_t w1, w2;
+    float thr1, thr2, ph;
+    int lead;               // speculative warm-up in samples (results do not depend on it)
+    uint32_t max_read_len;
+};
+// persistent workgroups.  Registers and LDS would let 3072 be resident, but the detector's loads of the prefix arrays are
+// uncoalesced and the workgroups' scratch is their working set: 10 000 x 100 000 samples take 101.5 ms with 768, 95.5 ms
+// with 1024 and 142.5 ms with 2663 workgroups (profiles/event_params.md)
+constexpr uint32_t PARAM_MAX_BLOCKS = 1024;
+constexpr uint64_t PARAM_SCRATCH_BUDGET = 2ull << 30;  // bytes of per-workgroup scratch at most (fewer workgroups, >= 1)
+struct EvParamWorkspace {
+    size_t off_hdr, off_order, off_scratch, total;
+    uint64_t scratch_stride;  // doubles per workgroup
+    uint32_t n_blocks;
+};
+EvParamWorkspace event_param_workspace_layout(uint32_t n_reads, uint32_t max_read_len);
+int launch_event_param(const EvArgs &a, const EvParamArgs &pa, bool float_input, uint32_t n_blocks, hipStream_t st);  // event_launch.hip
+
 // ---- one launch per kernel, defined in the unit that holds the kernel (without relocatable device code a kernel is
 // launched from its own translation unit); launch_event is made of these.  rna / float_input select the kernel's
 // <W1, T> instance: detector preset (3: DNA, 7: RNA) and sample type (int16_t or float).
@@ -159,5 +182,6 @@ int launch_k_event_seg(int rna, bool float_input, hipStream_t st, const EvArgs &
 int launch_k_event(int rna, bool float_input, hipStream_t st, const EvArgs &a);                // event_whole.hip
 int launch_k_event_multi(int rna, bool float_input, hipStream_t st, const EvArgs &a);          // event_multi.hip
 int launch_k_event_fallback(int rna, bool float_input, uint32_t n_fb_blocks, hipStream_t st, const EvArgs &a);  // event_fallback.hip
+int launch_k_event_param(bool float_input, uint32_t n_blocks, hipStream_t st, const EvArgs &a, const EvParamArgs &pa);  // event_param.hip
 
 }  // namespace sgk

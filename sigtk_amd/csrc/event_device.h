@@ -26,6 +26,8 @@
 //                    the wave of a segment runs the detector over it, checks the seam against the segment in front and
 //                    builds its own events (chain_segment, round 4; a kernel of its own since round 5)
 //   k_event_multi    several short reads per wave, `lanes` lanes each, on a side stream beside k_event (round 3)
+//   k_event_param    persistent kernel for caller-supplied detector parameters: the fallback's exact path with the
+//                    windows and thresholds as run-time values (event_param.hip)
 //   k_event_fallback persistent kernel over the reads that fail the exactness guard: lane 0 reproduces
 //                    compute_sum_sumsq's sequential double prefix scan (events.c:293-303) into workspace
 //                    scratch, then the same detector and builder run with window/event sums taken as
@@ -50,8 +52,12 @@
 //   event_whole.hip    k_event.
 //   event_seg.hip      k_seg_plan, chain_segment, k_event_seg.
 //   event_multi.hip    k_event_multi.
-//   event_fallback.hip k_event_fallback and what only it uses: the generic detector on the reference's prefix arrays
-//                      (detect_pass), the sequential prefix scan, the builder on those arrays.
+//   event_generic.h    the exact generic path on the reference's sequentially rounded prefix arrays: the prefix scan, the
+//                      two automata stepped on every index (detect_pass / detect_read), the builder on those arrays --
+//                      for a preset (<W1>) or for parameters given at run time (<0>, DetVals).
+//   event_fallback.hip k_event_fallback: a preset's reads that fail the exactness guard, on event_generic.h.
+//   event_param.hip    k_event_param: caller-supplied detector parameters (sgk_event_param), on event_generic.h; a
+//                      persistent grid with per-workgroup prefix arrays, launched by launch_event_param.
 //   event_launch.hip   launch_event: order, plan, side streams, the launches; it holds no kernel and launches them through
 //                      the launch_k_* functions of event_args.h, one per kernel, each defined next to its kernel.
 #pragma once

@@ -53,4 +53,17 @@ int launch_event(const EvArgs &a, int rna, bool float_input, uint32_t n_fb_block
     return launch_k_event_fallback(rna, float_input, n_fb_blocks, st, a);
 }
 
+// The generic kernel for caller-supplied parameters: the header, the dispatch order, one persistent launch.
+int launch_event_param(const EvArgs &a, const EvParamArgs &pa, bool float_input, uint32_t n_blocks, hipStream_t st) {
+    if (a.n_reads == 0) return SGK_OK;
+    ProfScope whole("path:event_param", st);
+    SGK_HIP_TRY(hipMemsetAsync(a.hdr, 0, sizeof(EvHeader), st));
+    EvArgs ao = a;
+    if (a.n_reads >= ORDER_MIN_READS && a.order) {
+        const int rc = launch_order(a.lengths, a.n_reads, a.order, a.order + a.n_reads, st);
+        if (rc != SGK_OK) return rc;
+    } else ao.order = nullptr;
+    return launch_k_event_param(float_input, n_blocks, st, ao, pa);
+}
+
 }  // namespace sgk

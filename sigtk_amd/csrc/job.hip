@@ -161,6 +161,8 @@ struct sgk_job {
     bool begun = false, submitted = false, ent_over = false;
     sgk_event_status_t ev_status;
     sgk_event_options_t ev_opt;   // sgk_job_set_options (all zero: the defaults)
+    sgk_event_params_t ev_params; // sgk_job_set_event_params
+    bool has_ev_params = false;
     sgk_stat_options_t st_opt;
 };
 
@@ -209,6 +211,18 @@ int sgk_job_set_options(sgk_job_t *j, const sgk_event_options_t *event_opt, cons
     else memset(&j->ev_opt, 0, sizeof j->ev_opt);
     if (stat_opt) j->st_opt = *stat_opt;
     else memset(&j->st_opt, 0, sizeof j->st_opt);
+    return SGK_OK;
+}
+
+int sgk_job_set_event_params(sgk_job_t *j, const sgk_event_params_t *params) {
+    if (!j) return SGK_ERR_ARG;
+    if (!params) {
+        j->has_ev_params = false;
+        return SGK_OK;
+    }
+    if (sgk_event_params_check(params) != SGK_OK) return SGK_ERR_ARG;
+    j->ev_params = *params;
+    j->has_ev_params = true;
     return SGK_OK;
 }
 
@@ -761,10 +775,15 @@ int sgk_job_submit(sgk_job_t *j, int tool, int rna, int pore, int flags) {
                     if ((rc = j->d_out[k].ensure(s * 4)) != SGK_OK) return rc;
             }
             if ((rc = j->d_cnt.ensure(nr * 4)) != SGK_OK) return rc;
-            j->ws_bytes = ev ? sgk_event_workspace_bytes_opt(j->n_reads, j->n_samples, j->max_len, &j->ev_opt)
-                             : sgk_jnn_workspace_bytes(j->n_reads, j->n_samples, j->max_len);
+            const bool evp = ev && j->has_ev_params;
+            j->ws_bytes = evp ? sgk_event_workspace_bytes_param(j->n_reads, j->n_samples, j->max_len, &j->ev_opt, &j->ev_params)
+                          : ev ? sgk_event_workspace_bytes_opt(j->n_reads, j->n_samples, j->max_len, &j->ev_opt)
+                               : sgk_jnn_workspace_bytes(j->n_reads, j->n_samples, j->max_len);
             if ((rc = j->d_ws.ensure(j->ws_bytes)) != SGK_OK) return rc;
-            if (ev)
+            if (evp)
+                rc = sgk_event_param(&view, &j->ev_params, j->d_slots.as<uint64_t>(), j->d_out[0].as<sgk_event_rec_t>(),
+                                     j->d_cnt.as<uint32_t>(), j->d_ws.p, j->d_ws.cap, st, &j->ev_opt);
+            else if (ev)
                 rc = sgk_event_opt(&view, rna, j->d_slots.as<uint64_t>(), j->d_out[0].as<sgk_event_rec_t>(),
                                    j->d_cnt.as<uint32_t>(), j->d_ws.p, j->d_ws.cap, st, &j->ev_opt);
             else

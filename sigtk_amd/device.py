@@ -101,7 +101,8 @@ def upload_reads(reads, dig, off, rng, device: torch.device) -> DeviceReads:
 class EventArena:
     """Output arena + workspace of sgk_event for one batch shape (allocated once, reused)."""
 
-    def __init__(self, b: DeviceReads):
+    def __init__(self, b: DeviceReads, params: Optional["api.EventParams"] = None):
+        """`params`: size the workspace for sgk_event_param with these detector parameters as well"""
         L = api.load_library()
         dev = b.samples.device
         slots = np.zeros(b.n_reads + 1, dtype=np.int64)
@@ -116,8 +117,21 @@ class EventArena:
         # (sized for the options of the call that follows: api.EVENT_OPTIONS as they are now)
         self.opt = api.EventOptions.from_buffer_copy(bytes(api.EVENT_OPTIONS))
         self.ws_bytes = int(L.sgk_event_workspace_bytes_opt(b.n_reads, b.n_samples, b.max_read_len, C.byref(self.opt)))
+        if params is not None:
+            self.ws_bytes = max(self.ws_bytes, self.param_workspace_bytes(b, params))
         self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
         assert self.ws.data_ptr() % 64 == 0
+
+    def param_workspace_bytes(self, b: DeviceReads, params: "api.EventParams") -> int:
+        params.check()
+        return int(api.load_library().sgk_event_workspace_bytes_param(b.n_reads, b.n_samples, b.max_read_len,
+                                                                     C.byref(self.opt), C.byref(params)))
+
+    def ensure_workspace(self, nbytes: int) -> None:
+        if nbytes > self.ws_bytes:
+            self.ws_bytes = int(nbytes)
+            self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.ws.device)
+            assert self.ws.data_ptr() % 64 == 0
 
     def status(self) -> api.EventStatus:
         L = api.load_library()
@@ -152,12 +166,37 @@ class EventArena:
         return self.events.view(torch.float32)[:, 3]
 
 
-def event(b: DeviceReads, arena: EventArena, rna: int) -> None:
-    """Enqueue one pass of the event path over the batch on the current stream (async)."""
+def event(b: DeviceReads, arena: EventArena, rna: int, params: Optional["api.EventParams"] = None) -> None:
+    """Enqueue one pass of the event path over the batch on the current stream (async).  With `params` the detector
+    takes the caller's parameters (sgk_event_param) and `rna` is ignored; the arena's workspace grows when it was not
+    sized for them."""
     L = api.load_library()
     view = b.view()
+    if params is not None:
+        arena.ensure_workspace(arena.param_workspace_bytes(b, params))
+        api.check(L.sgk_event_param(C.byref(view), C.byref(params), _ptr(arena.slots), _ptr(arena.events),
+                                    _ptr(arena.n_events), _ptr(arena.ws), arena.ws_bytes, _stream_ptr(),
+                                    C.byref(arena.opt)), "sgk_event_param")
+        return
     api.check(L.sgk_event_opt(C.byref(view), int(rna), _ptr(arena.slots), _ptr(arena.events), _ptr(arena.n_events),
                               _ptr(arena.ws), arena.ws_bytes, _stream_ptr(), C.byref(arena.opt)), "sgk_event_opt")
+
+
+def event_pa(pa: torch.Tensor, b: DeviceReads, arena: EventArena, rna: int,
+             params: Optional["api.EventParams"] = None) -> None:
+    """The event path on pA floats laid out like the batch's samples (sgk_event_pa_opt / sgk_event_pa_param)."""
+    L = api.load_library()
+    assert pa.dtype == torch.float32 and pa.numel() >= b.n_samples and pa.data_ptr() % 16 == 0
+    if params is not None:
+        arena.ensure_workspace(arena.param_workspace_bytes(b, params))
+        api.check(L.sgk_event_pa_param(_ptr(pa), _ptr(b.offsets), _ptr(b.lengths), b.n_reads, b.max_read_len,
+                                       b.n_samples, C.byref(params), _ptr(arena.slots), _ptr(arena.events),
+                                       _ptr(arena.n_events), _ptr(arena.ws), arena.ws_bytes, _stream_ptr(),
+                                       C.byref(arena.opt)), "sgk_event_pa_param")
+        return
+    api.check(L.sgk_event_pa_opt(_ptr(pa), _ptr(b.offsets), _ptr(b.lengths), b.n_reads, b.max_read_len, b.n_samples,
+                                 int(rna), _ptr(arena.slots), _ptr(arena.events), _ptr(arena.n_events), _ptr(arena.ws),
+                                 arena.ws_bytes, _stream_ptr(), C.byref(arena.opt)), "sgk_event_pa_opt")
 
 
 # ---------------------------------------------------------------------- stat / jnn / prefix / pa (device API)

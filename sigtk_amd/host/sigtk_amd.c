@@ -17,6 +17,9 @@
  * the GPU with the new column written there (k_slow5_text_write) and copies them out.
  * Extra options: --gpus N, --batch-samples M, -t/--threads T, --host-decode.
  */
+#include <ctype.h>
+#include <errno.h>
+#include <float.h>
 #include <getopt.h>
 #include <pthread.h>
 #include <sched.h>
@@ -376,6 +379,7 @@ typedef struct {
     b5_file_t *f;
     int mode, nthreads, host_decode;
     int gpu_text;        /* --gpu-text (pa / event, whole-file mode): the rows come from the GPU as text */
+    const sgk_event_params_t *ev_params; /* event --detector: every job's detector parameters (NULL: the presets) */
     uint64_t text_bytes; /* ... their bytes over PCIe */
     int zrec;            /* records go to the GPU as they sit in the file (zlib / zstd records, svb-zd or uncompressed signal, auxiliary columns of known types) */
     sgk_aux_field_t *aux_tab; /* ... those columns, in header order */
@@ -1017,6 +1021,13 @@ static void *writer_main(void *arg) {
     return NULL;
 }
 
+/* event --detector: a new job takes the command line's detector parameters */
+static void job_detector(const pipe_t *P, sgk_job_t *job) {
+    if (!P->ev_params) return;
+    const int rc = sgk_job_set_event_params(job, P->ev_params);
+    if (rc != SGK_OK) gpu_fail("sgk_job_set_event_params", rc);
+}
+
 /* ------------------------------------------------------------------ reader thread
  * Pulls the records' bytes off the file (sequentially, or by read id) into free batches and hands each full batch
  * to the loader, so that file reads overlap with inflating / staging the previous batch. */
@@ -1027,6 +1038,7 @@ static batch_t *take_free_batch(pipe_t *P) {
         b = &P->pool[P->n_created];
         const int rc = sgk_job_create(P->n_created % P->n_gpus, &b->job);
         if (rc != SGK_OK) gpu_fail("sgk_job_create", rc);
+        job_detector(P, b->job);
         P->n_created++;
     }
     if (!b) b = q_pop(&P->free_q);
@@ -1102,6 +1114,7 @@ static void run_pipeline(pipe_t *P, int n_gpus, double t_init) {
     for (int i = 0; i < P->n_created; i++) {
         const int rc = sgk_job_create(i % n_gpus, &pool[i].job);
         if (rc != SGK_OK) gpu_fail("sgk_job_create", rc);
+        job_detector(P, pool[i].job);
         q_push(&P->free_q, &pool[i]);
     }
     const double t_jobs = realtime() - t_jobs0;
@@ -1190,7 +1203,50 @@ static struct option long_options[] = {
     {"output", required_argument, 0, 'o'},  {"print-stat", no_argument, 0, 0},   {"no-header", no_argument, 0, 'n'},
     {"compact", no_argument, 0, 'c'},       {"gpus", required_argument, 0, 0},   {"batch-samples", required_argument, 0, 0},
     {"threads", required_argument, 0, 't'}, {"host-decode", no_argument, 0, 0},  {"host-inflate", no_argument, 0, 0},
-    {"gpu-text", no_argument, 0, 0},        {"aux-slack", required_argument, 0, 0}, {0, 0, 0, 0}};
+    {"gpu-text", no_argument, 0, 0},        {"aux-slack", required_argument, 0, 0}, {"detector", required_argument, 0, 0},
+    {0, 0, 0, 0}};
+
+/* event --detector W1,W2,THR1,THR2,PEAK_HEIGHT: exactly five fields, none empty, nothing behind a number, windows as
+ * decimal integers; the domain is the library's (sgk_event_params_check, a host-only call).  Returns 0, or -1 with *why
+ * set to what is wrong. */
+static int parse_detector(const char *arg, sgk_event_params_t *out, const char **why) {
+    double v[5];
+    const char *p = arg;
+    memset(out, 0, sizeof *out);
+    for (int k = 0; k < 5; k++) {
+        if (*p == '\0' || *p == ',') { *why = "an empty field"; return -1; }
+        if (isspace((unsigned char)*p)) { *why = "white space in a field"; return -1; }
+        char *end = NULL;
+        if (k < 2) {
+            if (*p < '0' || *p > '9') { *why = "a window length that is no unsigned integer"; return -1; }
+            errno = 0;
+            const unsigned long long u = strtoull(p, &end, 10);
+            if (errno || u > 0xffffffffull) { *why = "a window length out of range"; return -1; }
+            v[k] = (double)u;
+        } else {
+            v[k] = strtod(p, &end);
+            if (end == p) { *why = "a field that is no number"; return -1; }
+            /* (in double, before the cast: a double beyond float's range has no defined conversion; NaN fails too) */
+            if (!(v[k] >= 0.0 && v[k] <= (double)FLT_MAX)) { *why = "a threshold or peak height that is not finite and >= 0"; return -1; }
+        }
+        if (k < 4) {
+            if (*end == '\0') { *why = "fewer than five fields"; return -1; }
+            if (*end != ',') { *why = "text behind a number"; return -1; }
+            p = end + 1;
+        } else if (*end == ',') { *why = "more than five fields"; return -1; }
+        else if (*end != '\0') { *why = "text behind a number"; return -1; }
+    }
+    out->window_length1 = (uint32_t)v[0];
+    out->window_length2 = (uint32_t)v[1];
+    out->threshold1 = (float)v[2];
+    out->threshold2 = (float)v[3];
+    out->peak_height = (float)v[4];
+    if (sgk_event_params_check(out) != SGK_OK) {
+        *why = "values out of domain (windows 2 .. 64, W2 of 2 or 3 only with W1 = W2; thresholds and peak height finite and >= 0)";
+        return -1;
+    }
+    return 0;
+}
 
 /* What a pipeline needs to send the records of P->f to the GPU as they sit in the file (cmain, qts --gpu-inflate): the
  * header's auxiliary columns as sgk_job_begin_zrec_aux takes them, how many are arrays, the bytes of the others, the slack
@@ -1229,6 +1285,8 @@ static int cmain(int argc, char *argv[], const char *mode_s) {
     opt_t opt = {0, 0, 0, 0};
     int n_gpus = 1, nthreads = 0, host_decode = 0, host_inflate = 0, batch_set = 0, gpu_text = 0;
     uint64_t aux_slack = 256; /* bytes of room per array column of a zlib record sent to the GPU (load_parse) */
+    sgk_event_params_t det;   /* event --detector */
+    int have_det = 0;
     /* default batch: small (16 M samples) where the GPU stage is short -- a job's buffers are then cheap to set up
      * and the host stages overlap sooner; 64 M for jnn / prefix, whose one-read-per-lane kernels take as long for
      * a small batch as for a large one */
@@ -1262,6 +1320,17 @@ static int cmain(int argc, char *argv[], const char *mode_s) {
         } else if (c == 0 && longindex == 13) {
             aux_slack = strtoull(optarg, NULL, 10);
             if (aux_slack > (1ull << 20)) aux_slack = 1ull << 20;
+        } else if (c == 0 && longindex == 14) {
+            const char *why = "";
+            if (strcmp(mode_s, "event") != 0) {
+                ERROR("cmain", "%s", "--detector is an option of the event subtool");
+                exit(EXIT_FAILURE);
+            }
+            if (parse_detector(optarg, &det, &why) != 0) {
+                ERROR("cmain", "--detector wants W1,W2,THR1,THR2,PEAK_HEIGHT; '%s' has %s", optarg, why);
+                exit(EXIT_FAILURE);
+            }
+            have_det = 1;
         }
     }
     if (is_ent && (argc - optind != 1 || fp_help == stdout)) {
@@ -1368,6 +1437,7 @@ static int cmain(int argc, char *argv[], const char *mode_s) {
     /* rows as text from the GPU: the three large-output grammars, when the whole file is read in order (with read ids
      * on the command line, and for the other subtools, the option changes nothing) */
     P.gpu_text = gpu_text && (mode == MODE_PA || mode == MODE_EVENT) && P.n_ids == 0;
+    P.ev_params = (have_det && mode == MODE_EVENT) ? &det : NULL;  /* the read kind no longer selects the detector */
     run_pipeline(&P, n_gpus, t_init);
     fflush(stdout);
     b5_close(f);
