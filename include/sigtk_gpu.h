@@ -78,7 +78,15 @@ extern "C" {
  *        qts_record* fields at the end of sgk_job_output_t (`qts --gpu-deflate`: records deflated on the GPU);
  *        sgk_slow5_text_* and SGK_SIGNAL_TEXT as input and output format of sgk_job_submit_qts (`qts` on text SLOW5);
  *        SGK_QTS_ZREC_FRAMES (`qts --gpu-inflate`: the frames of the record mode taken from the records inflated on the GPU);
- *        sgk_sigraw_unit_samples, sgk_sigraw_gather and sgk_job_begin_zrec_signal (compressed records around an uncompressed signal). */
+ *        sgk_sigraw_unit_samples, sgk_sigraw_gather and sgk_job_begin_zrec_signal (compressed records around an uncompressed signal).
+ *        The literal medians (additive to 0.2.3, no version change: every 0.2.3 caller keeps working): pA medians that are a
+ *        pick among equal-comparing or unordered values (a zero; a unit or offset that is not finite) are the element the
+ *        reference's selection leaves at n / 2.  sgk_stat / sgk_stat_pa / sgk_prefix redo them on scratch rows that
+ *        sgk_stat_workspace_bytes / sgk_prefix_workspace_bytes now ask for: min(n_reads, 1024) rows of 2 max_read_len bytes,
+ *        fewer rows where that would pass SGK_LITERAL_MAX_BYTES (256 MiB), never less than one.  A smaller workspace, down
+ *        to the 0.2.3 size, still works: with fewer rows fewer workgroups share the work; with none such a median is
+ *        pA(raw order statistic) as before, its record keeps SGK_MEDIAN_INEXACT / SGK_MEDIAN_INEXACT_POLYA in `reserved`, and
+ *        sgk_stat_literal_status counts it. */
 #define SGK_VERSION_STRING "0.2.3"
 
 /* ---- error codes --------------------------------------------------------------- */
@@ -284,8 +292,14 @@ typedef struct sgk_stat_rec {
     int32_t raw_median;
     float pa_median;
     uint32_t n;
-    uint32_t reserved;
+    uint32_t reserved;   /* 0, or SGK_MEDIAN_INEXACT: see below */
 } sgk_stat_rec_t; /* 32 bytes per read */
+/* `reserved` of a stat / prefix record after the call: pa_median / adapt_median (SGK_MEDIAN_INEXACT) or polya_median
+ * (SGK_MEDIAN_INEXACT_POLYA) is a zero, or the read's unit or offset is not finite, and the workspace had no scratch row
+ * to redo it with the reference's selection: the value is pA(raw order statistic), which can differ from the reference's
+ * in the sign of a zero, or in inf against NaN.  Never set with a workspace of sgk_*_workspace_bytes. */
+#define SGK_MEDIAN_INEXACT 4u
+#define SGK_MEDIAN_INEXACT_POLYA 8u
 
 size_t sgk_stat_workspace_bytes(uint32_t n_reads, uint64_t n_samples, uint32_t max_read_len);
 int sgk_stat(const sgk_batch_t *batch, sgk_stat_rec_t *out, void *workspace, size_t workspace_bytes,
@@ -311,7 +325,7 @@ typedef struct sgk_prefix_rec {
     float adapt_mean, adapt_std, adapt_median;
     float polya_mean, polya_std, polya_median;
     uint32_t n;
-    uint32_t reserved;
+    uint32_t reserved;   /* 0, or SGK_MEDIAN_INEXACT | SGK_MEDIAN_INEXACT_POLYA */
 } sgk_prefix_rec_t; /* 48 bytes per read */
 
 size_t sgk_prefix_workspace_bytes(uint32_t n_reads, uint64_t n_samples, uint32_t max_read_len);
@@ -392,6 +406,14 @@ typedef struct sgk_long_status {
                            * jobs report the count through sgk_job_long_declined() */
 } sgk_long_status_t;
 int sgk_stat_long_status(const void *workspace, size_t workspace_bytes, uint32_t n_reads, sgk_long_status_t *out);
+/* the last sgk_stat / sgk_stat_pa / sgk_prefix call on this workspace (synchronises): medians redone with the reference's
+ * own selection, and medians that would have been but for the workspace (their records keep SGK_MEDIAN_INEXACT*) */
+#define SGK_LITERAL_MAX_BYTES (256u << 20) /* what the scratch rows add to sgk_stat / sgk_prefix_workspace_bytes at most
+                                            * (one row, 2 max_read_len bytes, if a single read is longer than that) */
+typedef struct sgk_literal_status {
+    uint32_t n_literal, n_inexact;
+} sgk_literal_status_t;
+int sgk_stat_literal_status(const void *workspace, size_t workspace_bytes, uint32_t n_reads, sgk_literal_status_t *out);
 
 /* ---- ent: the histograms behind `sigtk ent` (src/ent.c) ----------------- */
 /* The counting runs on the GPU, the sum of -p*log2(p) over the (few thousand) non-empty bins on the host

@@ -32,29 +32,44 @@ void orc_pa(const int16_t *raw, int64_t n, double digitisation, double offset, d
 
 /* ------------------------------------------------------------------ selection */
 
+/* src/ksort.h:233-259, step for step: WHICH element ends at position k matters, not only its value.  Floats that
+ * compare equal need not be the same bits (+0 and -0) and a NaN orders with nothing, so the element the reference
+ * returns is whatever its own exchanges leave at k; any other exact selection may return another one.  The working
+ * range [lo, hi] shrinks around k:
+ *   - one element: done; two: put them in order, done;
+ *   - order a[mid], a[lo], a[hi] with three conditional exchanges (hi against mid, hi against lo, lo against mid),
+ *     so that a[lo] is the pivot, then park a[mid] at lo + 1;
+ *   - i walks up from lo + 1 past elements below the pivot, j walks down from hi past elements above it, both
+ *     pre-stepping; while they have not crossed, exchange a[i] and a[j];
+ *   - the pivot goes to j; the side(s) of j that hold k stay. */
 #define ORC_DEFINE_SELECT(NAME, T)                                   \
     static T NAME(T *a, int64_t n, int64_t k) {                      \
         int64_t lo = 0, hi = n - 1;                                  \
-        while (lo < hi) {                                            \
-            const T pivot = a[lo + (hi - lo) / 2];                   \
-            int64_t i = lo, j = hi;                                  \
-            while (i <= j) {                                         \
-                while (a[i] < pivot) i++;                            \
-                while (pivot < a[j]) j--;                            \
-                if (i <= j) {                                        \
-                    const T tmp = a[i];                              \
-                    a[i] = a[j];                                     \
-                    a[j] = tmp;                                      \
-                    i++;                                             \
-                    j--;                                             \
-                }                                                    \
+        for (;;) {                                                   \
+            T tmp;                                                   \
+            if (hi <= lo) return a[k];                               \
+            if (hi == lo + 1) {                                      \
+                if (a[hi] < a[lo]) ORC_SWAP(a[lo], a[hi]);           \
+                return a[k];                                         \
             }                                                        \
-            if (k <= j) hi = j;                                      \
-            else if (k >= i) lo = i;                                 \
-            else break;                                              \
+            const int64_t mid = lo + (hi - lo) / 2;                  \
+            if (a[hi] < a[mid]) ORC_SWAP(a[mid], a[hi]);             \
+            if (a[hi] < a[lo]) ORC_SWAP(a[lo], a[hi]);               \
+            if (a[lo] < a[mid]) ORC_SWAP(a[mid], a[lo]);             \
+            ORC_SWAP(a[mid], a[lo + 1]);                             \
+            int64_t i = lo + 1, j = hi;                              \
+            for (;;) {                                               \
+                do i++; while (a[i] < a[lo]);                        \
+                do j--; while (a[lo] < a[j]);                        \
+                if (j < i) break;                                    \
+                ORC_SWAP(a[i], a[j]);                                \
+            }                                                        \
+            ORC_SWAP(a[lo], a[j]);                                   \
+            if (j <= k) lo = i;                                      \
+            if (j >= k) hi = j - 1;                                  \
         }                                                            \
-        return a[k];                                                 \
     }
+#define ORC_SWAP(x, y) (tmp = (x), (x) = (y), (y) = tmp)
 
 ORC_DEFINE_SELECT(select_f32, float)
 ORC_DEFINE_SELECT(select_i16, int16_t)
@@ -99,7 +114,9 @@ float orc_stdvi16(const int16_t *x, int64_t n) {
     return sqrtf(acc / (float)(int)n);
 }
 
-/* src/stat.h:56-64 + src/ksort.h:233-259: element of rank n/2 (0-based, upper median) */
+/* src/stat.h:56-64 + src/ksort.h:233-259: the element the reference's selection leaves at position n/2 of a copy (of
+ * rank n/2, 0-based, the upper median; which of several equal-comparing elements, or what beside a NaN, is select_f32's
+ * business) */
 float orc_medianf(const float *x, int64_t n) {
     if (n <= 0) return 0.0f;
     float *tmp = (float *)malloc(sizeof(float) * (size_t)n);

@@ -116,6 +116,10 @@ class LongStatus(C.Structure):    # sgk_long_status_t
                 ("n_timeouts", C.c_uint32)]
 
 
+class LiteralStatus(C.Structure):  # sgk_literal_status_t
+    _fields_ = [("n_literal", C.c_uint32), ("n_inexact", C.c_uint32)]
+
+
 def _env_int(name, default=0):
     try:
         return int(os.environ.get(name, default))
@@ -310,7 +314,7 @@ ABI_SYMBOLS = [
     "sgk_pa", "sgk_event_workspace_bytes", "sgk_event", "sgk_event_pa", "sgk_event_status", "sgk_event_plan", "sgk_event_plan_opt", "sgk_job_long_declined", "sgk_inflate", "sgk_deflate", "sgk_deflate_bound", "sgk_deflate_block_bytes", "sgk_job_set_record_frames", "sgk_job_begin_zrec", "sgk_zstd_decompress", "sgk_job_begin_zrec_format", "sgk_zrec_tail_check", "sgk_job_begin_zrec_aux", "sgk_sigraw_unit_samples", "sgk_sigraw_gather", "sgk_job_begin_zrec_signal", "sgk_pipeline", "sgk_stat_lane_rules",
     "sgk_event_workspace_bytes_opt", "sgk_event_opt", "sgk_event_pa_opt", "sgk_event_host_opt",
     "sgk_stat_workspace_bytes", "sgk_stat", "sgk_stat_pa", "sgk_jnn_workspace_bytes", "sgk_jnn",
-    "sgk_prefix_workspace_bytes", "sgk_prefix", "sgk_stat_opt", "sgk_stat_long_status", "sgk_stat_plan", "sgk_stat_pa_opt", "sgk_jnn_opt", "sgk_prefix_opt",
+    "sgk_prefix_workspace_bytes", "sgk_prefix", "sgk_stat_opt", "sgk_stat_long_status", "sgk_stat_literal_status", "sgk_stat_plan", "sgk_stat_pa_opt", "sgk_jnn_opt", "sgk_prefix_opt",
     "sgk_stat_host_opt", "sgk_jnn_host_opt", "sgk_prefix_host_opt", "sgk_job_set_options", "sgk_ent", "sgk_ent_finish", "sgk_svbzd_decode", "sgk_sigtext_decode",
     "sgk_qts", "sgk_svbzd_size", "sgk_svbzd_encode", "sgk_synth_reads", "sgk_synth_reads_host",
     "sgk_profile_enable", "sgk_profile_reset", "sgk_profile_read",
@@ -454,6 +458,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     for f in ("sgk_stat", "sgk_stat_pa", "sgk_jnn", "sgk_prefix"):
         getattr(L, f + "_opt").argtypes = getattr(L, f).argtypes + [OS]
     L.sgk_stat_long_status.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(LongStatus)]
+    L.sgk_stat_literal_status.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(LiteralStatus)]
     L.sgk_stat_plan.argtypes = [C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, OS, C.POINTER(StatPlan)]
     L.sgk_pipeline.argtypes = [C.POINTER(Batch), C.c_int] + [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, OE, OS]
     L.sgk_inflate.argtypes = [C.c_void_p] * 3 + [C.c_uint32] + [C.c_void_p] * 6

@@ -22,11 +22,16 @@ extern "C" {
 // 64 bytes of counters + room for the longest-first dispatch order (a smaller workspace, down to 64 bytes -- none for
 // stat / prefix -- is accepted: the kernels then take the reads in batch order)
 // ... and the records of the batch's long reads (k_long_chains; without that room long reads run on one wavefront)
-static size_t stat_ws(uint32_t n_reads, uint64_t n_samples, uint32_t max_len) {
+// ... and, for stat and prefix, the scratch rows of k_median_literal (without them a median that is a pick among
+// equal-comparing values keeps SGK_MEDIAN_INEXACT in its record)
+static size_t jnn_ws(uint32_t n_reads, uint64_t n_samples, uint32_t max_len) {
     return order_workspace_bytes(n_reads) + long_workspace_bytes(n_samples, max_len);
 }
+static size_t stat_ws(uint32_t n_reads, uint64_t n_samples, uint32_t max_len) {
+    return jnn_ws(n_reads, n_samples, max_len) + literal_workspace_bytes(n_reads, max_len);
+}
 size_t sgk_stat_workspace_bytes(uint32_t n_reads, uint64_t n_samples, uint32_t max_len) { return stat_ws(n_reads, n_samples, max_len); }
-size_t sgk_jnn_workspace_bytes(uint32_t n_reads, uint64_t n_samples, uint32_t max_len) { return stat_ws(n_reads, n_samples, max_len); }
+size_t sgk_jnn_workspace_bytes(uint32_t n_reads, uint64_t n_samples, uint32_t max_len) { return jnn_ws(n_reads, n_samples, max_len); }
 size_t sgk_prefix_workspace_bytes(uint32_t n_reads, uint64_t n_samples, uint32_t max_len) { return stat_ws(n_reads, n_samples, max_len); }
 
 int sgk_stat_opt(const sgk_batch_t *b, sgk_stat_rec_t *out, void *ws, size_t ws_bytes, void *stream,
@@ -41,6 +46,7 @@ int sgk_stat_opt(const sgk_batch_t *b, sgk_stat_rec_t *out, void *ws, size_t ws_
     a.stat = out;
     if ((rc = prepare_order(a, ws, ws_bytes, static_cast<hipStream_t>(stream))) != SGK_OK) return rc;
     if ((rc = prepare_long(a, ws, ws_bytes, opt ? opt->long_min : 0, LC_AUTO_DIV_STAT, static_cast<hipStream_t>(stream))) != SGK_OK) return rc;
+    prepare_literal(a, ws, ws_bytes);
     return launch_stat(a, static_cast<hipStream_t>(stream));
 }
 
@@ -62,6 +68,7 @@ int sgk_stat_pa_opt(const sgk_batch_t *b, sgk_stat_rec_t *out, float *pa_out, vo
     a.pa_out = pa_out;  // written by the first pass of k_stat_wave (lane-per-read kernels: by the median pass)
     if ((rc = prepare_order(a, ws, ws_bytes, static_cast<hipStream_t>(stream))) != SGK_OK) return rc;
     if ((rc = prepare_long(a, ws, ws_bytes, opt ? opt->long_min : 0, LC_AUTO_DIV_STAT, static_cast<hipStream_t>(stream))) != SGK_OK) return rc;
+    prepare_literal(a, ws, ws_bytes);
     return launch_stat(a, static_cast<hipStream_t>(stream));
 }
 
@@ -106,6 +113,7 @@ int sgk_prefix_opt(const sgk_batch_t *b, int rna, int pore, sgk_prefix_rec_t *ou
     a.prefix = out;
     if ((rc = prepare_order(a, ws, ws_bytes, static_cast<hipStream_t>(stream))) != SGK_OK) return rc;
     if ((rc = prepare_long(a, ws, ws_bytes, opt ? opt->long_min : 0, LC_AUTO_DIV_PREFIX, static_cast<hipStream_t>(stream))) != SGK_OK) return rc;
+    prepare_literal(a, ws, ws_bytes);
     return launch_prefix(a, rna, pore, static_cast<hipStream_t>(stream));
 }
 
@@ -121,7 +129,7 @@ int sgk_stat_plan(int tool, uint32_t n_reads, uint64_t n_samples, uint32_t max_r
     const int kernels = opt ? opt->kernels : 0;
     const int32_t lm_opt = opt ? opt->long_min : 0;
     out->kernels = stat_lane_per_read(tool, kernels, n_reads, n_samples, max_read_len) ? 1u : 2u;
-    out->workspace_bytes = stat_ws(n_reads, n_samples, max_read_len);
+    out->workspace_bytes = tool == 1 ? jnn_ws(n_reads, n_samples, max_read_len) : stat_ws(n_reads, n_samples, max_read_len);
     const uint32_t lm = long_threshold(n_samples, lm_opt, tool == 1 ? LC_AUTO_DIV_JNN : (tool == 2 ? LC_AUTO_DIV_PREFIX : LC_AUTO_DIV_STAT));
     // (the long-read path belongs to the wave-per-read kernels and needs a read that long in the batch)
     if (out->kernels == 2u && lm_opt >= 0 && max_read_len >= lm) {
@@ -154,6 +162,18 @@ int sgk_stat_long_status(const void *ws, size_t ws_bytes, uint32_t n_reads, sgk_
     out->n_tiles = h.n_tiles;
     out->n_true_tiles = h.n_true;
     out->n_timeouts = h.n_declined;  // (h.n_timeout: the waits given up -- none when a fault was only injected)
+    return SGK_OK;
+}
+
+int sgk_stat_literal_status(const void *ws, size_t ws_bytes, uint32_t n_reads, sgk_literal_status_t *out) {
+    if (!out) return SGK_ERR_ARG;
+    memset(out, 0, sizeof *out);
+    const size_t off = order_workspace_bytes(n_reads);
+    if (!ws || ws_bytes < off + long_workspace_bytes(0, 0)) return SGK_OK;
+    LongHdr h;
+    SGK_HIP_TRY(hipMemcpy(&h, static_cast<const char *>(ws) + off, sizeof h, hipMemcpyDeviceToHost));
+    out->n_literal = h.n_literal;
+    out->n_inexact = h.n_inexact;
     return SGK_OK;
 }
 
@@ -218,10 +238,10 @@ int sgk_jnn_host_opt(const sgk_host_batch_t *hb, int rna, sgk_segs_host_t *out, 
     if ((rc = d_x.alloc(nslots * 4)) != SGK_OK) return rc;
     if ((rc = d_y.alloc(nslots * 4)) != SGK_OK) return rc;
     if ((rc = d_n.alloc((size_t)nr * 4)) != SGK_OK) return rc;
-    if ((rc = d_ws.alloc(stat_ws(nr, db.view.n_samples, db.view.max_read_len))) != SGK_OK) return rc;
+    if ((rc = d_ws.alloc(jnn_ws(nr, db.view.n_samples, db.view.max_read_len))) != SGK_OK) return rc;
     SGK_HIP_TRY(hipMemcpy(d_slots.p, slots.data(), (nr + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
     rc = sgk_jnn_opt(&db.view, rna, d_slots.as<uint64_t>(), d_x.as<int32_t>(), d_y.as<int32_t>(), d_n.as<uint32_t>(),
-                     d_ws.p, stat_ws(nr, db.view.n_samples, db.view.max_read_len), nullptr, opt);
+                     d_ws.p, jnn_ws(nr, db.view.n_samples, db.view.max_read_len), nullptr, opt);
     if (rc != SGK_OK) return rc;
     SGK_HIP_TRY(hipDeviceSynchronize());
     uint32_t nerr = 0;

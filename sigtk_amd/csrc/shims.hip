@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "host_util.h"
+#include "median_literal.h"
 #include "seqsum.h"
 #include "sgk_common.h"
 #include "stat_args.h"
@@ -87,9 +88,14 @@ __device__ float ss_chain_f32(const float *x, int n, F term) {
     return m == 0.0f ? 0.0f : m * sg;
 }
 
-__global__ __launch_bounds__(256) void k_stat_f32(const float *x, int n, float *out3) {
+// The median: a three-level radix on the floats' bit keys finds the VALUE of rank n / 2.  Where that is a zero (+0 and -0
+// compare equal) or the array holds a NaN (which orders with nothing), the reference's median is the element its own
+// selection leaves at n / 2: redone literally by one lane on `scratch`, a copy of the array (median_literal.h).  An array
+// with a NaN or an infinity in it also gets its mean and deviation redone by that lane, for the sign of their NaN.
+__global__ __launch_bounds__(256) void k_stat_f32(const float *x, int n, float *out3, float *scratch) {
     __shared__ uint32_t hist[2048];
-    __shared__ uint32_t sel_prefix, sel_rank;
+    __shared__ uint32_t sel_prefix, sel_rank, has_nan;
+    if (threadIdx.x == 0) has_nan = 0u;
     if (threadIdx.x < 64) {  // wave 0: the sequential float sums through seqsum.h
         const float s = ss_chain_f32(x, n, [](float v) { return v; });
         const float mn = s / n;
@@ -108,7 +114,9 @@ __global__ __launch_bounds__(256) void k_stat_f32(const float *x, int n, float *
         for (int k = threadIdx.x; k < 2048; k += 256) hist[k] = 0u;
         __syncthreads();
         for (int j = threadIdx.x; j < n; j += 256) {
-            const uint32_t kk = key(x[j]);
+            const float xj = x[j];
+            if (lvl == 0 && !(fabsf(xj) < __builtin_inff())) atomicOr(&has_nan, xj != xj ? 3u : 1u);   // (1: not finite, 2: a NaN)
+            const uint32_t kk = key(xj);
             if ((kk & known) == prefix) atomicAdd(&hist[(kk >> shifts[lvl]) & ((1u << bitsn[lvl]) - 1u)], 1u);
         }
         __syncthreads();
@@ -131,11 +139,19 @@ __global__ __launch_bounds__(256) void k_stat_f32(const float *x, int n, float *
     if (threadIdx.x == 0) {
         const uint32_t u = (prefix & 0x80000000u) ? (prefix & 0x7fffffffu) : ~prefix;
         out3[2] = __uint_as_float(u);
+        sel_rank = (__uint_as_float(u) == 0.0f || (has_nan & 2u)) ? 1u : 0u;
+        if (has_nan) x86_mean_std((int64_t)n, [&](int64_t i) { return x[i]; }, out3[0], out3[1]);
+    }
+    __syncthreads();
+    if (sel_rank) {  // (workgroup-uniform)
+        for (int j = threadIdx.x; j < n; j += 256) scratch[j] = x[j];
+        __syncthreads();
+        if (threadIdx.x == 0) out3[2] = literal_select(scratch, (int64_t)n, (int64_t)(n / 2), [](float p, float q) { return p < q; });
     }
 }
 
-static int launch_stat_f32(const float *x, int n, float *out3, hipStream_t st) {
-    SGK_LAUNCH("k_stat_f32", k_stat_f32, 1, 256, st, x, n, out3);
+static int launch_stat_f32(const float *x, int n, float *out3, float *scratch, hipStream_t st) {
+    SGK_LAUNCH("k_stat_f32", k_stat_f32, 1, 256, st, x, n, out3, scratch);
     return SGK_OK;
 }
 
@@ -198,12 +214,13 @@ int stat_i16(const int16_t *x, int n, sgk_stat_rec_t *rec) {
 int stat_f32(const float *x, int n, float *out3) {
     if (!x || n <= 0) return SGK_ERR_ARG;
     if (sgk_device_count() <= 0) return SGK_ERR_NODEVICE;
-    DevBuf d_x, d_o;
+    DevBuf d_x, d_o, d_s;
     int rc;
     if ((rc = d_x.alloc((size_t)n * sizeof(float))) != SGK_OK) return rc;
     if ((rc = d_o.alloc(3 * sizeof(float))) != SGK_OK) return rc;
+    if ((rc = d_s.alloc((size_t)n * sizeof(float))) != SGK_OK) return rc;
     SGK_HIP_TRY(hipMemcpy(d_x.p, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-    if ((rc = launch_stat_f32(d_x.as<float>(), n, d_o.as<float>(), nullptr)) != SGK_OK) return rc;
+    if ((rc = launch_stat_f32(d_x.as<float>(), n, d_o.as<float>(), d_s.as<float>(), nullptr)) != SGK_OK) return rc;
     SGK_HIP_TRY(hipDeviceSynchronize());
     SGK_HIP_TRY(hipMemcpy(out3, d_o.p, 3 * sizeof(float), hipMemcpyDeviceToHost));
     return SGK_OK;

@@ -31,6 +31,10 @@ struct StatArgs {
     uint32_t long_redo;          // wave kernels: 1 = this launch only takes the long reads k_long_chains DECLINED (a barrier
                                  // of theirs timed out): wave i looks at long_list[i], everything else returns at once
     uint32_t long_fault;         // sgk_stat_options_t::debug_fault (tests): see lc_barrier
+    // medians redone with the reference's own selection (k_median_literal): null / 0 when the workspace has no room
+    struct LongHdr *lit_hdr;     // its two counters live in the long reads' header, which every call clears
+    int16_t *lit_scratch;        // lit_blocks x lit_stride samples, one row per workgroup
+    uint32_t lit_stride, lit_blocks;
 };
 constexpr uint32_t JNN_REDO_MARK = 0xffffffffu;
 
@@ -49,7 +53,9 @@ struct LongHdr {
     uint32_t n_timeout;  // barrier waits given up after seconds (never, on a GPU that dispatches a grid's workgroups in
                          // order): the read is DECLINED -- nothing of it is written -- and redone on one wavefront
     uint32_t n_declined; // reads declined that way (counted by the redo launch that takes them)
-    uint32_t pad[10];
+    uint32_t n_literal;  // k_median_literal: medians redone with the reference's selection ...
+    uint32_t n_inexact;  // ... and medians it had no scratch for (the record keeps SGK_MEDIAN_INEXACT)
+    uint32_t pad[8];
 };
 struct LongSums {
     uint32_t read;
@@ -184,6 +190,12 @@ int launch_k_adaptor_wave(const char *name, uint32_t grid, hipStream_t st, const
 // stat_long.hip -- k_long_chains<kind>, LC_PARTS workgroups per long read the batch can hold
 enum { LC_STAT = 0, LC_JNN = 1, LC_ADAPT = 2 };
 int launch_k_long_chains(const char *name, int kind, hipStream_t st, const StatArgs &a, const JnnP &p, const AdaptP &ap);
+// stat_literal.hip -- k_median_literal: min(n_reads, LIT_BLOCKS) workgroups, each with a scratch row for the batch's
+// longest read behind the long reads' part of the workspace
+constexpr uint32_t LIT_BLOCKS = 1024;
+size_t literal_workspace_bytes(uint32_t n_reads, uint32_t max_read_len);
+void prepare_literal(StatArgs &a, void *ws, size_t ws_bytes);   // fills a.lit_*; call it behind prepare_long
+int launch_k_median_literal(const char *name, int region, hipStream_t st, const StatArgs &a);
 
 
 }  // namespace sgk

@@ -10,11 +10,15 @@
 //       - round 1 (SGK_LANE_PER_READ=1, and find_polya on large uniform batches): one read per LANE, serial float
 //         chain, the 64 reads of a wave streamed through the LDS row stager (row_stream.h): k_moments, k_jnn, k_adaptor,
 //         k_polya.  Kept as the independent second implementation the tests compare against, bit for bit.
-//   * medians are order statistics (rank n/2, src/stat.h:56-73 + ksort.h:233-259): any exact selection works -> a
-//     histogram with one bin per raw value over a window centred on the read's mean (k_stat_wave: 2048 bins per wave,
-//     fused into its second pass; k_median: 8192 bins per 256-thread workgroup), a two-level radix select for regions
-//     and for reads whose order statistic falls outside the window; pA median = pA(raw order statistic) because the
-//     int16 -> pA map is monotone (non-increasing when range/digitisation < 0).
+//   * medians are order statistics (rank n/2, src/stat.h:56-73 + ksort.h:233-259).  For the int16 median any exact
+//     selection works -> a histogram with one bin per raw value over a window centred on the read's mean (k_stat_wave:
+//     2048 bins per wave, fused into its second pass; k_median: 8192 bins per 256-thread workgroup), a two-level radix
+//     select for regions and for reads whose order statistic falls outside the window.  The pA median is
+//     pA(raw order statistic) because the int16 -> pA map is monotone (non-increasing when range/digitisation < 0) --
+//     EXCEPT where pA values compare equal without being the same bits (+0 / -0: a unit of 0, products that underflow)
+//     or do not order (NaN: a unit or offset that is not finite): there it is the element the reference's own
+//     exchanges leave at n/2.  Such a median is a zero or comes with a non-finite scale; k_median_literal
+//     (stat_literal.hip, median_literal.h) finds those records behind the other kernels and redoes them literally.
 //   * jnn_core (src/jnn.c:190-278) and jnnv2 (src/jnn.c:99-179) are serial automata with thresholds derived from those
 //     sequential float moments.  Their per-sample work is integer: in / out-of-range flags of the raw samples, integer
 //     rolling totals with the exact constant division (tstat_math.h) and integer thresholds for jnnv2's run finder.
@@ -27,6 +31,7 @@
 //   stat_wave.hip   one read per WAVE on seqsum.h: k_stat_wave, k_jnn_wave, k_polya_wave, k_adaptor_wave, and the sort
 //                   that hands them the reads longest first (k_order_*).
 //   stat_long.hip   a long read on 64 waves: k_long_list, k_long_limit, k_long_chains and the long reads' workspace.
+//   stat_literal.hip  k_median_literal, behind all three.
 //   stat_wave.h     the wave-per-read building blocks, shared by stat_wave.hip and stat_long.hip (never by the lanes).
 //   stat_device.h   (this file) what all three share: regions, the long reads' hand-over, the clamps and the automata
 //                   and thresholds of the reference that both implementations must state the same way.  k_jnn_f32 of
@@ -125,6 +130,8 @@ __device__ __forceinline__ s16x2 clamp_raw2(uint32_t w) {
 
 // (sgk_stat_rec_t::reserved / sgk_prefix_rec_t::reserved between kernels: reads whose median is still to be found)
 constexpr uint32_t FLAG_MEDIAN_WHOLE = 1u, FLAG_MEDIAN_ADAPT = 1u, FLAG_MEDIAN_POLYA = 2u;
+// (what a record KEEPS: a pA median that is a pick among equal-comparing values and could not be redone, median_literal.h)
+constexpr uint32_t FLAG_MEDIAN_INEXACT = SGK_MEDIAN_INEXACT, FLAG_MEDIAN_INEXACT_POLYA = SGK_MEDIAN_INEXACT_POLYA;
 
 // ---------------------------------------------------------------- jnn_core automaton (src/jnn.c:190-278)
 struct JnnAuto {

@@ -96,9 +96,16 @@ static int launch_beside_long(int kind, const StatArgs &a, const JnnP &p, const 
     return wave_launch(st, redo, LC_CAP / 4);
 }
 
+static int launch_stat_medians(const StatArgs &a, hipStream_t st);
+// ... and behind whichever implementation ran, the pA medians that are a pick among equal-comparing values (a zero, a
+// scale that is not finite) are redone with the reference's own selection (stat_literal.hip): one look per record
 int launch_stat(const StatArgs &a, hipStream_t st) {
+    if (a.b.n_reads == 0) return SGK_OK;
+    const int rc = launch_stat_medians(a, st);
+    return rc != SGK_OK ? rc : launch_k_median_literal("k_median_literal", REG_WHOLE, st, a);
+}
+static int launch_stat_medians(const StatArgs &a, hipStream_t st) {
     const uint32_t nr = a.b.n_reads;
-    if (nr == 0) return SGK_OK;
     int rc;
     if (lane_per_read(a.pa_out ? 3 : 0, a)) {
         if (a.pa_out) {
@@ -158,6 +165,7 @@ static int launch_region_stats(int region, const StatArgs &a, bool lanes, bool l
     static constexpr Names NAMES[2] = {
         {"k_moments_median_adapt", "k_median_adapt_flagged", "k_moments_adapt", "k_median_adapt", "k_stat_wave_adapt"},
         {"k_moments_median_polya", "k_median_polya_flagged", "k_moments_polya", "k_median_polya", "k_stat_wave_polya"}};
+    static constexpr const char *LITERAL[2] = {"k_median_literal_adapt", "k_median_literal_polya"};
     if (region != REG_ADAPT && region != REG_POLYA) return SGK_ERR_ARG;  // a prefix region
     const Names &n = NAMES[region == REG_POLYA];
     int rc;
@@ -171,6 +179,7 @@ static int launch_region_stats(int region, const StatArgs &a, bool lanes, bool l
         rc = launch_k_stat_wave(n.stat_wave, region, false, (a.b.n_reads + 3) / 4, st, a);
         if (rc == SGK_OK) rc = launch_k_median(n.median_flagged, region, false, true, st, a);
     }
+    if (rc == SGK_OK) rc = launch_k_median_literal(LITERAL[region == REG_POLYA], region, st, a);  // (see launch_stat)
     return rc;
 }
 

@@ -223,6 +223,15 @@ def long_status(b: "DeviceReads", tool: str = "stat", ws: Optional[torch.Tensor]
     return st
 
 
+def literal_status(b: "DeviceReads", tool: str = "stat") -> "api.LiteralStatus":
+    """sgk_stat_literal_status of the workspace the last stat / prefix call on this batch used; synchronises"""
+    ws = _workspace(b, "sgk_%s_workspace_bytes" % tool)
+    torch.cuda.synchronize()
+    st = api.LiteralStatus()
+    api.check(api.load_library().sgk_stat_literal_status(_ptr(ws), ws.numel(), b.n_reads, C.byref(st)), "sgk_stat_literal_status")
+    return st
+
+
 def stat(b: DeviceReads) -> torch.Tensor:
     """sgk_stat -> uint8 tensor holding n_reads sgk_stat_rec_t (view it with api.STAT_DTYPE)."""
     L = api.load_library()

@@ -11,6 +11,7 @@ import hashlib
 import json
 import os
 import sys
+import zlib
 
 import numpy as np
 import pytest
@@ -22,6 +23,7 @@ if ROOT not in sys.path:
 from sigtk_amd import api  # noqa: E402
 import event_cases  # noqa: E402
 import jnn_cases  # noqa: E402
+import median_cases  # noqa: E402
 import prefix_cases  # noqa: E402  (tests/ is on the path: conftest.py lies there)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -163,12 +165,91 @@ def observe_event_catalogue(lib):
     return out
 
 
+def _nbits(x):
+    """float32 bits; every NaN as its sign bit + the quiet pattern: two NaNs are equal iff their sign bits are"""
+    b = int(np.float32(x).view(np.uint32))
+    return (b & 0x80000000) | 0x7fc00000 if (b & 0x7fffffff) > 0x7f800000 else b
+
+
+def _median_arrays(seed, count):
+    """seeded arrays for the selection: floats with +-0, NaNs of both signs, duplicates, all-equal, sorted, reversed,
+    and int16 reads under ordinary, negative and tie-class scales"""
+    rs = np.random.RandomState(seed)
+    nan_p, nan_n = np.uint32(0x7fc00000).view(np.float32), np.uint32(0xffc00000).view(np.float32)
+    for i in range(count):
+        n = int(rs.randint(1, 120)) if i % 16 else int(rs.randint(120, 3000))
+        kind = i % 8
+        if kind < 5:
+            x = rs.normal(0, 1, size=n).astype(np.float32) if kind != 1 else rs.randint(-3, 4, size=n).astype(np.float32)
+            if kind == 2:
+                x[:] = x[0]
+            if kind == 3:
+                x = np.sort(x) if i % 16 < 8 else np.sort(x)[::-1].copy()
+            for v, p in ((0.0, 0.5), (-0.0, 0.5), (nan_p, 0.3), (nan_n, 0.3), (np.inf, 0.1), (-np.inf, 0.1)):
+                if rs.rand() < p:
+                    x[rs.randint(0, n, size=rs.randint(1, 4))] = v
+            yield "f", x
+        else:
+            raw = rs.randint(-20, 20, size=n).astype(np.int16) if kind < 7 else rs.randint(-32768, 32768, size=n).astype(np.int16)
+            if i % 24 == 5:
+                raw[:] = raw[0]
+            if i % 24 == 13:
+                raw = np.sort(raw) if i % 48 < 24 else np.sort(raw)[::-1].copy()
+            nm, dig, rng = median_cases.TIE_SCALES[i % 6] if kind == 5 else ("", 8192.0, (1402.882324, -1402.882324)[i % 2])
+            yield "i", (raw, dig, float(rs.randint(-10, 10)), rng)
+
+
+def observe_median_arrays(lib, seed):
+    """the selection on 2 600 seeded arrays (x 4 seeds: 10 400): medianf with the other two float statistics, stat's raw
+    and pA medians; one hash per 650 arrays, NaNs by their sign"""
+    out = {}
+    acc = []
+    with np.errstate(all="ignore"):
+        for i, (kind, v) in enumerate(_median_arrays(seed, 2600)):
+            if kind == "f":
+                acc += [_nbits(t) for t in lib.statf(v)]
+            else:
+                s = lib.stat(*v)
+                acc += [int(s[4]) & 0xffffffff] + [_nbits(s[k]) for k in (0, 1, 2, 3, 5)]
+            if i % 650 == 649:
+                out["%04d" % (i - 649)] = hashlib.sha256(np.array(acc, dtype=np.uint32).tobytes()).hexdigest()
+                acc = []
+    return out
+
+
+def observe_median_catalogue(lib):
+    """tests/median_cases.py: stat on every read, statf on every float array, and the region medians of prefix as
+    cfunc.c forms them, NaNs by their sign; one hash per family of cases (the values themselves are in
+    tests/golden/median_cases.json, which test_median_cases_cpu.py holds the oracle against case by case)"""
+    out = {}
+    with np.errstate(all="ignore"):
+        for k in median_cases.cases():
+            s = lib.stat(k.raw, k.dig, k.off, k.rng)
+            out[k.name] = [int(s[4])] + [_nbits(s[i]) for i in (0, 1, 2, 3, 5)]
+        for k in median_cases.float_cases():
+            out["f:" + k.name] = [_nbits(t) for t in lib.statf(k.x)]
+        for k in median_cases.region_cases():
+            pa = lib.pa(k.raw, k.dig, k.off, k.rng)
+            ax, ay = lib.find_adaptor(k.raw, median_cases.REGION_PORE)
+            st = lib.statf(pa[ax:ay])
+            mid = np.float32(st[0]) + np.float32(30)
+            px, py = lib.find_polya(pa[ay:], mid + np.float32(20), mid - np.float32(20), median_cases.REGION_PORE)
+            out["r:" + k.name] = [ax, ay, px, py] + [_nbits(t) for t in st] + \
+                ([_nbits(t) for t in lib.statf(pa[ay + px:ay + py])] if py > 0 else [])
+    fam = {}
+    for name in sorted(out):
+        fam.setdefault(name.split("_")[0], []).extend([zlib.crc32(name.encode())] + [int(v) & 0xffffffff for v in out[name]])
+    return {k: hashlib.sha256(np.array(v, dtype=np.uint32).tobytes()).hexdigest() for k, v in fam.items()}
+
+
 OBSERVATIONS = {"pa_event_stat_seed%d" % s: (observe_pa_event_stat, (s,)) for s in (1, 2, 3)}
 OBSERVATIONS.update({"jnn_adaptor_polya_seed%d" % s: (observe_jnn_adaptor_polya, (s,)) for s in (4, 5)})
 OBSERVATIONS["soak_fixtures"] = (observe_soak_fixtures, ())
 OBSERVATIONS["prefix_catalogue"] = (observe_prefix_catalogue, ())
 OBSERVATIONS["jnn_catalogue"] = (observe_jnn_catalogue, ())
 OBSERVATIONS["event_catalogue"] = (observe_event_catalogue, ())
+OBSERVATIONS.update({"median_arrays_seed%d" % s: (observe_median_arrays, (s,)) for s in (11, 12, 13, 14)})
+OBSERVATIONS["median_catalogue"] = (observe_median_catalogue, ())
 
 
 def _check(name, oracle, reflib):
@@ -214,6 +295,19 @@ def test_event_catalogue(oracle, reflib):
     """every branch of the peak detector, the boundaries of its long detector among them (tests/event_cases.py): the oracle
     the GPU tests compare against equals the real reference on every read of the catalogue the reference can take"""
     _check("event_catalogue", oracle, reflib)
+
+
+@pytest.mark.parametrize("seed", [11, 12, 13, 14])
+def test_selection_on_seeded_arrays(oracle, reflib, seed):
+    """10 400 seeded arrays in all: the oracle's selection leaves the element at n / 2 that the reference's leaves there,
+    bit for bit (a NaN: the same sign), with +-0, NaNs, duplicates, constant, sorted and reversed arrays, and int16 reads
+    under the tie-class scales"""
+    _check("median_arrays_seed%d" % seed, oracle, reflib)
+
+
+def test_median_catalogue(oracle, reflib):
+    """every read and float array of tests/median_cases.py, and the region medians of its prefix reads"""
+    _check("median_catalogue", oracle, reflib)
 
 
 if __name__ == "__main__":
