@@ -55,6 +55,16 @@ static_assert(LzCfg<3>::NP >= 8 && LzCfg<7>::NP >= 16, "prefix ring holds P(i) .
 #define SGK_EVENT_BOOK 1
 #endif
 
+// How the fast pass of k_event<3, *> (the leading-edge form with the mask history: LEAD and BOOK) keeps the emission's
+// bookkeeping, as bits (tools/build_variant.sh <tag> -DSGK_EVENT_EMIT=<bits>; 0: a bit selected and ORed into the bitmap
+// word and two rare tests per index); profiles/event_emission.md has the listings and what each part showed.
+//   1  the bitmap word is built in REVERSED order, bw = bw + bw + carry(em): the emission mask is the carry-in of one
+//      v_addc_co_u32 per index, and the word is bit-reversed once per 32 positions where it leaves for the ring
+//   2  one test per index, (rare emission | recorded run) != 0, marked unlikely, with both rare blocks behind it
+#ifndef SGK_EVENT_EMIT
+#define SGK_EVENT_EMIT 3
+#endif
+
 constexpr int LZ_NONE = -(1 << 29);   // "no mask" / far in the past (block-relative positions drift by -16 per block)
 constexpr int LZ_NREC = 8;            // hot long-detector runs a lane can record per pass (more: read -> exact fallback)
 constexpr int LZ_RING_WORDS = 16;     // per-lane bitmap ring: 512 positions
@@ -251,6 +261,12 @@ typedef unsigned long long lmask_t;  // one bit per lane: lives in a scalar regi
 // mask -> per-lane predicate without vector work: selects become v_cndmask with the mask as its condition operand,
 // branches become s_and_saveexec
 __device__ __forceinline__ bool lane_of(lmask_t m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+// w + w + (the lane's bit of c): a lane mask shifted into a word as the carry-in of one add (the carry-out is dropped)
+__device__ __forceinline__ uint32_t shift_in(uint32_t w, lmask_t c) {
+    lmask_t co;
+    asm("v_addc_co_u32_e64 %0, %1, %0, %0, %2" : "+v"(w), "=s"(co) : "s"(c));
+    return w;
+}
 
 // State of one fast pass.  Every ring access uses a compile-time index (U is a template parameter and the pass
 // starts on a multiple of the unroll length), so the rings live in registers; the 16 steps of one loop iteration
@@ -279,6 +295,8 @@ struct LazyPass {
     static_assert(NA2 > (LEAD ? 2 : 1) * W1 && (!LEAD || NS > W1) && R % NA2 == 0, "ring depths");
     // BOOK: the long detector's mask as a history of lane masks, its run start as one register (see moff / rs)
     static constexpr bool BOOK = ((SGK_EVENT_BOOK) & (FLAGGED ? 4 : (LEAD ? 1 : 2))) != 0;
+    // EMIT: SGK_EVENT_EMIT, for the one pass it is written for
+    static constexpr int EMIT = (LEAD && BOOK && W1 == 3) ? (SGK_EVENT_EMIT) : 0;
     static constexpr int NM = W1 - H1;   // an emission masks the long detector at its own index and at the NM - 1 behind it
     // rings
     double Ps[NP], Pq[NP];        // running prefix sums of x and of fl(x*x); slot of P(k) = k mod NP
@@ -295,6 +313,8 @@ struct LazyPass {
     lmask_t inpk, val, strong;
     lmask_t hist[H1 + 1];           // hist[k]: lanes whose peak_pos was set k+1 indices ago
     uint32_t bw;                  // bitmap word (32 positions) that holds position j - H1 - 1, the usual emitted peak
+                                  // (EMIT & 1: the emissions of the last 32 indices, the latest in bit 0 -- the word of
+                                  // the span in reversed order, right-aligned)
     // lazy long detector
     int lm, r0;                   // short peak position at the last reset (masked while i <= lm + W1); last reset
     // BOOK, instead of lm and r0.  An emission is the last reset of its peak and masks the long detector up to
@@ -440,6 +460,7 @@ struct LazyPass {
         lmask_t off = 0ull, nx[NM - 1];
         if (SLOW && oldpeak) {
             // some lane holds a peak older than the bitmap ring reaches (or one from before the pass)
+            if constexpr ((EMIT & 1) != 0) bw += bw;   // (the position belongs to u: every step shifts; these bits go to the ring)
             if (lane_of(em)) {
                 lz_emit_slow(ring, bm, flushed, i_begin, s, e, jb + sp, jb + u);
                 if constexpr (BOOK) {
@@ -457,7 +478,8 @@ struct LazyPass {
             }
         } else {
             if constexpr (BOOK) {
-                if (lane_of(em)) bw |= bit;
+                if constexpr ((EMIT & 1) != 0) bw = shift_in(bw, em);
+                else if (lane_of(em)) bw |= bit;
                 rs = lane_of(em) ? u + NM : rs;
                 const lmask_t eusual = em & hist[H1];
                 off = moff[0] | eusual;
@@ -471,16 +493,16 @@ struct LazyPass {
                 }
             }
             const lmask_t erare = em & ~hist[H1];
-            if (erare != 0ull) {
-                if (lane_of(erare)) {  // an older peak: undo the bit, set the right one (its word is in the ring)
-                    bw &= ~bit;
-                    const int p = jb + sp, own = s - i_begin;
-                    if (p >= own) atomicOr(&ring[(p >> 5) & (LZ_RING_WORDS - 1)], 1u << (p & 31));
-                    else if (jb >= own) ring[LZ_PRE] = (uint32_t)(i_begin + p);  // inherited, see lz_emit_slow
-                    if constexpr (BOOK) rs = max(u, sp + W1 + 1);
+            if constexpr ((EMIT & 2) != 0) {
+                // both rare blocks behind one test that the usual step falls through (the emission's rs first: the
+                // recorded run reads it)
+                const lmask_t rec = dom & hot;
+                if (__builtin_expect((erare | rec) != 0ull, 0)) {
+                    if (erare != 0ull) emit_rare(erare, u, bit, off, nx);
+                    if (rec != 0ull) record_run(rec, u);
                 }
-                // (sp <= u - H1 - 2: masked up to index u + NM - 2 at the most)
-                if constexpr (BOOK) book_mask_from_sp<NM - 2>(erare, u, off, nx);
+            } else {
+                if (erare != 0ull) emit_rare(erare, u, bit, off, nx);
             }
         }
         sv = lane_of(upd) ? v : sv;
@@ -499,9 +521,9 @@ struct LazyPass {
         }
         // lazy long detector: the run that ends at this reset is recorded if it was hot; a new run starts at the
         // peak's last reset (its emission); resets in between leave nothing behind
-        const lmask_t rec = dom & hot;
-        if (rec != 0ull) {
-            if (lane_of(rec)) nrec = lz_record(runs, nrec, ib + run_start(), ib + u, s, e, n);
+        if ((EMIT & 2) == 0 || (SLOW && oldpeak)) {
+            const lmask_t rec = dom & hot;
+            if (rec != 0ull) record_run(rec, u);
         }
         lmask_t on;
         if constexpr (BOOK) {
@@ -517,6 +539,23 @@ struct LazyPass {
         }
         if constexpr (SLOW) on &= live;
         hot = (hot & ~dom) | (on & hck & (~dom | em));
+    }
+    // the rare emission (lanes `erare`): an older peak.  Undo the usual bit, set the right one (its word is in the ring)
+    __device__ __forceinline__ void emit_rare(const lmask_t erare, const int u, const uint32_t bit, lmask_t &off,
+                                              lmask_t (&nx)[NM - 1]) {
+        if (lane_of(erare)) {
+            if constexpr ((EMIT & 1) != 0) bw &= ~1u;
+            else bw &= ~bit;
+            const int p = jb + sp, own = s - i_begin;
+            if (p >= own) atomicOr(&ring[(p >> 5) & (LZ_RING_WORDS - 1)], 1u << (p & 31));
+            else if (jb >= own) ring[LZ_PRE] = (uint32_t)(i_begin + p);  // inherited, see lz_emit_slow
+            if constexpr (BOOK) rs = max(u, sp + W1 + 1);
+        }
+        // (sp <= u - H1 - 2: masked up to index u + NM - 2 at the most)
+        if constexpr (BOOK) book_mask_from_sp<NM - 2>(erare, u, off, nx);
+    }
+    __device__ __forceinline__ void record_run(const lmask_t rec, const int u) {
+        if (lane_of(rec)) nrec = lz_record(runs, nrec, ib + run_start(), ib + u, s, e, n);
     }
     // first index (block-relative) of the long detector's current run: behind its last reset and behind the mask
     __device__ __forceinline__ int run_start() const {
@@ -534,6 +573,13 @@ struct LazyPass {
     // the bitmap word moves on when position j - H1 - 1 enters the next 32-position span
     __device__ __forceinline__ void bw_advance() {
         const int p = jb - 1;  // last position of the span that is complete (jb is a multiple of 32 here)
+        if constexpr ((EMIT & 1) != 0) {
+            // the ring keeps the natural bit order.  (bw need not be zeroed, the span's 32 shifts push every older bit
+            // out; it is, one v_mov per 32 indices: with the word live across the flush k_event<3, float> spills a VGPR)
+            atomicOr(&ring[(p >> 5) & (LZ_RING_WORDS - 1)], __builtin_bitreverse32(bw));
+            bw = 0u;
+            return;
+        }
         atomicOr(&ring[(p >> 5) & (LZ_RING_WORDS - 1)], bw);
         bw = 0u;
     }
@@ -902,7 +948,14 @@ __device__ __forceinline__ void pass_lazy(const ReadCtx<T> &rc, bool given, int 
     // remaining ring words (the current bitmap word first)
     {
         const int p = jb - LP::H1 - 2 < 0 ? 0 : jb - LP::H1 - 2;  // a position inside the word bw stands for
-        atomicOr(&f.ring[(p >> 5) & (LZ_RING_WORDS - 1)], f.bw);
+        uint32_t w = f.bw;
+        if constexpr ((LP::EMIT & 1) != 0) {
+            // the word has seen m < 32 shifts since its span began (14 or 30: jb is a multiple of 16); its first position
+            // sits in bit m - 1.  Reversed, the span's positions are the top m bits.
+            const int m = (jb - LP::H1 - 1) & 31;
+            w = __builtin_bitreverse32(w) >> (32 - m);
+        }
+        atomicOr(&f.ring[(p >> 5) & (LZ_RING_WORDS - 1)], w);
     }
     for (int p0 = f.flushed; p0 < jb; p0 += 256) lz_flush(f.ring, f.bm, i_begin, p0, own_lo, own_hi);
     if (active) L->nrec[l] = f.nrec;

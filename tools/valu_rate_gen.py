@@ -142,6 +142,18 @@ T("v_addc_co_u32_vcc", "v_addc_co_u32 {d}, vcc, {d}, {d}, vcc")
 T("v_addc_co_u32_e64_sgpr", "v_addc_co_u32_e64 {d}, s[20:21], {d}, {d}, s[22:23]")
 tests.append(("v_addc_co_u32_e64_salu_1to1", "".join("v_addc_co_u32_e64 %%%d, s[20:21], %%%d, %%%d, s[22:23]\\n s_and_b64 s[24:25], s[26:27], s[26:27]\\n " % (i, i, i) for i in range(4)), 4))
 
+# ---- a rare test beside the vector stream (profiles/event_emission.md): one s_cmp + s_cbranch_scc1 per vector instruction,
+# the branch TAKEN over a block the compiler left inline (two instructions that never run) against the branch that FALLS
+# THROUGH (the block moved away), and the compare alone; beside slow-class (v_cndmask) and fast-class (v_add_f32) work.
+# (s[26:27] compared with itself: equal whatever it holds.)
+BR_VALU = {"slow": "v_cndmask_b32 %{i}, %{i}, %16, s[22:23]", "fast": "v_add_f32 %{i}, %{i}, %16"}
+BR_TAIL = {"taken": "s_cmp_eq_u64 s[26:27], s[26:27]\\n s_cbranch_scc1 1f\\n v_mov_b32 %7, %16\\n v_mov_b32 %7, %16\\n 1:\\n ",
+           "fallthrough": "s_cmp_lg_u64 s[26:27], s[26:27]\\n s_cbranch_scc1 1f\\n 1:\\n ",
+           "cmp_only": "s_cmp_lg_u64 s[26:27], s[26:27]\\n "}
+for cls in ("slow", "fast"):
+    for kind in ("taken", "fallthrough", "cmp_only"):
+        tests.append(("branch_%s_%s" % (kind, cls), "".join(BR_VALU[cls].format(i=i) + "\\n " + BR_TAIL[kind] for i in range(4)), 4))
+
 out = []
 for name, body, valu in tests:
     out.append('DEFINE_KERNEL(%s, "%s")' % (name, body))
