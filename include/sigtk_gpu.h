@@ -255,9 +255,23 @@ int sgk_event_status(const void *workspace, sgk_event_status_t *out, void *strea
  *   detector emits as soon as i - pos > 1, which can be the index at which a short peak opens -- two peaks 2 apart.
  *   A slot range smaller than a read's events behaves as in sgk_event: the surplus is dropped, n_events[r] holds the
  *   true count and sgk_event_status returns SGK_ERR_CAPACITY.
- *   Routing: parameters that equal a preset bit for bit, without SGK_EVENT_PARAMS_GENERIC, take sgk_event_opt's kernels
- *   through sgk_event_opt's launch (same results, same time, same status fields, workspace as sgk_event_workspace_bytes_opt).
- *   Everything else takes the generic kernel k_event_param: one wavefront per read of any length, reads dispatched
+ *   Routing (sgk_event_params_route is the one decision every entry point uses):
+ *     SGK_EVENT_ROUTE_PRESET          parameters that equal a preset bit for bit, without SGK_EVENT_PARAMS_GENERIC, whatever
+ *                                     else flags holds: sgk_event_opt's kernels through sgk_event_opt's launch (same results,
+ *                                     same time, same status fields, workspace as sgk_event_workspace_bytes_opt).
+ *     SGK_EVENT_ROUTE_PRESET_WINDOWS  opt-in by SGK_EVENT_PARAMS_PRESET_KERNELS, without SGK_EVENT_PARAMS_GENERIC: windows
+ *                                     3 / 6 or 7 / 14 and threshold2 >= 9.0f, any threshold1 and peak_height of the domain.
+ *                                     The presets' kernels compiled with the three thresholds as run-time arguments, planned
+ *                                     and launched like sgk_event_opt with rna = (window_length1 == 7): every field of `opt`
+ *                                     applies, the status is filled as for sgk_event_opt, the workspace is
+ *                                     sgk_event_workspace_bytes_opt's (and, as there, a smaller one is accepted while
+ *                                     the scratch of at least one fallback workgroup fits).  Why 9: the fast kernels
+ *                                     skip the long detector wherever they prove its statistic <= 9, which is then not
+ *                                     > threshold2 either; where the proof fails the long detector is replayed exactly
+ *                                     with the caller's threshold2 and peak_height (DESIGN.md 3.16 goes through every
+ *                                     site and lists the kernels' registers, spills, scratch and LDS).
+ *     SGK_EVENT_ROUTE_GENERIC         everything else, and everything with SGK_EVENT_PARAMS_GENERIC (both flags: generic).
+ *   The generic route takes the kernel k_event_param: one wavefront per read of any length, reads dispatched
  *   longest first; of `opt` only `warmup` applies there (results do not depend on it); of the status it fills
  *   n_rerun_passes, n_capacity_overflow and n_events_total, the rest are zero.
  *   Workspace of the generic kernel: 64 + 4 n_reads + 512 bytes (rounded up to 64) + B x S, where
@@ -267,6 +281,11 @@ int sgk_event_status(const void *workspace, sgk_event_status_t *out, void *strea
  *   workspace gives SGK_ERR_WORKSPACE and nothing is written. */
 #define SGK_EVENT_W_MAX 64
 #define SGK_EVENT_PARAMS_GENERIC 1u /* flags: take the generic kernel even for a preset (tests, measurements) */
+#define SGK_EVENT_PARAMS_PRESET_KERNELS 4u /* flags: the presets' kernels with run-time thresholds where the domain allows
+                                             (bit 2u is not assigned: like every unknown bit it is SGK_ERR_ARG) */
+#define SGK_EVENT_ROUTE_PRESET 0
+#define SGK_EVENT_ROUTE_PRESET_WINDOWS 1
+#define SGK_EVENT_ROUTE_GENERIC 2
 typedef struct sgk_event_params {
     uint32_t window_length1, window_length2;
     float threshold1, threshold2, peak_height;
@@ -276,6 +295,8 @@ typedef struct sgk_event_params {
 int sgk_event_params_preset(int rna, sgk_event_params_t *out);
 /* host only: SGK_OK when `p` lies in the domain above, else SGK_ERR_ARG */
 int sgk_event_params_check(const sgk_event_params_t *p);
+/* host only: the route these parameters take, SGK_EVENT_ROUTE_*; SGK_ERR_ARG when sgk_event_params_check refuses them */
+int sgk_event_params_route(const sgk_event_params_t *p);
 size_t sgk_event_workspace_bytes_param(uint32_t n_reads, uint64_t n_samples, uint32_t max_read_len,
                                        const sgk_event_options_t *opt, const sgk_event_params_t *p);
 int sgk_event_param(const sgk_batch_t *batch, const sgk_event_params_t *p, const uint64_t *ev_slots,

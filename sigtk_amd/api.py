@@ -65,6 +65,11 @@ class EventOptions(C.Structure):   # sgk_event_options_t (all zero = the default
 
 SGK_EVENT_W_MAX = 64
 SGK_EVENT_PARAMS_GENERIC = 1
+#: opt-in: the presets' kernels with run-time thresholds for windows 3/6 and 7/14 with threshold2 >= 9
+SGK_EVENT_PARAMS_PRESET_KERNELS = 4
+SGK_EVENT_ROUTE_PRESET = 0
+SGK_EVENT_ROUTE_PRESET_WINDOWS = 1
+SGK_EVENT_ROUTE_GENERIC = 2
 #: read length per step of the generic event kernel's chunk length (GENERIC_CHUNK_SAMPLES, csrc/event_generic.h): a read
 #: of n samples runs in 64 chunks of 64 * ceil(n / EVENT_GENERIC_CHUNK_SAMPLES) samples.  tests/test_event_params_cpu.py
 #: reads the header and compares.
@@ -91,6 +96,17 @@ class EventParams(C.Structure):   # sgk_event_params_t: detector_param of src/ev
         q = EventParams.from_buffer_copy(bytes(self))
         q.flags |= SGK_EVENT_PARAMS_GENERIC
         return q
+
+    def preset_kernels(self) -> "EventParams":
+        """A copy that takes the presets' kernels with these thresholds where the domain allows
+        (SGK_EVENT_PARAMS_PRESET_KERNELS; elsewhere the flag is ignored)."""
+        q = EventParams.from_buffer_copy(bytes(self))
+        q.flags |= SGK_EVENT_PARAMS_PRESET_KERNELS
+        return q
+
+    def route(self) -> int:
+        """SGK_EVENT_ROUTE_* these parameters take (sgk_event_params_route); raises when they are out of domain."""
+        return event_params_route(self)
 
     def astuple(self):
         return (int(self.window_length1), int(self.window_length2), float(self.threshold1), float(self.threshold2),
@@ -320,7 +336,7 @@ ABI_SYMBOLS = [
     "sgk_profile_enable", "sgk_profile_reset", "sgk_profile_read",
     "sgk_event_host", "sgk_events_host_free", "sgk_pa_host", "sgk_stat_host", "sgk_jnn_host",
     "sgk_segs_host_free", "sgk_prefix_host", "sgk_signal_in_picoamps", "sgk_getevents",
-    "sgk_event_params_preset", "sgk_event_params_check", "sgk_event_workspace_bytes_param", "sgk_event_param",
+    "sgk_event_params_preset", "sgk_event_params_check", "sgk_event_params_route", "sgk_event_workspace_bytes_param", "sgk_event_param",
     "sgk_event_pa_param", "sgk_job_set_event_params", "sgk_getevents_param",
     "sgk_job_create", "sgk_job_destroy", "sgk_job_device", "sgk_job_begin", "sgk_job_submit", "sgk_job_submit_qts",
     "sgk_job_wait",
@@ -437,6 +453,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         OP = C.POINTER(EventParams)
         L.sgk_event_params_preset.argtypes = [C.c_int, OP]
         L.sgk_event_params_check.argtypes = [OP]
+        if not (old_ok and not hasattr(L, "sgk_event_params_route")):   # (an A/B build from before the route query)
+            L.sgk_event_params_route.argtypes = [OP]
+            L.sgk_event_params_route.restype = C.c_int
         L.sgk_event_workspace_bytes_param.restype = C.c_size_t
         L.sgk_event_workspace_bytes_param.argtypes = [C.c_uint32, C.c_uint64, C.c_uint32, OE, OP]
         L.sgk_event_param.argtypes = [C.POINTER(Batch), OP] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p, OE]
@@ -582,6 +601,15 @@ def device_count() -> int:
 
 
 # ---------------------------------------------------------------------- host batches (numpy)
+
+def event_params_route(params: "EventParams") -> int:
+    """The route sgk_event_param and every other entry point take for these detector parameters (host only):
+    SGK_EVENT_ROUTE_PRESET, SGK_EVENT_ROUTE_PRESET_WINDOWS or SGK_EVENT_ROUTE_GENERIC; raises when they are out of domain."""
+    rc = int(load_library().sgk_event_params_route(C.byref(params)))
+    if rc < 0:
+        check(rc, "sgk_event_params_route")
+    return rc
+
 
 class _HB:
     """Keeps the numpy arrays behind a sgk_host_batch_t alive."""

@@ -334,7 +334,8 @@ static int run_event(const void *samples, bool float_input, const uint64_t *offs
                      const double *dig, const double *off, const double *rng, uint32_t n_reads,
                      uint32_t max_read_len, uint64_t n_samples, int rna, const uint64_t *ev_slots,
                      sgk_event_rec_t *events, uint32_t *n_events, void *ws, size_t ws_bytes, void *stream,
-                     const sgk_event_options_t *opt) {
+                     const sgk_event_options_t *opt, const sgk_event_params_t *rt = nullptr) {
+    // rt: the thresholds of the <.., RT = true> kernels (SGK_EVENT_ROUTE_PRESET_WINDOWS; rna says which windows)
     if (n_reads == 0) return SGK_OK;
     if (!samples || !offsets || !lengths || !ev_slots || !events || !n_events || !ws) return SGK_ERR_ARG;
     if (reinterpret_cast<uintptr_t>(samples) & 15u) return SGK_ERR_ALIGN;
@@ -377,7 +378,10 @@ static int run_event(const void *samples, bool float_input, const uint64_t *offs
     event_multi_plan(sc, n_reads, n_samples, max_read_len, rna, sorted, a.multi_lanes, a.multi_max);
     event_tail_plan(sc, n_reads, n_samples, max_read_len, rna, a.multi_lanes != 0, a.split_from, a.split_seg);
     a.has_long = max_read_len >= sc.long_min ? 1u : 0u;
-    return launch_event(a, rna, float_input, w.n_fb_blocks, static_cast<hipStream_t>(stream));
+    a.thr1 = rt ? rt->threshold1 : 0.0f;
+    a.thr2 = rt ? rt->threshold2 : 0.0f;
+    a.ph = rt ? rt->peak_height : 0.0f;
+    return launch_event(a, rna, float_input, w.n_fb_blocks, static_cast<hipStream_t>(stream), rt != nullptr);
 }
 
 // ---------------------------------------------------------------- caller-supplied detector parameters
@@ -408,12 +412,18 @@ static bool params_equal_preset(const sgk_event_params_t *p, int rna) {
            memcmp(&p->threshold1, &q.threshold1, 4) == 0 && memcmp(&p->threshold2, &q.threshold2, 4) == 0 &&
            memcmp(&p->peak_height, &q.peak_height, 4) == 0;
 }
-// -1: the generic kernel; 0 / 1: the preset's own kernels (sgk_event_opt with this rna)
+// The presets' windows with the caller's thresholds on the presets' kernels (<.., RT = true>): the fast pass skips the
+// long detector where it proves the statistic <= 9 (sgk_long_cold), which says "not > threshold2" from 9.0f on.
+static bool params_preset_windows(const sgk_event_params_t *p) {
+    const bool win = (p->window_length1 == 3 && p->window_length2 == 6) || (p->window_length1 == 7 && p->window_length2 == 14);
+    return win && p->threshold2 >= 9.0f;
+}
+// the one routing decision (sgk_event_params_route); `p` has passed sgk_event_params_check
 static int params_route(const sgk_event_params_t *p) {
-    if (p->flags & SGK_EVENT_PARAMS_GENERIC) return -1;
-    if (params_equal_preset(p, 0)) return 0;
-    if (params_equal_preset(p, 1)) return 1;
-    return -1;
+    if (p->flags & SGK_EVENT_PARAMS_GENERIC) return SGK_EVENT_ROUTE_GENERIC;
+    if (params_equal_preset(p, 0) || params_equal_preset(p, 1)) return SGK_EVENT_ROUTE_PRESET;
+    if ((p->flags & SGK_EVENT_PARAMS_PRESET_KERNELS) && params_preset_windows(p)) return SGK_EVENT_ROUTE_PRESET_WINDOWS;
+    return SGK_EVENT_ROUTE_GENERIC;
 }
 
 static int run_event_param(const void *samples, bool float_input, const uint64_t *offsets, const uint32_t *lengths,
@@ -422,10 +432,11 @@ static int run_event_param(const void *samples, bool float_input, const uint64_t
                            const uint64_t *ev_slots, sgk_event_rec_t *events, uint32_t *n_events, void *ws,
                            size_t ws_bytes, void *stream, const sgk_event_options_t *opt) {
     if (sgk_event_params_check(p) != SGK_OK) return SGK_ERR_ARG;
-    const int route = params_route(p);
-    if (route >= 0)
-        return run_event(samples, float_input, offsets, lengths, dig, off, rng, n_reads, max_read_len, n_samples, route,
-                         ev_slots, events, n_events, ws, ws_bytes, stream, opt);
+    const int route = sgk_event_params_route(p);
+    if (route != SGK_EVENT_ROUTE_GENERIC)   // (both presets' kernels: the plan follows the windows)
+        return run_event(samples, float_input, offsets, lengths, dig, off, rng, n_reads, max_read_len, n_samples,
+                         p->window_length1 == 7 ? 1 : 0, ev_slots, events, n_events, ws, ws_bytes, stream, opt,
+                         route == SGK_EVENT_ROUTE_PRESET_WINDOWS ? p : nullptr);
     if (n_reads == 0) return SGK_OK;
     if (!samples || !offsets || !lengths || !ev_slots || !events || !n_events || !ws) return SGK_ERR_ARG;
     if (reinterpret_cast<uintptr_t>(samples) & 15u) return SGK_ERR_ALIGN;
@@ -640,13 +651,17 @@ int sgk_event_params_check(const sgk_event_params_t *p) {
     const float f[3] = {p->threshold1, p->threshold2, p->peak_height};
     for (int k = 0; k < 3; ++k)
         if (!(f[k] >= 0.0f) || !(f[k] <= FLT_MAX)) return SGK_ERR_ARG;  // NaN fails both comparisons
-    if (p->flags & ~SGK_EVENT_PARAMS_GENERIC) return SGK_ERR_ARG;
+    if (p->flags & ~(SGK_EVENT_PARAMS_GENERIC | SGK_EVENT_PARAMS_PRESET_KERNELS)) return SGK_ERR_ARG;
     return SGK_OK;
+}
+int sgk_event_params_route(const sgk_event_params_t *p) {
+    if (sgk_event_params_check(p) != SGK_OK) return SGK_ERR_ARG;
+    return params_route(p);
 }
 size_t sgk_event_workspace_bytes_param(uint32_t n_reads, uint64_t n_samples, uint32_t max_read_len,
                                        const sgk_event_options_t *opt, const sgk_event_params_t *p) {
     if (sgk_event_params_check(p) != SGK_OK) return 0;
-    if (params_route(p) >= 0) return sgk_event_workspace_bytes_opt(n_reads, n_samples, max_read_len, opt);
+    if (sgk_event_params_route(p) != SGK_EVENT_ROUTE_GENERIC) return sgk_event_workspace_bytes_opt(n_reads, n_samples, max_read_len, opt);
     return event_param_workspace_layout(n_reads, max_read_len).total;
 }
 int sgk_event_param(const sgk_batch_t *b, const sgk_event_params_t *p, const uint64_t *ev_slots, sgk_event_rec_t *events,

@@ -108,6 +108,9 @@ struct EvArgs {
     uint32_t split_from, split_seg;  // (split_from >= n_reads: none)
     uint32_t has_long;               // the batch may hold reads of long_min samples or more
     uint32_t dev;                    // development builds only (-DSGK_DEV, tools/build_variant.sh): SGK_DEV_* below; else 0
+    // the detector's thresholds at run time: read by the <.., RT = true> instances only (the presets' windows with the
+    // caller's thresholds, Det<W1, true> of event_device.h); the presets' own instances never load them
+    float thr1, thr2, ph;
 };
 // What a development build (never the shipped library) can switch off or record per call, from
 // sgk_event_options_t::reserved[0]: the ablation behind profiles/r05_event_instruction_table.md and the per-wave
@@ -149,7 +152,8 @@ struct EvWorkspace {
 EvWorkspace event_workspace_layout(const EvSegConfig &c, uint32_t n_reads, uint64_t n_samples, uint32_t max_read_len,
                                    size_t available /* 0 = default sizing */);
 
-int launch_event(const EvArgs &a, int rna, bool float_input, uint32_t n_fb_blocks, hipStream_t st);  // event_launch.hip
+// rt: the <.., RT = true> instances, thresholds from a.thr1 / thr2 / ph (rna then only selects the windows)
+int launch_event(const EvArgs &a, int rna, bool float_input, uint32_t n_fb_blocks, hipStream_t st, bool rt = false);  // event_launch.hip
 
 // ---- caller-supplied detector parameters (k_event_param, event_param.hip) ----------------------------------------
 // What the generic kernel takes beside EvArgs, of which it uses the batch, the arena, hdr, order (null: batch order) and
@@ -176,12 +180,13 @@ int launch_event_param(const EvArgs &a, const EvParamArgs &pa, bool float_input,
 
 // ---- one launch per kernel, defined in the unit that holds the kernel (without relocatable device code a kernel is
 // launched from its own translation unit); launch_event is made of these.  rna / float_input select the kernel's
-// <W1, T> instance: detector preset (3: DNA, 7: RNA) and sample type (int16_t or float).
+// <W1, T, RT> instance: detector preset (3: DNA, 7: RNA), sample type (int16_t or float) and where the thresholds come
+// from (rt: the arguments).
 int launch_k_seg_plan(hipStream_t st, const EvArgs &a);                                        // event_seg.hip
-int launch_k_event_seg(int rna, bool float_input, hipStream_t st, const EvArgs &a);            // event_seg.hip
-int launch_k_event(int rna, bool float_input, hipStream_t st, const EvArgs &a);                // event_whole.hip
-int launch_k_event_multi(int rna, bool float_input, hipStream_t st, const EvArgs &a);          // event_multi.hip
-int launch_k_event_fallback(int rna, bool float_input, uint32_t n_fb_blocks, hipStream_t st, const EvArgs &a);  // event_fallback.hip
+int launch_k_event_seg(int rna, bool float_input, hipStream_t st, const EvArgs &a, bool rt = false);            // event_seg.hip
+int launch_k_event(int rna, bool float_input, hipStream_t st, const EvArgs &a, bool rt = false);                // event_whole.hip
+int launch_k_event_multi(int rna, bool float_input, hipStream_t st, const EvArgs &a, bool rt = false);          // event_multi.hip
+int launch_k_event_fallback(int rna, bool float_input, uint32_t n_fb_blocks, hipStream_t st, const EvArgs &a, bool rt = false);  // event_fallback.hip
 int launch_k_event_param(bool float_input, uint32_t n_blocks, hipStream_t st, const EvArgs &a, const EvParamArgs &pa);  // event_param.hip
 
 }  // namespace sgk

@@ -285,7 +285,7 @@ __device__ __forceinline__ uint32_t shift_in(uint32_t w, lmask_t c) {
 // and i + W1: its estimates come from their four floats (sgk_lside_halves) -- two f64 subtractions and two conversions
 // per index less than with b2 = P(i+W2) - P(i), and P(i) .. P(i+W1-1) need not stay in the prefix ring.  Every sum is
 // exact and every float the same RN32 of it, so the short statistic is bit for bit what the trailing form computes.
-template <int W1, typename T, bool FLAGGED, bool LEAD = false>
+template <int W1, typename T, bool FLAGGED, bool LEAD = false, bool RT = false>
 struct LazyPass {
     static_assert(!(LEAD && FLAGGED), "the fallback keeps its domain checks and TwoSum form");
     using C = LzCfg<W1>;
@@ -340,6 +340,7 @@ struct LazyPass {
     unsigned long long *bm;       // read's bitmap (global)
     RepairCtx rep;                // FLAGGED only
     int next_t;                   // FLAGGED only
+    [[no_unique_address]] Det<W1, RT> dt;   // the thresholds: the preset's constants (empty) or three wave-uniform floats
     int dirty;                    // FLAGGED only: block-relative index up to which this lane's own window sums are
                                   // not trusted (an addition of ITS running prefix was inexact, see tstep)
 
@@ -428,7 +429,7 @@ struct LazyPass {
     // masks.  u: block-relative index (an inline constant in the fast form); live: lanes that take the step.
     template <bool SLOW>
     __device__ __forceinline__ void dstep_core(const int u, const float v, const lmask_t hck, const lmask_t live) {
-        constexpr float ph = DetParam<W1>::ph, thr1 = DetParam<W1>::thr1;
+        const float ph = dt.ph(), thr1 = dt.thr1();
         const float d1 = v - sv;
         const float ee = lane_of(inpk) ? d1 : -d1;   // in a peak: v - peak_value; before one: peak_value - v
         lmask_t P = __ballot(ee > 0.0f);             // v > peak_value (in a peak) / v < peak_value (before one)
@@ -745,14 +746,16 @@ __device__ __forceinline__ void lz_flush(uint32_t *ring, unsigned long long *bm,
 //   steps  : indices every lane runs (wave-uniform: warm-up + chunk length)
 //   active : whether this lane runs in this pass
 // Writes the lane's bitmap words, its hot-run records and (speculative pass) snap.init / snap.at_e.
-template <int W1, typename T, bool FLAGGED, bool LEAD = false>
+template <int W1, typename T, bool FLAGGED, bool LEAD = false, bool RT = false>
 __device__ __forceinline__ void pass_lazy(const ReadCtx<T> &rc, bool given, int lead, int steps, bool active, int s,
-                                          int e, LzLds *L, const RepairCtx *rep, bool by_progress = false) {
-    using LP = LazyPass<W1, T, FLAGGED, LEAD>;
+                                          int e, LzLds *L, const RepairCtx *rep, bool by_progress = false,
+                                          const Det<W1, RT> dt = Det<W1, RT>{}) {
+    using LP = LazyPass<W1, T, FLAGGED, LEAD, RT>;
     constexpr int W2 = LP::W2, R = LP::R;
     if (!__any(active)) return;
     const int l = lane_id();
     LP f;
+    f.dt = dt;
     f.n = (int)rc.n;
     // lanes that do not take part in the pass own nothing: nothing they emit or record can land anywhere
     f.s = active ? s : 0x7fffffff;
@@ -969,12 +972,12 @@ __device__ __forceinline__ void pass_lazy(const ReadCtx<T> &rc, bool given, int 
 // on whether chain_segment is in the unit.
 // (`inline`: pins the inlining of both instances into k_event_seg, as in the unit that held every kernel -- out of line
 // they cost its int16 instances 80 bytes of scratch)
-template <int W1, typename T, bool FLAGGED, bool COLLECT = false>
+template <int W1, typename T, bool FLAGGED, bool COLLECT = false, bool RT = false>
 __device__ inline void replay_run(const ReadCtx<T> &rc, const RepairCtx *rep, bool has, int i, int b, int bits_lo,
-                           int bits_hi, EvHeader *hdr, int *found = nullptr) {
+                           int bits_hi, EvHeader *hdr, int *found = nullptr, const Det<W1, RT> dt = Det<W1, RT>{}) {
     if (has && b > i) atomicAdd(&hdr->n_replay_idx, (unsigned long long)(b - i));
     constexpr int W2 = 2 * W1;
-    constexpr float ph = DetParam<W1>::ph, thr2 = DetParam<W1>::thr2;
+    const float ph = dt.ph(), thr2 = dt.thr2();
     const int n = (int)rc.n;
     const unsigned cnt2 = (n - 2 * W2 + 1) > 0 ? (unsigned)(n - 2 * W2 + 1) : 0u;
     uint32_t *bm32 = reinterpret_cast<uint32_t *>(rc.bm);
@@ -1019,9 +1022,9 @@ __device__ inline void replay_run(const ReadCtx<T> &rc, const RepairCtx *rep, bo
 // began in front of it leaves its peaks in front of the span to whoever replays the span's cross runs)
 // (`inline`, as above: out of line -- where k_event<3, short> with the mask-history bookkeeping had it -- the read's
 // context has to live in scratch for it)
-template <int W1, typename T, bool FLAGGED>
+template <int W1, typename T, bool FLAGGED, bool RT = false>
 __device__ inline void replay_long_runs(const ReadCtx<T> &rc, LzLds *L, const RepairCtx *rep, bool active, int bits_lo,
-                                        EvHeader *hdr) {
+                                        EvHeader *hdr, const Det<W1, RT> dt = Det<W1, RT>{}) {
     const int l = lane_id();
     const int nrec = active ? L->nrec[l] : 0;
     for (int k = 0; k < LZ_NREC; ++k) {
@@ -1029,7 +1032,7 @@ __device__ inline void replay_long_runs(const ReadCtx<T> &rc, LzLds *L, const Re
         if (!__any(has)) break;
         const int i = has ? L->runs[l][k].a : 0;
         const int b = has ? L->runs[l][k].b : 0;
-        replay_run<W1, T, FLAGGED>(rc, rep, has, i, b, bits_lo, 0x7fffffff, hdr);
+        replay_run<W1, T, FLAGGED, false, RT>(rc, rep, has, i, b, bits_lo, 0x7fffffff, hdr, nullptr, dt);
     }
 }
 
@@ -1047,10 +1050,11 @@ __device__ inline void replay_long_runs(const ReadCtx<T> &rc, LzLds *L, const Re
 // MULTI (k_event_multi): the wave holds 64 / lanes reads, `lanes` consecutive lanes each (rc, b and the return code are
 // per lane; a = 0, mode 0, no seg): a short read on all 64 lanes spends more steps on warm-ups than on its samples.
 // LEAD: the form of the fast pass (LazyPass).
-template <int W1, typename T, bool FLAGGED, bool MULTI = false, bool LEAD = false>
+template <int W1, typename T, bool FLAGGED, bool MULTI = false, bool LEAD = false, bool RT = false>
 __device__ __forceinline__ int detect_span(const ReadCtx<T> &rc, EvHeader *hdr, LzLds *L, const RepairCtx *rep,
                                            const int a, const int b, const int mode, const int lead_override,
-                                           SegState *seg, const int lanes = 64) {
+                                           SegState *seg, const int lanes = 64,
+                                           const Det<W1, RT> dt = Det<W1, RT>{}) {
     const int n = (int)rc.n;
     if constexpr (!MULTI) {
         if (b <= a) return 0;
@@ -1115,8 +1119,8 @@ __device__ __forceinline__ int detect_span(const ReadCtx<T> &rc, EvHeader *hdr, 
     const int l = lane_id();
     const uint32_t pol = FLAGGED ? 0u : prio_policy(rc.dev);
     for (int iter = 0; iter < 66; ++iter) {
-        pass_lazy<W1, T, FLAGGED, LEAD>(rc, first ? (mode == 2 && c == 0) : true, first ? lead_c : 0, first ? TT : Kmax, run,
-                                        s, e, L, rep, first && (pol == 1u || pol == 2u));
+        pass_lazy<W1, T, FLAGGED, LEAD, RT>(rc, first ? (mode == 2 && c == 0) : true, first ? lead_c : 0, first ? TT : Kmax, run,
+                                            s, e, L, rep, first && (pol == 1u || pol == 2u), dt);
         __syncthreads();
         // chunk c is right iff it started (at s) from the state chunk c-1 ended with
         const LzSnapState pe = L->snap.at_e[c > 0 ? l - 1 : l];
@@ -1186,16 +1190,17 @@ __device__ __forceinline__ int detect_span(const ReadCtx<T> &rc, EvHeader *hdr, 
         __threadfence_block();
         __syncthreads();  // every lane's bitmap words are in memory before anything is ORed into them
         if (pre >= 0 && !pre_out) atomicOr(reinterpret_cast<uint32_t *>(rc.bm) + (pre >> 5), 1u << (pre & 31));
-        if (hotm != 0ull) replay_long_runs<W1, T, FLAGGED>(rc, L, rep, mine_ok, a, hdr);
+        if (hotm != 0ull) replay_long_runs<W1, T, FLAGGED, RT>(rc, L, rep, mine_ok, a, hdr, dt);
     }
     return rcode;
 }
 // one wave, one read
-template <int W1, typename T, bool FLAGGED>
-__device__ __forceinline__ int detect_read_lazy(const ReadCtx<T> &rc, EvHeader *hdr, LzLds *L, const RepairCtx *rep) {
+template <int W1, typename T, bool FLAGGED, bool RT = false>
+__device__ __forceinline__ int detect_read_lazy(const ReadCtx<T> &rc, EvHeader *hdr, LzLds *L, const RepairCtx *rep,
+                                                const Det<W1, RT> dt = Det<W1, RT>{}) {
     const int n = (int)rc.n;
     if (n <= 0) return 0;
-    return detect_span<W1, T, FLAGGED>(rc, hdr, L, rep, 0, n, 0, 0, nullptr);
+    return detect_span<W1, T, FLAGGED, false, false, RT>(rc, hdr, L, rep, 0, n, 0, 0, nullptr, 64, dt);
 }
 
 }  // namespace sgk

@@ -96,6 +96,28 @@ template <>
 struct DetParam<7> {  // event_detection_rna, src/events.c:50-54
     static constexpr float thr1 = 2.5f, thr2 = 9.0f, ph = 1.0f;
 };
+// Where the fast kernels take the three thresholds from.  RT = false: the preset's constants, an empty object that costs
+// nothing.  RT = true: three wave-uniform floats of the kernel's arguments (EvArgs::thr1 / thr2 / ph) -- the presets'
+// windows with the caller's thresholds (SGK_EVENT_PARAMS_PRESET_KERNELS; domain and per-site argument: DESIGN.md 3.16).
+template <int W1, bool RT>
+struct Det;
+template <int W1>
+struct Det<W1, false> {
+    Det() = default;
+    __device__ __forceinline__ explicit Det(const EvArgs &) {}
+    __device__ __forceinline__ constexpr float thr1() const { return DetParam<W1>::thr1; }
+    __device__ __forceinline__ constexpr float thr2() const { return DetParam<W1>::thr2; }
+    __device__ __forceinline__ constexpr float ph() const { return DetParam<W1>::ph; }
+};
+template <int W1>
+struct Det<W1, true> {
+    float t1, t2, h;
+    Det() = default;
+    __device__ __forceinline__ explicit Det(const EvArgs &a) : t1(a.thr1), t2(a.thr2), h(a.ph) {}
+    __device__ __forceinline__ float thr1() const { return t1; }
+    __device__ __forceinline__ float thr2() const { return t2; }
+    __device__ __forceinline__ float ph() const { return h; }
+};
 
 // ---------------------------------------------------------------- per-read context
 template <typename T>

@@ -10,7 +10,9 @@ namespace sgk {
 
 using EventList = EventListT<REP_MAX_EVENTS>;
 
-template <int W1, typename T>
+// RT: the preset's windows, thresholds from the arguments -- in the fast pass with its repair context and in the
+// generic pass alike
+template <int W1, typename T, bool RT = false>
 __global__ __launch_bounds__(64) void k_event_fallback(EvArgs a) {
     __shared__ PrefixLds L;
     __shared__ LzLds Lz;
@@ -18,6 +20,8 @@ __global__ __launch_bounds__(64) void k_event_fallback(EvArgs a) {
     double *P = a.scratch + (uint64_t)blockIdx.x * a.scratch_stride;
     double *P2 = P + a.scratch_stride / 2;
     const uint32_t nf = a.hdr->n_flagged;
+    const Det<W1, RT> dt(a);
+    const DetVals dv = RT ? DetVals{W1, 2 * W1, dt.thr1(), dt.thr2(), dt.ph()} : DetVals{};  // (RT = false: det_vals ignores it)
     for (;;) {
         uint32_t w = 0;
         if (lane_id() == 0) w = atomicAdd(&a.hdr->fb_next, 1u);
@@ -36,8 +40,8 @@ __global__ __launch_bounds__(64) void k_event_fallback(EvArgs a) {
         rep.ev = events.ev;
         rep.nev = events.count < REP_MAX_EVENTS ? events.count : REP_MAX_EVENTS;
         rep.all_dirty = events.count > REP_MAX_EVENTS;
-        const int rcode = detect_read_lazy<W1, T, true>(rc, a.hdr, &Lz, &rep);
-        if (rcode) detect_read<W1, T>(rc, DetVals{}, LEAD, a.hdr);
+        const int rcode = detect_read_lazy<W1, T, true, RT>(rc, a.hdr, &Lz, &rep, dt);
+        if (rcode) detect_read<W1, T, RT>(rc, dv, LEAD, a.hdr);
         __threadfence();
         __syncthreads();
         build_read_prefix<T>(a, rc, r);
@@ -45,8 +49,12 @@ __global__ __launch_bounds__(64) void k_event_fallback(EvArgs a) {
     }
 }
 
-int launch_k_event_fallback(int rna, bool float_input, uint32_t n_fb_blocks, hipStream_t st, const EvArgs &a) {
-    if (rna && float_input) SGK_LAUNCH("k_event_fallback", (k_event_fallback<7, float>), n_fb_blocks, 64, st, a);
+int launch_k_event_fallback(int rna, bool float_input, uint32_t n_fb_blocks, hipStream_t st, const EvArgs &a, bool rt) {
+    if (rt && rna && float_input) SGK_LAUNCH("k_event_fallback", (k_event_fallback<7, float, true>), n_fb_blocks, 64, st, a);
+    else if (rt && rna) SGK_LAUNCH("k_event_fallback", (k_event_fallback<7, int16_t, true>), n_fb_blocks, 64, st, a);
+    else if (rt && float_input) SGK_LAUNCH("k_event_fallback", (k_event_fallback<3, float, true>), n_fb_blocks, 64, st, a);
+    else if (rt) SGK_LAUNCH("k_event_fallback", (k_event_fallback<3, int16_t, true>), n_fb_blocks, 64, st, a);
+    else if (rna && float_input) SGK_LAUNCH("k_event_fallback", (k_event_fallback<7, float>), n_fb_blocks, 64, st, a);
     else if (rna) SGK_LAUNCH("k_event_fallback", (k_event_fallback<7, int16_t>), n_fb_blocks, 64, st, a);
     else if (float_input) SGK_LAUNCH("k_event_fallback", (k_event_fallback<3, float>), n_fb_blocks, 64, st, a);
     else SGK_LAUNCH("k_event_fallback", (k_event_fallback<3, int16_t>), n_fb_blocks, 64, st, a);

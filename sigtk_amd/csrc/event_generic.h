@@ -2,7 +2,9 @@
 // scan (seq_prefix), the two-automaton detector stepped index by index on differences of those arrays (det_step,
 // detect_pass, detect_read) and the builder on them (build_read_prefix).  Two kernels share it:
 //   k_event_fallback  (event_fallback.hip)  a preset's reads the fast pass cannot take: <W1> is a template argument, the
-//                                           windows and thresholds are DetParam<W1>'s constants
+//                                           windows and thresholds are DetParam<W1>'s constants (RT: the windows are,
+//                                           the thresholds are DetVals' -- the presets' windows with the caller's
+//                                           thresholds)
 //   k_event_param     (event_param.hip)     caller-supplied detector parameters: <0>, everything in DetVals at run time
 // The map of the event units is in event_device.h.
 #pragma once
@@ -21,20 +23,20 @@ __device__ inline uint32_t chunk_len(int64_t n) {
 
 // ---------------------------------------------------------------- detector parameters
 // detector_param of src/events.c:35-41 as values.  With W1 > 0 (a preset) every user below takes the compile-time
-// constants instead and the struct is dead.
+// constants instead and the struct is dead; with RT as well only its windows are.
 struct DetVals {
     int w1, w2;
     float thr1, thr2, ph;
 };
-template <int W1>
+template <int W1, bool RT = false>
 __device__ __forceinline__ DetVals det_vals(const DetVals &dv) {
     if constexpr (W1 > 0) {
         DetVals p;
         p.w1 = W1;
         p.w2 = 2 * W1;
-        p.thr1 = DetParam<W1>::thr1;
-        p.thr2 = DetParam<W1>::thr2;
-        p.ph = DetParam<W1>::ph;
+        p.thr1 = RT ? dv.thr1 : DetParam<W1>::thr1;
+        p.thr2 = RT ? dv.thr2 : DetParam<W1>::thr2;
+        p.ph = RT ? dv.ph : DetParam<W1>::ph;
         return p;
     } else {
         return dv;
@@ -101,9 +103,9 @@ __device__ inline DetState det_shfl_up(const DetState &a) {
 
 // One index of short_long_peak_detector (src/events.c:383-440): short first, then long.
 // emit_s / emit_l receive the emitted peak position of each detector, or -1.
-template <int W1>
+template <int W1, bool RT = false>
 __device__ inline void det_step(const DetVals &dv, DetState &d, int i, float v1, float v2, int &emit_s, int &emit_l) {
-    const DetVals p = det_vals<W1>(dv);
+    const DetVals p = det_vals<W1, RT>(dv);
     emit_s = -1;
     emit_l = -1;
     // ---- short detector: its masked_to stays 0, so only index 0 is skipped (events.c:387)
@@ -169,11 +171,11 @@ __device__ inline void det_step(const DetVals &dv, DetState &d, int i, float v1,
 //   st     : state at the pass start (lead == 0 only; the speculative pass starts fresh)
 //   at_s   : out, normalised state when the lane reaches its chunk start s (speculative pass)
 //   at_e   : out, normalised state when the lane reaches its chunk end e (written only when reached)
-template <int W1, typename T>
+template <int W1, typename T, bool RT = false>
 __device__ __attribute__((noinline)) void detect_pass(const ReadCtx<T> &rc, const DetVals &dv, int lead, bool active,
                                                       int64_t s, int64_t e, uint32_t K, DetState st, DetState &at_s,
                                                       DetState &at_e) {
-    const DetVals p = det_vals<W1>(dv);
+    const DetVals p = det_vals<W1, RT>(dv);
     const int w1 = p.w1, w2 = p.w2;
     const int64_t n = rc.n;
     const int64_t i_begin = s - lead;
@@ -222,7 +224,7 @@ __device__ __attribute__((noinline)) void detect_pass(const ReadCtx<T> &rc, cons
                     else v2 = sgk_tstat_ref_rt(wf2, A, A2, B, B2);
                 }
                 int es, el;
-                det_step<W1>(dv, d, (int)i, v1, v2, es, el);
+                det_step<W1, RT>(dv, d, (int)i, v1, v2, es, el);
 #pragma unroll
                 for (int z = 0; z < 2; ++z) {
                     const int pk = z ? el : es;
@@ -250,7 +252,7 @@ __device__ __attribute__((noinline)) void detect_pass(const ReadCtx<T> &rc, cons
 // the speculative pass its end state is final; every iteration of the loop below makes at least the first lane whose
 // start state was wrong final.  63 iterations therefore always reach the sequential result whatever `lead` is; the loop
 // allows 64.
-template <int W1, typename T>
+template <int W1, typename T, bool RT = false>
 __device__ void detect_read(const ReadCtx<T> &rc, const DetVals &dv, int lead, EvHeader *hdr) {
     const int64_t n = rc.n;
     if (n <= 0) return;
@@ -261,7 +263,7 @@ __device__ void detect_read(const ReadCtx<T> &rc, const DetVals &dv, int lead, E
     const bool active = s < n;
     const DetState fresh = det_fresh(0);
     DetState at_s = fresh, at_e = fresh;
-    detect_pass<W1, T>(rc, dv, lead, active, s, e, K, fresh, at_s, at_e);
+    detect_pass<W1, T, RT>(rc, dv, lead, active, s, e, K, fresh, at_s, at_e);
     DetState init = at_s;
     for (int iter = 0; iter < 64; ++iter) {
         const DetState pe = det_shfl_up(at_e);
@@ -270,7 +272,7 @@ __device__ void detect_read(const ReadCtx<T> &rc, const DetVals &dv, int lead, E
         if (badmask == 0ull) break;
         if (bad) init = pe;
         DetState unused = fresh;
-        detect_pass<W1, T>(rc, dv, 0, bad, s, e, K, pe, unused, at_e);
+        detect_pass<W1, T, RT>(rc, dv, 0, bad, s, e, K, pe, unused, at_e);
         if (c == 0) atomicAdd(&hdr->n_rerun, (uint32_t)__popcll(badmask));
     }
 }

@@ -17,7 +17,7 @@ namespace sgk {
 // (Tried in round 1: cutting the batch into read slices and running the builder of slice s on a side stream under the
 // detector of slice s+1.  Both kernels contend for VALU issue and the detector needs >= 3072 reads in flight to fill its
 // 12 waves/CU, so the overlapped step was 8.8 ms against 7.8 ms.)
-int launch_event(const EvArgs &a, int rna, bool float_input, uint32_t n_fb_blocks, hipStream_t st) {
+int launch_event(const EvArgs &a, int rna, bool float_input, uint32_t n_fb_blocks, hipStream_t st, bool rt) {
     if (a.n_reads == 0) return SGK_OK;
     ProfScope whole("path:event", st);
     SGK_HIP_TRY(hipMemsetAsync(a.hdr, 0, sizeof(EvHeader), st));
@@ -43,14 +43,14 @@ int launch_event(const EvArgs &a, int rna, bool float_input, uint32_t n_fb_block
     side.open(st, (int)side_multi + (int)side_whole);
     const hipStream_t st_multi = side_multi ? side.stream(0) : st;
     const hipStream_t st_whole = side_whole ? side.stream(side_multi ? 1 : 0) : st;
-    if (rc == SGK_OK && ao.max_segs && !tail_only) rc = launch_k_event_seg(rna, float_input, st, ao);
-    if (rc == SGK_OK && ao.multi_lanes) rc = launch_k_event_multi(rna, float_input, st_multi, ao);
-    if (rc == SGK_OK && !all_short) rc = launch_k_event(rna, float_input, st_whole, ao);
-    if (rc == SGK_OK && tail_only) rc = launch_k_event_seg(rna, float_input, st, ao);
+    if (rc == SGK_OK && ao.max_segs && !tail_only) rc = launch_k_event_seg(rna, float_input, st, ao, rt);
+    if (rc == SGK_OK && ao.multi_lanes) rc = launch_k_event_multi(rna, float_input, st_multi, ao, rt);
+    if (rc == SGK_OK && !all_short) rc = launch_k_event(rna, float_input, st_whole, ao, rt);
+    if (rc == SGK_OK && tail_only) rc = launch_k_event_seg(rna, float_input, st, ao, rt);
     // join: the fallback kernel (and whatever the caller enqueues next) waits for the side streams as well
     side.join();
     if (rc != SGK_OK) return rc;
-    return launch_k_event_fallback(rna, float_input, n_fb_blocks, st, a);
+    return launch_k_event_fallback(rna, float_input, n_fb_blocks, st, a, rt);
 }
 
 // The generic kernel for caller-supplied parameters: the header, the dispatch order, one persistent launch.

@@ -6,7 +6,7 @@ namespace sgk {
 // Short reads, several per wavefront: `lanes` consecutive lanes share a read (detector: detect_span<MULTI>), then the
 // wave builds its reads one after the other.  The short reads are the tail of the dispatch order (launch_order sorts by
 // length class, longest first; multi_max is a class boundary) or, in a batch without an order, all reads.
-template <int W1, typename T>
+template <int W1, typename T, bool RT = false>
 __global__ __launch_bounds__(64, (W1 == 3 ? DET_WAVES_DNA : DET_WAVES_RNA)) void k_event_multi(EvArgs a) {
     __shared__ EventLds L;
     const int lanes = (int)a.multi_lanes, G = 64 / lanes;
@@ -24,8 +24,8 @@ __global__ __launch_bounds__(64, (W1 == 3 ? DET_WAVES_DNA : DET_WAVES_RNA)) void
     const bool mine = has && !(a.max_segs && rc.n >= (int64_t)a.long_min);  // (no tail split in a batch with packed reads)
     if (!mine) rc.n = 0;
     constexpr bool MULTI_LEAD = W1 == 3 && ((SGK_EVENT_LEAD) & 4) != 0;  // (off in the shipped build, event_detect.h)
-    const int rcode = detect_span<W1, T, false, true, MULTI_LEAD>(rc, a.hdr, &L.lz, nullptr, 0, (int)rc.n, 0,
-                                                                  a.lead_override, nullptr, lanes);
+    const int rcode = detect_span<W1, T, false, true, MULTI_LEAD, RT>(rc, a.hdr, &L.lz, nullptr, 0, (int)rc.n, 0,
+                                                                  a.lead_override, nullptr, lanes, Det<W1, RT>(a));
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __syncthreads();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -41,10 +41,14 @@ __global__ __launch_bounds__(64, (W1 == 3 ? DET_WAVES_DNA : DET_WAVES_RNA)) void
     }
 }
 
-int launch_k_event_multi(int rna, bool float_input, hipStream_t st, const EvArgs &a) {
+int launch_k_event_multi(int rna, bool float_input, hipStream_t st, const EvArgs &a, bool rt) {
     const uint32_t per_wave = 64u / a.multi_lanes;
     const uint32_t grid = (a.n_reads + per_wave - 1) / per_wave;
-    if (rna && float_input) SGK_LAUNCH("k_event_multi", (k_event_multi<7, float>), grid, 64, st, a);
+    if (rt && rna && float_input) SGK_LAUNCH("k_event_multi", (k_event_multi<7, float, true>), grid, 64, st, a);
+    else if (rt && rna) SGK_LAUNCH("k_event_multi", (k_event_multi<7, int16_t, true>), grid, 64, st, a);
+    else if (rt && float_input) SGK_LAUNCH("k_event_multi", (k_event_multi<3, float, true>), grid, 64, st, a);
+    else if (rt) SGK_LAUNCH("k_event_multi", (k_event_multi<3, int16_t, true>), grid, 64, st, a);
+    else if (rna && float_input) SGK_LAUNCH("k_event_multi", (k_event_multi<7, float>), grid, 64, st, a);
     else if (rna) SGK_LAUNCH("k_event_multi", (k_event_multi<7, int16_t>), grid, 64, st, a);
     else if (float_input) SGK_LAUNCH("k_event_multi", (k_event_multi<3, float>), grid, 64, st, a);
     else SGK_LAUNCH("k_event_multi", (k_event_multi<3, int16_t>), grid, 64, st, a);

@@ -71,7 +71,7 @@ __device__ __forceinline__ void st_agent(uint32_t *p, uint32_t v) {
 }
 // (ONE call site of detect_span for the speculative pass and the re-run from the true state: each inlined copy of the
 // detector pass is ~25 KB of code.)
-template <int W1, typename T>
+template <int W1, typename T, bool RT = false>
 __device__ __forceinline__ void chain_segment(const EvArgs &a, uint32_t bx, EventLds *L) {
     if (bx >= a.hdr->n_segs) return;
     const SegDesc d = a.segs[bx];
@@ -84,6 +84,7 @@ __device__ __forceinline__ void chain_segment(const EvArgs &a, uint32_t bx, Even
     seg_span(seg_len, g, rc.n, sa, sb);
     SegState *st = a.seg_state + bx;
     const int l = lane_id();
+    const Det<W1, RT> dt(a);
     const uint32_t nseg = lrp->nseg;
     bool declined = false;
     uint32_t prev_cum = 0u;
@@ -94,7 +95,7 @@ __device__ __forceinline__ void chain_segment(const EvArgs &a, uint32_t bx, Even
     if (a.dev & SGK_DEV_TRACE) tt0 = wall_clock64();
 #endif
     for (int attempt = 0; attempt < 2; ++attempt) {
-        const int rcode = detect_span<W1, T, false>(rc, a.hdr, &L->lz, nullptr, sa, sb, mode, a.lead_override, st);
+        const int rcode = detect_span<W1, T, false, false, false, RT>(rc, a.hdr, &L->lz, nullptr, sa, sb, mode, a.lead_override, st, 64, dt);
 #ifdef SGK_DEV
         if ((a.dev & SGK_DEV_TRACE) && attempt == 0) tt1 = wall_clock64();
 #endif
@@ -147,7 +148,7 @@ __device__ __forceinline__ void chain_segment(const EvArgs &a, uint32_t bx, Even
             const bool has = l < nc;
             const LzRun run = has ? st->cross[l] : LzRun{0, 0};
             int found = 0;
-            replay_run<W1, T, false, true>(rc, nullptr, has, run.a, run.b, 0, sa, a.hdr, &found);
+            replay_run<W1, T, false, true, RT>(rc, nullptr, has, run.a, run.b, 0, sa, a.hdr, &found, dt);
             if (__any(found != 0)) declined = true;
         }
     }
@@ -264,18 +265,22 @@ __device__ __forceinline__ void chain_segment(const EvArgs &a, uint32_t bx, Even
 }
 
 // The segments' kernel: a workgroup per entry of the segment list (usually much shorter than its capacity).
-template <int W1, typename T>
+template <int W1, typename T, bool RT = false>
 __global__ __launch_bounds__(64, (W1 == 3 ? DET_WAVES_DNA : DET_WAVES_RNA)) void k_event_seg(EvArgs a) {
     __shared__ EventLds L;
-    chain_segment<W1, T>(a, blockIdx.x, &L);
+    chain_segment<W1, T, RT>(a, blockIdx.x, &L);
 }
 
 int launch_k_seg_plan(hipStream_t st, const EvArgs &a) {
     SGK_LAUNCH_UNTIMED(k_seg_plan, (a.n_reads + 255) / 256, 256, st, a);
     return SGK_OK;
 }
-int launch_k_event_seg(int rna, bool float_input, hipStream_t st, const EvArgs &a) {
-    if (rna && float_input) SGK_LAUNCH("k_event_seg", (k_event_seg<7, float>), a.max_segs, 64, st, a);
+int launch_k_event_seg(int rna, bool float_input, hipStream_t st, const EvArgs &a, bool rt) {
+    if (rt && rna && float_input) SGK_LAUNCH("k_event_seg", (k_event_seg<7, float, true>), a.max_segs, 64, st, a);
+    else if (rt && rna) SGK_LAUNCH("k_event_seg", (k_event_seg<7, int16_t, true>), a.max_segs, 64, st, a);
+    else if (rt && float_input) SGK_LAUNCH("k_event_seg", (k_event_seg<3, float, true>), a.max_segs, 64, st, a);
+    else if (rt) SGK_LAUNCH("k_event_seg", (k_event_seg<3, int16_t, true>), a.max_segs, 64, st, a);
+    else if (rna && float_input) SGK_LAUNCH("k_event_seg", (k_event_seg<7, float>), a.max_segs, 64, st, a);
     else if (rna) SGK_LAUNCH("k_event_seg", (k_event_seg<7, int16_t>), a.max_segs, 64, st, a);
     else if (float_input) SGK_LAUNCH("k_event_seg", (k_event_seg<3, float>), a.max_segs, 64, st, a);
     else SGK_LAUNCH("k_event_seg", (k_event_seg<3, int16_t>), a.max_segs, 64, st, a);

@@ -12,7 +12,8 @@ constexpr bool EV_LEAD = ((SGK_EVENT_LEAD) & (W1 == 3 ? 1 : 2)) != 0;
 template <int W1>
 constexpr bool EV_CARRY = ((SGK_BUILD_CARRY) & (W1 == 3 ? 1 : 2)) != 0;
 
-template <int W1, typename T>
+// RT: the thresholds come from the arguments (Det<W1, RT>, event_device.h)
+template <int W1, typename T, bool RT = false>
 __global__ __launch_bounds__(64, (W1 == 3 ? DET_WAVES_DNA : DET_WAVES_RNA)) void k_event(EvArgs a) {
     __shared__ EventLds L;
     // One read per workgroup, longest first (launch_order): a kernel cannot end before its longest read has, so that one
@@ -29,10 +30,10 @@ __global__ __launch_bounds__(64, (W1 == 3 ? DET_WAVES_DNA : DET_WAVES_RNA)) void
     unsigned long long t0 = 0ull, t1 = 0ull;
     if (a.dev & SGK_DEV_TRACE) t0 = wall_clock64();
     int rcode = 0;
-    if (!(a.dev & SGK_DEV_NO_DETECT)) rcode = detect_span<W1, T, false, false, EV_LEAD<W1>>(rc, a.hdr, &L.lz, nullptr, 0, (int)rc.n, 0, a.lead_override, nullptr);
+    if (!(a.dev & SGK_DEV_NO_DETECT)) rcode = detect_span<W1, T, false, false, EV_LEAD<W1>, RT>(rc, a.hdr, &L.lz, nullptr, 0, (int)rc.n, 0, a.lead_override, nullptr, 64, Det<W1, RT>(a));
     if (a.dev & SGK_DEV_TRACE) t1 = wall_clock64();
 #else
-    const int rcode = detect_span<W1, T, false, false, EV_LEAD<W1>>(rc, a.hdr, &L.lz, nullptr, 0, (int)rc.n, 0, a.lead_override, nullptr);
+    const int rcode = detect_span<W1, T, false, false, EV_LEAD<W1>, RT>(rc, a.hdr, &L.lz, nullptr, 0, (int)rc.n, 0, a.lead_override, nullptr, 64, Det<W1, RT>(a));
 #endif
     // the bitmap words of every lane (and the replay's atomics) are complete before any lane of this workgroup reads
     // them back.  Workgroup scope: the wave's own CU only -- an agent-scope release / acquire pair here writes back and
@@ -57,8 +58,12 @@ __global__ __launch_bounds__(64, (W1 == 3 ? DET_WAVES_DNA : DET_WAVES_RNA)) void
 #endif
 }
 
-int launch_k_event(int rna, bool float_input, hipStream_t st, const EvArgs &a) {
-    if (rna && float_input) SGK_LAUNCH("k_event", (k_event<7, float>), a.n_reads, 64, st, a);
+int launch_k_event(int rna, bool float_input, hipStream_t st, const EvArgs &a, bool rt) {
+    if (rt && rna && float_input) SGK_LAUNCH("k_event", (k_event<7, float, true>), a.n_reads, 64, st, a);
+    else if (rt && rna) SGK_LAUNCH("k_event", (k_event<7, int16_t, true>), a.n_reads, 64, st, a);
+    else if (rt && float_input) SGK_LAUNCH("k_event", (k_event<3, float, true>), a.n_reads, 64, st, a);
+    else if (rt) SGK_LAUNCH("k_event", (k_event<3, int16_t, true>), a.n_reads, 64, st, a);
+    else if (rna && float_input) SGK_LAUNCH("k_event", (k_event<7, float>), a.n_reads, 64, st, a);
     else if (rna) SGK_LAUNCH("k_event", (k_event<7, int16_t>), a.n_reads, 64, st, a);
     else if (float_input) SGK_LAUNCH("k_event", (k_event<3, float>), a.n_reads, 64, st, a);
     else SGK_LAUNCH("k_event", (k_event<3, int16_t>), a.n_reads, 64, st, a);

@@ -220,7 +220,7 @@ int sgk_job_set_event_params(sgk_job_t *j, const sgk_event_params_t *params) {
         j->has_ev_params = false;
         return SGK_OK;
     }
-    if (sgk_event_params_check(params) != SGK_OK) return SGK_ERR_ARG;
+    if (sgk_event_params_route(params) < 0) return SGK_ERR_ARG;  // (the submits route by the same call: sgk_event_param)
     j->ev_params = *params;
     j->has_ev_params = true;
     return SGK_OK;

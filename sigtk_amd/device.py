@@ -102,7 +102,9 @@ class EventArena:
     """Output arena + workspace of sgk_event for one batch shape (allocated once, reused)."""
 
     def __init__(self, b: DeviceReads, params: Optional["api.EventParams"] = None):
-        """`params`: size the workspace for sgk_event_param with these detector parameters as well"""
+        """`params`: size the workspace for sgk_event_param with these detector parameters as well (by their route,
+        api.event_params_route: sgk_event_opt's workspace for a preset and for the presets' kernels with run-time
+        thresholds, the generic kernel's otherwise -- sgk_event_workspace_bytes_param decides)"""
         L = api.load_library()
         dev = b.samples.device
         slots = np.zeros(b.n_reads + 1, dtype=np.int64)
@@ -169,7 +171,8 @@ class EventArena:
 def event(b: DeviceReads, arena: EventArena, rna: int, params: Optional["api.EventParams"] = None) -> None:
     """Enqueue one pass of the event path over the batch on the current stream (async).  With `params` the detector
     takes the caller's parameters (sgk_event_param) and `rna` is ignored; the arena's workspace grows when it was not
-    sized for them."""
+    sized for them.  `params.preset_kernels()` opts in to the presets' kernels with run-time thresholds (windows 3/6 and
+    7/14, threshold2 >= 9); the arena's options (`arena.opt`) apply there as they do to the presets."""
     L = api.load_library()
     view = b.view()
     if params is not None:

@@ -1278,7 +1278,7 @@ static int cmain(int argc, char *argv[], const char *mode_s) {
     /* `ent` has its own front end in the reference (src/ent.c:63-105): only -h/-V (and --no-header) are options,
      * exactly one file argument, no DNA/RNA or pore detection */
     const int is_ent = strcmp(mode_s, "ent") == 0;
-    const char *optstring = is_ent ? "hVt:" : "o:hVnct:";
+    const char *optstring = is_ent ? "hVt:" : "o:hVnct:v:";
     int longindex = 0, c;
     FILE *fp_help = stderr;
     int8_t hdr = 1;
@@ -1286,7 +1286,7 @@ static int cmain(int argc, char *argv[], const char *mode_s) {
     int n_gpus = 1, nthreads = 0, host_decode = 0, host_inflate = 0, batch_set = 0, gpu_text = 0;
     uint64_t aux_slack = 256; /* bytes of room per array column of a zlib record sent to the GPU (load_parse) */
     sgk_event_params_t det;   /* event --detector */
-    int have_det = 0;
+    int have_det = 0, verbosity = 0;   /* -v / --verbose: 4 and up names the detector route of event --detector */
     /* default batch: small (16 M samples) where the GPU stage is short -- a job's buffers are then cheap to set up
      * and the host stages overlap sooner; 64 M for jnn / prefix, whose one-read-per-lane kernels take as long for
      * a small batch as for a large one */
@@ -1304,6 +1304,8 @@ static int cmain(int argc, char *argv[], const char *mode_s) {
             opt.compact = 1;
         } else if (c == 't') {
             nthreads = atoi(optarg);
+        } else if (c == 'v') {
+            verbosity = atoi(optarg);
         } else if (c == 0 && longindex == 4) {
             opt.p_stat = 1;
         } else if (c == 0 && longindex == 7) {
@@ -1438,6 +1440,16 @@ static int cmain(int argc, char *argv[], const char *mode_s) {
      * on the command line, and for the other subtools, the option changes nothing) */
     P.gpu_text = gpu_text && (mode == MODE_PA || mode == MODE_EVENT) && P.n_ids == 0;
     P.ev_params = (have_det && mode == MODE_EVENT) ? &det : NULL;  /* the read kind no longer selects the detector */
+    if (P.ev_params) {
+        /* the presets' kernels with these thresholds wherever the library's domain allows (windows 3/6 or 7/14,
+         * THR2 >= 9); elsewhere the flag is ignored and the generic kernel runs.  The rows do not depend on the route. */
+        det.flags |= SGK_EVENT_PARAMS_PRESET_KERNELS;
+        if (verbosity >= 4) {
+            const int route = sgk_event_params_route(&det);
+            fprintf(stderr, "[event] detector route: %s\n", route == SGK_EVENT_ROUTE_PRESET ? "preset" :
+                    route == SGK_EVENT_ROUTE_PRESET_WINDOWS ? "preset windows" : "generic");
+        }
+    }
     run_pipeline(&P, n_gpus, t_init);
     fflush(stdout);
     b5_close(f);

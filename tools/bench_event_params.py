@@ -7,7 +7,12 @@ bytes.  The generic kernel's events on the presets are compared with sgk_event_o
 every record of every read's used slots) before anything is timed.  One JSON line per batch shape; what
 profiles/event_params.md quotes.
 
-    python tools/bench_event_params.py [--shapes 10000x100000,1000x100000] [--steps 5] [--warmup 1]"""
+The fast route (SGK_EVENT_PARAMS_PRESET_KERNELS: the presets' kernels with run-time thresholds) is timed beside them: per
+preset its numbers moved by one ulp (the preset's work through the <.., RT = true> instances) and one tuned set, each
+against k_event_param on the same set and batch -- after the two routes' counts and records have been compared.
+--no-generic-grid leaves out the off-preset sets of the generic kernel.
+
+    python tools/bench_event_params.py [--shapes 10000x100000,1000x100000] [--steps 5] [--warmup 1] [--no-generic-grid]"""
 import argparse
 import json
 import os
@@ -20,6 +25,15 @@ import torch
 from sigtk_amd import api, device
 
 OFF_PRESET = [(5, 9, 1.4, 3.0, 0.2), (3, 20, 1.4, 2.0, 0.2)]
+#: per preset: a tuned set of the fast domain (the preset's numbers moved by one ulp are formed from the preset)
+TUNED = {0: (3, 6, 1.0, 9.0, 0.1), 1: (7, 14, 1.5, 12.0, 0.5)}
+
+
+def one_ulp_off(rna):
+    """the preset's thresholds and peak height, each one float up: another parameter set, the same work"""
+    p = api.EventParams.preset(rna)
+    up = lambda v: float(np.nextafter(np.float32(v), np.float32(np.inf)))
+    return (p.window_length1, p.window_length2, up(p.threshold1), up(p.threshold2), up(p.peak_height))
 
 
 def used_slots(arena):
@@ -28,6 +42,18 @@ def used_slots(arena):
     idx = torch.arange(arena.n_slots, device=arena.slots.device)
     read = torch.searchsorted(arena.slots, idx, right=True) - 1
     return (idx - arena.slots[read]) < arena.n_events[:n].to(torch.int64)[read]
+
+
+def same_records(x, y, what):
+    """every record of every read's used slots is the same in both arenas; otherwise: where they differ"""
+    used = used_slots(x)
+    bad = torch.nonzero((x.events != y.events).any(dim=1) & used).flatten()
+    if bad.numel() == 0:
+        return
+    reads = torch.unique(torch.searchsorted(x.slots, bad, right=True) - 1)
+    s = int(bad[0].item())
+    raise AssertionError("%s: %d records of %d reads differ (reads %s ...); first at slot %d: %s against %s" % (
+        what, bad.numel(), reads.numel(), reads[:8].tolist(), s, x.events[s].tolist(), y.events[s].tolist()))
 
 
 def timed(fn, steps, warmup):
@@ -50,6 +76,7 @@ def main():
     ap.add_argument("--shapes", default="10000x100000,1000x100000", help="READSxSAMPLES, comma separated")
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--no-generic-grid", action="store_true")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     dev = torch.device("cuda", 0)
@@ -79,7 +106,7 @@ def main():
                                                        "workspace_bytes": int(garena.param_workspace_bytes(b, p)),
                                                        "rerun_chunks": int(gst.n_rerun_passes),
                                                        "ratio_generic_over_preset": round(gmed / med, 2)}
-            if rna == 0:
+            if rna == 0 and not a.no_generic_grid:
                 for q in OFF_PRESET:
                     p2 = api.EventParams(*q)
                     a2 = device.EventArena(b, params=p2)
@@ -91,6 +118,27 @@ def main():
                         "rerun_chunks": int(s2.n_rerun_passes), "overflow": int(s2.n_capacity_overflow),
                         "samples_per_s": round(n_reads * read_len / (m2 * 1e-3), 0)}
                     del a2
+            # the fast route against the generic kernel on the same set and batch
+            for tag, q in (("ulp", one_ulp_off(rna)), ("tuned", TUNED[rna])):
+                pf = api.EventParams(*q, api.SGK_EVENT_PARAMS_PRESET_KERNELS)
+                pg = api.EventParams(*q, api.SGK_EVENT_PARAMS_GENERIC)
+                assert pf.route() == api.SGK_EVENT_ROUTE_PRESET_WINDOWS and pg.route() == api.SGK_EVENT_ROUTE_GENERIC
+                fa = device.EventArena(b, params=pf)
+                device.event(b, fa, rna, params=pf)
+                device.event(b, garena, rna, params=pg)
+                torch.cuda.synchronize()
+                assert torch.equal(fa.n_events, garena.n_events), "fast route: other event counts than the generic kernel's"
+                same_records(fa, garena, "fast route (%s, preset %d) against the generic kernel" % (tag, rna))
+                fmed, fms = timed(lambda: device.event(b, fa, rna, params=pf), a.steps, a.warmup)
+                fst = fa.status()
+                g2, gms2 = timed(lambda: device.event(b, garena, rna, params=pg), a.steps, a.warmup)
+                res["sides"]["rt_%s%d" % (tag, rna)] = {
+                    "params": list(q), "ms": round(fmed, 3), "all_ms": [round(x, 3) for x in fms],
+                    "workspace_bytes": int(fa.param_workspace_bytes(b, pf)), "events": int(fst.n_events_total),
+                    "fallback_reads": int(fst.n_fallback_reads), "rerun_chunks": int(fst.n_rerun_passes),
+                    "rt_over_preset": round(fmed / med, 3), "generic_ms": round(g2, 3),
+                    "generic_all_ms": [round(x, 3) for x in gms2], "generic_over_rt": round(g2 / fmed, 2)}
+                del fa
             del arena, garena, b
             torch.cuda.empty_cache()
         print(json.dumps(res), flush=True)
