@@ -21,7 +21,7 @@ LIB = os.path.join(PKG, "libsigtk_gpu.so")
 CLI = os.path.join(PKG, "sigtk-amd")
 CLI_ASAN = os.path.join(PKG, "sigtk-amd-asan")
 
-EVENT_SOURCES = ["event_launch.hip", "event_whole.hip", "event_seg.hip", "event_multi.hip", "event_fallback.hip", "event_param.hip"]
+EVENT_SOURCES = ["event_plan.hip", "event_launch.hip","event_whole.hip", "event_seg.hip", "event_multi.hip", "event_fallback.hip", "event_param.hip"]
 HIP_SOURCES = ["api.hip", "api_stat.hip", *EVENT_SOURCES, "stat_launch.hip", "stat_lane.hip", "stat_wave.hip", "stat_long.hip", "stat_literal.hip",
                "misc_kernels.hip", "svb_kernels.hip", "sigtext_kernels.hip", "inflate_kernels.hip", "deflate_kernels.hip", "zstd_kernels.hip", "zrec_kernels.hip", "sigraw_kernels.hip", "ent_kernels.hip",
                "qts_kernels.hip", "text_kernels.hip", "slow5_text_kernels.hip", "sref_kernels.hip", "ss_kernels.hip", "job.hip", "shims.hip"]
@@ -82,10 +82,11 @@ def build_lib(force: bool = False, verbose: bool = False) -> str:
     return LIB
 
 
-def build_variant(tag: str, defines, sources=(*EVENT_SOURCES, "api.hip"), verbose: bool = False) -> str:
+def build_variant(tag: str, defines, sources=tuple(EVENT_SOURCES), verbose: bool = False) -> str:
     """A development variant of the library: `sources` recompiled with the given -D flags, everything else taken from
     the shipped build's objects -> sigtk_amd/_variants/libsigtk_gpu_<tag>.so (select it with SIGTK_AMD_LIB=<path>).
-    -DSGK_DEV=1 is the instrumented build of event_args.h (phases switched off per call, per-wave timestamps)."""
+    -DSGK_DEV=1 is the instrumented build of event_args.h (phases switched off per call, per-wave timestamps); the event
+    units are all that read it (event_plan.hip: the options' reserved word, sgk_debug_scratch_offset)."""
     build_lib(verbose=verbose)
     vdir = os.path.join(PKG, "_variants")
     os.makedirs(vdir, exist_ok=True)

@@ -1,5 +1,7 @@
 // event_args.h -- argument block and workspace header of the event kernels.
 #pragma once
+#include <type_traits>
+
 #include "sgk_common.h"
 
 namespace sgk {
@@ -122,7 +124,6 @@ constexpr uint32_t SGK_DEV_RAW_EVENTS = 8;   // builder: event rounds without cr
 constexpr uint32_t SGK_DEV_TRACE = 16;       // k_event: s_memrealtime at wave start / detector end / builder end + HW_ID, XCC_ID
                                              // per workgroup, 32 bytes each, into the fallback scratch (unused when no read is flagged)
 
-
 struct EvSegConfig {
     uint32_t dev;        // SGK_DEV builds: sgk_event_options_t::reserved[0]
     uint32_t seg_len, long_min;
@@ -130,19 +131,26 @@ struct EvSegConfig {
     int multi;  // lanes per short read: 0 = chosen per batch, -1 = off (64 lanes per read), 1 .. 32 = forced
     uint32_t multi_max;  // 0 = default; reads shorter than this (a power of two) count as short
     int tail_split;      // 0 = chosen per batch, -1 = off
-    bool auto_geometry;  // neither segment_len nor long_min was given: event_config_for picks them per batch
+    bool auto_geometry;  // neither segment_len nor long_min was given: event_plan picks them per batch
 };
 EvSegConfig event_config(const sgk_event_options_t *opt);  // null: the defaults
-// the configuration with the long reads' geometry resolved for a batch of these totals and this preset
-EvSegConfig event_config_for(const EvSegConfig &c, uint64_t n_samples, int rna);
-void event_multi_plan(const EvSegConfig &c, uint32_t n_reads, uint64_t n_samples, uint32_t max_read_len, int rna,
-                      bool sorted, uint32_t &multi_lanes, uint32_t &multi_max);
-void event_tail_plan(const EvSegConfig &c, uint32_t n_reads, uint64_t n_samples, uint32_t max_read_len, int rna,
-                     bool packed, uint32_t &split_from, uint32_t &split_seg);
-void event_seg_capacity(const EvSegConfig &c, uint32_t n_reads, uint64_t n_samples, uint32_t max_read_len, int rna,
-                        bool packed, uint32_t &max_segs, uint32_t &max_long);
 
-// workspace carving shared by sgk_event_workspace_bytes and sgk_event
+// ---- the plan of a batch (event_plan.hip): everything the host decides from the batch's totals and the preset, computed
+// once -- sgk_event_plan_opt reports it, the workspace layout takes its capacities, run_event launches it
+struct EvTotals { uint32_t n_reads; uint64_t n_samples; uint32_t max_read_len; int rna; };
+struct EvPlan {
+    uint32_t seg_len, long_min;      // the long reads' geometry, resolved for this batch and preset
+    int lead_override;
+    uint32_t dev;
+    bool ragged, sorted;             // lengths differ enough for a dispatch order (EvArgs::order); ... and launch_event makes one
+    uint32_t multi_lanes, multi_max; // short-read packing
+    uint32_t split_from, split_seg;  // tail split
+    uint32_t max_segs, max_long;     // capacities of the segment lists for THIS preset
+    bool has_long;                   // the batch may hold reads of long_min samples or more
+};
+EvPlan event_plan(const EvSegConfig &c, const EvTotals &t);
+
+// workspace carving shared by sgk_event_workspace_bytes and sgk_event; max_segs / max_long: the larger of both presets' plans
 struct EvWorkspace {
     size_t off_hdr, off_flags, off_list, off_order, off_bitmap, off_segs, off_seg_state, off_longs, off_scratch, total;
     uint32_t max_segs, max_long;
@@ -176,12 +184,45 @@ struct EvParamWorkspace {
     uint32_t n_blocks;
 };
 EvParamWorkspace event_param_workspace_layout(uint32_t n_reads, uint32_t max_read_len);
+int event_params_route(const sgk_event_params_t *p);  // SGK_EVENT_ROUTE_*; `p` has passed sgk_event_params_check
 int launch_event_param(const EvArgs &a, const EvParamArgs &pa, bool float_input, uint32_t n_blocks, hipStream_t st);  // event_launch.hip
+
+// ---- one run function behind every entry point (event_plan.hip) -------------------------------------------------
+struct EvBatch {   // the batch as the kernels see it: an sgk_batch_t, or pA floats laid out like one
+    const void *samples;
+    bool float_input;
+    const uint64_t *offsets;
+    const uint32_t *lengths;
+    const double *dig, *off, *rng;  // null for float (pA) input
+    uint32_t n_reads, max_read_len;
+    uint64_t n_samples;
+};
+inline EvBatch event_batch(const sgk_batch_t &b) {
+    return {b.samples, false, b.offsets, b.lengths, b.digitisation, b.offset, b.range, b.n_reads, b.max_read_len, b.n_samples};
+}
+struct EvArena {   // where the records go, the workspace, the stream
+    const uint64_t *ev_slots;
+    sgk_event_rec_t *events;
+    uint32_t *n_events;
+    void *ws;
+    size_t ws_bytes;
+    void *stream;
+};
+// params null: the preset `rna`; else the parameters are checked first, then take their route, and `rna` is ignored.
+// n_reads == 0 is SGK_OK before any pointer is looked at.
+int run_event(const EvBatch &b, const EvArena &o, int rna, const sgk_event_params_t *params, const sgk_event_options_t *opt);
 
 // ---- one launch per kernel, defined in the unit that holds the kernel (without relocatable device code a kernel is
 // launched from its own translation unit); launch_event is made of these.  rna / float_input select the kernel's
 // <W1, T, RT> instance: detector preset (3: DNA, 7: RNA), sample type (int16_t or float) and where the thresholds come
-// from (rt: the arguments).
+// from (rt: the arguments).  event_instance is that selection, once: f(W1, T, RT) gets the three as tag values, an
+// integral_constant, a value of the sample type and a bool_constant.
+template <typename F>
+int event_instance(int rna, bool float_input, bool rt, F f) {
+    const auto with_t = [&](auto w1, auto t) { return rt ? f(w1, t, std::true_type()) : f(w1, t, std::false_type()); };
+    const auto with_w1 = [&](auto w1) { return float_input ? with_t(w1, float()) : with_t(w1, int16_t()); };
+    return rna ? with_w1(std::integral_constant<int, 7>()) : with_w1(std::integral_constant<int, 3>());
+}
 int launch_k_seg_plan(hipStream_t st, const EvArgs &a);                                        // event_seg.hip
 int launch_k_event_seg(int rna, bool float_input, hipStream_t st, const EvArgs &a, bool rt = false);            // event_seg.hip
 int launch_k_event(int rna, bool float_input, hipStream_t st, const EvArgs &a, bool rt = false);                // event_whole.hip

@@ -60,6 +60,8 @@
 //                      persistent grid with per-workgroup prefix arrays, launched by launch_event_param.
 //   event_launch.hip   launch_event: order, plan, side streams, the launches; it holds no kernel and launches them through
 //                      the launch_k_* functions of event_args.h, one per kernel, each defined next to its kernel.
+//   event_plan.hip     host only, in front of launch_event: options -> configuration, the batch's plan (event_plan), both
+//                      workspace layouts, the parameters' route, and run_event behind every entry point of api.hip.
 #pragma once
 #include "event_args.h"
 #include "sgk_common.h"

@@ -50,15 +50,10 @@ __global__ __launch_bounds__(64) void k_event_fallback(EvArgs a) {
 }
 
 int launch_k_event_fallback(int rna, bool float_input, uint32_t n_fb_blocks, hipStream_t st, const EvArgs &a, bool rt) {
-    if (rt && rna && float_input) SGK_LAUNCH("k_event_fallback", (k_event_fallback<7, float, true>), n_fb_blocks, 64, st, a);
-    else if (rt && rna) SGK_LAUNCH("k_event_fallback", (k_event_fallback<7, int16_t, true>), n_fb_blocks, 64, st, a);
-    else if (rt && float_input) SGK_LAUNCH("k_event_fallback", (k_event_fallback<3, float, true>), n_fb_blocks, 64, st, a);
-    else if (rt) SGK_LAUNCH("k_event_fallback", (k_event_fallback<3, int16_t, true>), n_fb_blocks, 64, st, a);
-    else if (rna && float_input) SGK_LAUNCH("k_event_fallback", (k_event_fallback<7, float>), n_fb_blocks, 64, st, a);
-    else if (rna) SGK_LAUNCH("k_event_fallback", (k_event_fallback<7, int16_t>), n_fb_blocks, 64, st, a);
-    else if (float_input) SGK_LAUNCH("k_event_fallback", (k_event_fallback<3, float>), n_fb_blocks, 64, st, a);
-    else SGK_LAUNCH("k_event_fallback", (k_event_fallback<3, int16_t>), n_fb_blocks, 64, st, a);
-    return SGK_OK;
+    return event_instance(rna, float_input, rt, [&](auto w1, auto t, auto r) -> int {
+        SGK_LAUNCH("k_event_fallback", (k_event_fallback<decltype(w1)::value, decltype(t), decltype(r)::value>), n_fb_blocks, 64, st, a);
+        return SGK_OK;
+    });
 }
 
 }  // namespace sgk

@@ -44,15 +44,10 @@ __global__ __launch_bounds__(64, (W1 == 3 ? DET_WAVES_DNA : DET_WAVES_RNA)) void
 int launch_k_event_multi(int rna, bool float_input, hipStream_t st, const EvArgs &a, bool rt) {
     const uint32_t per_wave = 64u / a.multi_lanes;
     const uint32_t grid = (a.n_reads + per_wave - 1) / per_wave;
-    if (rt && rna && float_input) SGK_LAUNCH("k_event_multi", (k_event_multi<7, float, true>), grid, 64, st, a);
-    else if (rt && rna) SGK_LAUNCH("k_event_multi", (k_event_multi<7, int16_t, true>), grid, 64, st, a);
-    else if (rt && float_input) SGK_LAUNCH("k_event_multi", (k_event_multi<3, float, true>), grid, 64, st, a);
-    else if (rt) SGK_LAUNCH("k_event_multi", (k_event_multi<3, int16_t, true>), grid, 64, st, a);
-    else if (rna && float_input) SGK_LAUNCH("k_event_multi", (k_event_multi<7, float>), grid, 64, st, a);
-    else if (rna) SGK_LAUNCH("k_event_multi", (k_event_multi<7, int16_t>), grid, 64, st, a);
-    else if (float_input) SGK_LAUNCH("k_event_multi", (k_event_multi<3, float>), grid, 64, st, a);
-    else SGK_LAUNCH("k_event_multi", (k_event_multi<3, int16_t>), grid, 64, st, a);
-    return SGK_OK;
+    return event_instance(rna, float_input, rt, [&](auto w1, auto t, auto r) -> int {
+        SGK_LAUNCH("k_event_multi", (k_event_multi<decltype(w1)::value, decltype(t), decltype(r)::value>), grid, 64, st, a);
+        return SGK_OK;
+    });
 }
 
 }  // namespace sgk

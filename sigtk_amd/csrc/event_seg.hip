@@ -276,15 +276,10 @@ int launch_k_seg_plan(hipStream_t st, const EvArgs &a) {
     return SGK_OK;
 }
 int launch_k_event_seg(int rna, bool float_input, hipStream_t st, const EvArgs &a, bool rt) {
-    if (rt && rna && float_input) SGK_LAUNCH("k_event_seg", (k_event_seg<7, float, true>), a.max_segs, 64, st, a);
-    else if (rt && rna) SGK_LAUNCH("k_event_seg", (k_event_seg<7, int16_t, true>), a.max_segs, 64, st, a);
-    else if (rt && float_input) SGK_LAUNCH("k_event_seg", (k_event_seg<3, float, true>), a.max_segs, 64, st, a);
-    else if (rt) SGK_LAUNCH("k_event_seg", (k_event_seg<3, int16_t, true>), a.max_segs, 64, st, a);
-    else if (rna && float_input) SGK_LAUNCH("k_event_seg", (k_event_seg<7, float>), a.max_segs, 64, st, a);
-    else if (rna) SGK_LAUNCH("k_event_seg", (k_event_seg<7, int16_t>), a.max_segs, 64, st, a);
-    else if (float_input) SGK_LAUNCH("k_event_seg", (k_event_seg<3, float>), a.max_segs, 64, st, a);
-    else SGK_LAUNCH("k_event_seg", (k_event_seg<3, int16_t>), a.max_segs, 64, st, a);
-    return SGK_OK;
+    return event_instance(rna, float_input, rt, [&](auto w1, auto t, auto r) -> int {
+        SGK_LAUNCH("k_event_seg", (k_event_seg<decltype(w1)::value, decltype(t), decltype(r)::value>), a.max_segs, 64, st, a);
+        return SGK_OK;
+    });
 }
 
 }  // namespace sgk

@@ -59,15 +59,10 @@ __global__ __launch_bounds__(64, (W1 == 3 ? DET_WAVES_DNA : DET_WAVES_RNA)) void
 }
 
 int launch_k_event(int rna, bool float_input, hipStream_t st, const EvArgs &a, bool rt) {
-    if (rt && rna && float_input) SGK_LAUNCH("k_event", (k_event<7, float, true>), a.n_reads, 64, st, a);
-    else if (rt && rna) SGK_LAUNCH("k_event", (k_event<7, int16_t, true>), a.n_reads, 64, st, a);
-    else if (rt && float_input) SGK_LAUNCH("k_event", (k_event<3, float, true>), a.n_reads, 64, st, a);
-    else if (rt) SGK_LAUNCH("k_event", (k_event<3, int16_t, true>), a.n_reads, 64, st, a);
-    else if (rna && float_input) SGK_LAUNCH("k_event", (k_event<7, float>), a.n_reads, 64, st, a);
-    else if (rna) SGK_LAUNCH("k_event", (k_event<7, int16_t>), a.n_reads, 64, st, a);
-    else if (float_input) SGK_LAUNCH("k_event", (k_event<3, float>), a.n_reads, 64, st, a);
-    else SGK_LAUNCH("k_event", (k_event<3, int16_t>), a.n_reads, 64, st, a);
-    return SGK_OK;
+    return event_instance(rna, float_input, rt, [&](auto w1, auto t, auto r) -> int {
+        SGK_LAUNCH("k_event", (k_event<decltype(w1)::value, decltype(t), decltype(r)::value>), a.n_reads, 64, st, a);
+        return SGK_OK;
+    });
 }
 
 }  // namespace sgk

@@ -49,7 +49,7 @@ def test_library_is_reentrant_by_construction():
     a, b = api.EventOptions(), api.EventOptions()
     a.segment_len, a.long_min = 4096, 10000
     pa_, pb_ = api.event_plan(10, 10 * 300000, 300000, 0, a), api.event_plan(10, 10 * 300000, 300000, 0, b)
-    assert (pa_.segment_len, pb_.segment_len) == (4096, 65536)   # (the default geometry of a batch this small, api.hip: event_config_for)
+    assert (pa_.segment_len, pb_.segment_len) == (4096, 65536)   # (the default geometry of a batch this small, event_plan.hip: event_config_for)
 
 
 def test_no_cpu_fallback_without_gpu():

@@ -41,7 +41,7 @@ def test_defaults_and_no_long_reads(lib):
     from sigtk_amd import api
     q = api.EventPlan()
     assert lib.sgk_event_plan_opt(10, 10 * 5000, 5000, 0, None, C.byref(q)) == 0 and q.segment_len == 65536
-    # the long reads' geometry follows the batch (api.hip: event_config_for): long_min = 0.9 x the batch's samples per
+    # the long reads' geometry follows the batch (event_plan.hip: event_config_for): long_min = 0.9 x the batch's samples per
     # wavefront slot, between 131 072 and 262 144, segments of half of it; an explicit segment_len / long_min is kept
     assert [(plan(lib, [100000] * n)[0].long_min, plan(lib, [100000] * n)[0].segment_len) for n in (3000, 6000, 10000)] == \
         [(131072, 65536), (176128, 88064), (262144, 131072)]
@@ -95,7 +95,7 @@ def test_lanes_for_short_reads(lib):
 def test_tail_split(lib):
     """a batch of fewer than 8 rounds of wavefronts (256 CUs x 4 SIMDs x 3 waves with the DNA preset, x 2 with RNA
     parameters; without a GPU the plan assumes 256 CUs): the reads of its last, partial round are cut into segments where
-    that was measured to pay (api.hip: event_tail_plan, profiles/r05_tail_split_sweep.txt) -- a batch of at most 0.55 of a
+    that was measured to pay (event_plan.hip: event_tail_plan, profiles/r05_tail_split_sweep.txt) -- a batch of at most 0.55 of a
     round (RNA preset: 7 / 8), a last round of at most a quarter of a round behind one full round, a sixth behind more
     (RNA preset: never); a cut read costs 1.5 x a whole one"""
     p, _ = plan(lib, [100000] * 9300)                   # 9 300 = 3 x 3072 + 84: the last 84 reads, 16 384-sample segments

@@ -157,7 +157,7 @@ def test_long_reads_in_noise_stay_on_the_fast_path(gpu, memo, cat, longs, option
 
 @pytest.mark.parametrize("rna", [0, 1])
 def test_tail_split_cuts_the_long_reads(gpu, memo, cat, longs, options, rna):
-    """the tail split takes no batch whose reads are shorter than 32 768 samples on average (api.hip: event_tail_plan), so
+    """the tail split takes no batch whose reads are shorter than 32 768 samples on average (event_plan.hip: event_tail_plan), so
     on the whole catalogue tail_split = n changes nothing; the five reads from 32 767 samples on are cut, all of them"""
     cases = [k for k in cat if k.raw.size >= 32767]
     reads = [k.raw for k in cases]
@@ -427,3 +427,72 @@ def test_cli_is_byte_identical_to_the_reference(gpu, cat, tmp_path, kind):
             assert p.returncode == 0, p.stderr.decode()[-2000:]
             assert p.stdout == want, "%s options %s: first differing row %r" % (
                 fname, opts, next((a, b) for a, b in zip(p.stdout.split(b"\n") + [b""], want.split(b"\n")) if a != b))
+
+
+def _three_reads(cat, rna):
+    """the three longest catalogue reads of this preset with at most 3 000 samples"""
+    reads = sorted((k.raw for k in cat if rna in k.rna and k.raw.size <= 3000), key=lambda x: -x.size)[:3]
+    assert len(reads) == 3 and reads[-1].size >= 1000
+    return reads
+
+
+def _opt_records(gpu, reads, rna):
+    """sgk_event_opt with the default options on `reads` -> (the batch, per read its records as an int32 array [k, 4])"""
+    import torch
+    from sigtk_amd import device
+    b = device.upload_reads(reads, *_scal(len(reads)), torch.device("cuda", 0))
+    arena = device.EventArena(b)
+    device.event(b, arena, rna)
+    torch.cuda.synchronize()
+    assert arena.status().n_capacity_overflow == 0
+    recs = [arena.events[int(arena.slots_host[r]):int(arena.slots_host[r]) + int(arena.n_events[r].item())].cpu().numpy()
+            for r in range(len(reads))]
+    assert all(x.shape[0] >= 1 for x in recs) and sum(x.shape[0] for x in recs) > 10   # (one of the reads may be flat)
+    return b, recs
+
+
+@pytest.mark.parametrize("rna", [0, 1])
+def test_plain_sgk_event_equals_sgk_event_opt(gpu, cat, rna):
+    """sgk_event (no options argument) has no other caller in the suite: its records on three catalogue reads are
+    sgk_event_opt's with the default options, bit for bit"""
+    import ctypes as C
+    import torch
+    from sigtk_amd import device
+    b, want = _opt_records(gpu, _three_reads(cat, rna), rna)
+    L = gpu.load_library()
+    arena = device.EventArena(b)
+    assert arena.ws_bytes == L.sgk_event_workspace_bytes(b.n_reads, b.n_samples, b.max_read_len)
+    arena.events.fill_(-1)
+    arena.n_events.fill_(-1)
+    view = b.view()
+    gpu.check(L.sgk_event(C.byref(view), rna, arena.slots.data_ptr(), arena.events.data_ptr(), arena.n_events.data_ptr(),
+                          arena.ws.data_ptr(), arena.ws_bytes, device._stream_ptr()), "sgk_event")
+    torch.cuda.synchronize()
+    for r, w in enumerate(want):
+        s = int(arena.slots_host[r])
+        assert int(arena.n_events[r].item()) == w.shape[0]
+        assert np.array_equal(arena.events[s:s + w.shape[0]].cpu().numpy(), w), "read %d" % r
+
+
+@pytest.mark.parametrize("rna", [0, 1])
+def test_plain_sgk_event_host_equals_sgk_event_opt(gpu, cat, rna):
+    """sgk_event_host (no options argument) likewise: host arrays in, the four host arrays out, against sgk_event_opt's
+    records on the same three reads, bit for bit"""
+    import ctypes as C
+    reads = _three_reads(cat, rna)
+    _, want = _opt_records(gpu, reads, rna)
+    L = gpu.load_library()
+    hb = gpu._HB(reads, *E.SCALE)
+    ev = gpu.EventsHost()
+    gpu.check(L.sgk_event_host(C.byref(hb.c), rna, C.byref(ev)), "sgk_event_host")
+    try:
+        offs = gpu._np_from(ev.ev_offsets, len(reads) + 1, np.uint64)
+        tot = int(offs[-1])
+        cols = [gpu._np_from(p, tot, t) for p, t in ((ev.start, np.uint32), (ev.length, np.uint32), (ev.mean, np.float32),
+                                                     (ev.stdv, np.float32))]
+    finally:
+        L.sgk_events_host_free(C.byref(ev))
+    assert offs.tolist() == np.concatenate([[0], np.cumsum([w.shape[0] for w in want])]).tolist()
+    for r, w in enumerate(want):
+        for c, col in enumerate(cols):
+            assert np.array_equal(col[int(offs[r]):int(offs[r + 1])].view(np.int32), w[:, c]), "read %d column %d" % (r, c)

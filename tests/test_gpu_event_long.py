@@ -28,7 +28,7 @@ def test_long_reads_default_segments(gpu, oracle, rna):
     reads, dig, off, rng = gpu.synth_reads_host(len(lens), lens, seed=21 + rna, kind=rna)
     got, st = gpu.event(reads, dig, off, rng, rna)
     _check_events(oracle, reads, dig, off, rng, rna, got)
-    # (a batch this small: reads from 131 072 samples on are cut into segments of 65 536, api.hip: event_config_for; and it
+    # (a batch this small: reads from 131 072 samples on are cut into segments of 65 536, event_plan.hip: event_config_for; and it
     # is a partial round of waves: the tail split cuts the 100 000-sample read as well, into segments of 82 944 samples =
     # ceil(mean / 8) rounded up to 1024)
     assert st.n_split_reads == 6 and st.n_segments == 11 + 5 + 4 + 4 + 2 + 46
@@ -164,7 +164,7 @@ def test_flat_signal_costs_no_more_than_its_length(gpu, oracle, configure):
 
 @pytest.mark.parametrize("rna", [0, 1])
 def test_tail_split_rule_is_no_cliff(gpu, rna):
-    """VERDICT r04 task 8b: the tail split (api.hip: event_tail_plan -- the reads of a batch's last, partial round of
+    """VERDICT r04 task 8b: the tail split (event_plan.hip: event_tail_plan -- the reads of a batch's last, partial round of
     wavefronts are cut into segments iff the batch is at most 0.55 of a round, or that round at most a quarter of a round
     behind one full round, a sixth behind more) is a measured choice (tools/tail_sweep.py ->
     profiles/r05_tail_split_sweep.txt).  Either side of every cut the batch is timed with and without the split: what the
@@ -219,7 +219,7 @@ def test_tail_split_rule_is_no_cliff(gpu, rna):
 
 
 def test_long_read_threshold_is_no_cliff(gpu):
-    """From what length on a read is shared by several wavefronts follows the batch (api.hip: event_config_for): 262 144
+    """From what length on a read is shared by several wavefronts follows the batch (event_plan.hip: event_config_for): 262 144
     samples (segments of 131 072) in a batch of 10^9 samples, 131 072 (65 536) in one of 3 x 10^8.  Both geometries are
     timed on both kinds of batch: what the rule picks may be at most 1.10 x the other (+ 30 us)."""
     import torch

@@ -130,7 +130,7 @@ def test_a_read_that_is_short_and_long_belongs_to_its_segments(gpu, oracle, lane
 @pytest.mark.parametrize("rna", [0, 1])
 def test_packing_threshold_is_no_cliff(gpu, rna):
     """VERDICT r04 task 8b: reads under short_max samples (16 384; 65 536 with the RNA preset) share wavefronts in large
-    batches (api.hip: event_multi_plan).  Just under and just over that length the batch is timed packed and one read
+    batches (event_plan.hip: event_multi_plan).  Just under and just over that length the batch is timed packed and one read
     per wavefront: what the rule picks may be at most 1.10 x the other (+ 30 us)."""
     import torch
     from sigtk_amd import device

@@ -2,7 +2,7 @@
 """development (VERDICT r04 task 1a / 1b): where k_event's time and instructions go, by phase, and what the first round
 of waves does differently -- with the instrumented build of the library:
 
-    tools/build_variant.sh dev -DSGK_DEV=1          (recompiles the event units, csrc/event_*.hip, and api.hip)
+    tools/build_variant.sh dev -DSGK_DEV=1          (recompiles the event units, csrc/event_*.hip)
     SIGTK_AMD_LIB=sigtk_amd/_variants/libsigtk_gpu_dev.so python tools/event_phases.py [--reads 10000] [--rna 0] \
             [--trace out.npz] [--steps 5]
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Tail split on / off over batch sizes, whole sgk_event calls of the shipped library (HIP events around the call on the
-caller's stream, best of 5): what api.hip: event_tail_plan's rule is fitted to, and what
+caller's stream, best of 5): what event_plan.hip: event_tail_plan's rule is fitted to, and what
 tests/test_gpu_event_long.py::test_tail_split_rule_is_no_cliff guards.
     python tools/tail_sweep.py [--rna 0] > profiles/<round>_tail_split_sweep.txt"""
 import argparse
