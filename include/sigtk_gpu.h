@@ -1117,6 +1117,60 @@ int16_t sgk_mediani16(const int16_t *x, int n);
 /* SGK_OK, or why the last shim call of this thread returned NULL / {-1,-1} / NaN */
 int sgk_shim_status(void);
 
+/* ---- jnn and prefix with caller-supplied segmenter parameters (additive to 0.2.3) ------------------------------------
+ * The compiled-in constants of the reference's segmenters (src/jnn.h) as arguments: jnn_param_t for jnn, jnnv2_param_t
+ * for the adaptor finder, and for find_polya its jnn_param_t plus the band of src/cfunc.c:191,
+ * top = (m_a + shift) + band, bot = (m_a + shift) - band (presets 30 and 20; one float rounding per operator).  The
+ * results are, bit for bit, those of the reference's own steps with these numbers.  Outside the domain every entry
+ * returns SGK_ERR_ARG and launches nothing (DESIGN.md 3.17 has each bound's reason):
+ *   jnn      32 <= window <= 2^24 (from 32 up sgk_jnn_slots_for bounds a read's segments), corrector >= 1, error >= 0,
+ *            seg_dist >= 0, stall_len finite and >= 0, std_scale finite; std_scale <= 0 means the fixed top / bot,
+ *            which may be anything, NaN included.
+ *   adaptor  2 <= window <= 13 981 (below 2 the reference reads current[-1]; 13 981 is the largest window whose float
+ *            running total 1200 * window <= 2^24 is an exact integer), lo_thresh >= 1, hi_thresh >= lo_thresh,
+ *            seg_dist >= 0, std_scale finite; stall_len is ignored, as the reference ignores it.
+ *   polyA    corrector, seg_dist, window, stall_len, error as for jnn; shift and band finite, band >= 0.
+ * Routes (sgk_prefix_route): an adaptor set equal to a preset (JNNV2_RNA_R9_ADAPTOR or JNNV2_RNA_RNA004_ADAPTOR) takes
+ * sgk_prefix's kernels; anything else, and everything with SGK_PREFIX_PARAMS_GENERIC, takes k_adaptor_param: one
+ * wavefront per read, any window of the domain, any read length, no long-read split -- a read of 10^6 samples is slow
+ * and right.  A polyA set equal to the preset takes sgk_prefix's kernels; any other set with stall_len == 1 and error <
+ * corrector the same wave kernel with the set as an argument, the rest the lane-per-read kernel with the set as an
+ * argument.  sgk_jnn_param routes as sgk_jnn_raw does: the wave kernel where error < corrector, error <= 31 and
+ * window >= 128, else the lane-per-read kernel. */
+#define SGK_PREFIX_PARAMS_GENERIC 1u       /* flags: k_adaptor_param even for a preset (tests, measurements) */
+#define SGK_PREFIX_ROUTE_ADAPTOR_PARAM 1   /* sgk_prefix_route, bit set: k_adaptor_param */
+#define SGK_PREFIX_ROUTE_POLYA_WAVE_PARAM 2 /* the parametrised k_polya_wave */
+#define SGK_PREFIX_ROUTE_POLYA_LANE_PARAM 4 /* the parametrised k_polya */
+#define SGK_ADAPTOR_WINDOW_MAX 13981
+typedef struct sgk_prefix_params {
+    sgk_jnnv2_param_t adaptor; /* 24 bytes */
+    sgk_jnn_param_t polya;     /* 32 bytes; std_scale, top, bot are not used: the thresholds come from shift / band */
+    float shift, band;
+    uint32_t flags, reserved;
+} sgk_prefix_params_t; /* 72 bytes */
+/* host only: the sets sgk_prefix(rna, pore) uses, flags 0 */
+int sgk_prefix_params_preset(int rna, int pore, sgk_prefix_params_t *out);
+/* host only: SGK_OK inside the domain above, else SGK_ERR_ARG */
+int sgk_jnn_params_check(const sgk_jnn_param_t *p);
+int sgk_prefix_params_check(const sgk_prefix_params_t *p);
+/* host only: the SGK_PREFIX_ROUTE_* bits these parameters take (0: sgk_prefix's kernels); SGK_ERR_ARG outside the domain */
+int sgk_prefix_route(const sgk_prefix_params_t *p);
+/* sgk_jnn_opt / sgk_prefix_opt with the caller's parameters; workspaces as sgk_jnn / sgk_prefix_workspace_bytes */
+int sgk_jnn_param(const sgk_batch_t *batch, const sgk_jnn_param_t *p, const uint64_t *seg_slots, int32_t *seg_x,
+                  int32_t *seg_y, uint32_t *n_segs, void *workspace, size_t workspace_bytes, void *stream,
+                  const sgk_stat_options_t *opt);
+int sgk_prefix_param(const sgk_batch_t *batch, int rna, const sgk_prefix_params_t *p, sgk_prefix_rec_t *out,
+                     void *workspace, size_t workspace_bytes, void *stream, const sgk_stat_options_t *opt);
+/* per read: jnnv2 with any window of the domain (sgk_jnnv2 keeps refusing all but 2000), on k_adaptor_param;
+ * find_polya on pA samples with the caller's set, top and bot as given */
+sgk_jnn_pair_t sgk_jnnv2_param(const int16_t *sig, int64_t nsample, sgk_jnnv2_param_t param);
+sgk_jnn_pair_t sgk_find_polya_param(const float *raw, int64_t nsample, float top, float bot, sgk_jnn_param_t param);
+/* Segmenter parameters of the job's SGK_TOOL_JNN / SGK_TOOL_PREFIX submits (copied).  NULL: back to the presets. */
+int sgk_job_set_jnn_params(sgk_job_t *job, const sgk_jnn_param_t *params);
+int sgk_job_set_prefix_params(sgk_job_t *job, const sgk_prefix_params_t *params);
+/* tests: out[i] = the quotient k_adaptor_param forms for the rolling total i, 0 <= i < n (device pointer) */
+int sgk_debug_roll_means(int window, uint32_t n, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -354,6 +354,10 @@ ABI_SYMBOLS = [
     "sgk_ss_pipe_create", "sgk_ss_pipe_destroy", "sgk_ss_pipe_begin", "sgk_ss_pipe_submit", "sgk_ss_pipe_wait",
     # per-read shims with the reference's signatures (csrc/shims.hip)
     "sgk_jnn_raw", "sgk_jnn_pa", "sgk_jnnv2", "sgk_find_adaptor", "sgk_find_polya",
+    # jnn / prefix with caller-supplied segmenter parameters (csrc/stat_param.hip, api_stat.hip)
+    "sgk_prefix_params_preset", "sgk_jnn_params_check", "sgk_prefix_params_check", "sgk_prefix_route", "sgk_jnn_param",
+    "sgk_prefix_param", "sgk_jnnv2_param", "sgk_find_polya_param", "sgk_job_set_jnn_params", "sgk_job_set_prefix_params",
+    "sgk_debug_roll_means",
     "sgk_meanf", "sgk_meani16", "sgk_stdvf", "sgk_stdvi16", "sgk_medianf", "sgk_mediani16", "sgk_shim_status",
 ]
 
@@ -736,6 +740,71 @@ class Jnnv2Param(C.Structure):  # jnnv2_param_t, src/jnn.h:74-81
                 ("hi_thresh", C.c_int), ("lo_thresh", C.c_int)]
 
 
+PREFIX_PARAMS_GENERIC = 1
+PREFIX_ROUTE_ADAPTOR_PARAM, PREFIX_ROUTE_POLYA_WAVE_PARAM, PREFIX_ROUTE_POLYA_LANE_PARAM = 1, 2, 4
+ADAPTOR_WINDOW_MAX = 13981
+
+
+class PrefixParams(C.Structure):   # sgk_prefix_params_t: the adaptor set, the polyA set, the band of src/cfunc.c:191
+    _fields_ = [("adaptor", Jnnv2Param), ("polya", JnnParam), ("shift", C.c_float), ("band", C.c_float),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+    @classmethod
+    def preset(cls, rna: int = 1, pore: int = 0) -> "PrefixParams":
+        p = cls()
+        check(_param_lib().sgk_prefix_params_preset(int(rna), int(pore), C.byref(p)), "sgk_prefix_params_preset")
+        return p
+
+    def route(self) -> int:
+        """PREFIX_ROUTE_* bits these parameters take (sgk_prefix_route); raises when they are out of domain"""
+        rc = int(_param_lib().sgk_prefix_route(C.byref(self)))
+        if rc < 0:
+            check(rc, "sgk_prefix_route")
+        return rc
+
+
+def _param_lib():
+    L = load_library()
+    if not getattr(L, "_segmenter_params_bound", False):
+        PP, JP = C.POINTER(PrefixParams), C.POINTER(JnnParam)
+        L.sgk_prefix_params_preset.argtypes = [C.c_int, C.c_int, PP]
+        L.sgk_prefix_params_check.argtypes = [PP]
+        L.sgk_prefix_route.argtypes = [PP]
+        L.sgk_jnn_params_check.argtypes = [JP]
+        L.sgk_jnn_param.argtypes = [C.POINTER(Batch), JP] + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p, C.c_void_p]
+        L.sgk_prefix_param.argtypes = [C.POINTER(Batch), C.c_int, PP, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.sgk_job_set_jnn_params.argtypes = [C.c_void_p, JP]
+        L.sgk_job_set_prefix_params.argtypes = [C.c_void_p, PP]
+        L.sgk_debug_roll_means.argtypes = [C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
+        for f in ("sgk_prefix_params_preset", "sgk_prefix_params_check", "sgk_prefix_route", "sgk_jnn_params_check", "sgk_jnn_param",
+                  "sgk_prefix_param", "sgk_job_set_jnn_params", "sgk_job_set_prefix_params", "sgk_debug_roll_means"):
+            getattr(L, f).restype = C.c_int
+        L.sgk_jnnv2_param.restype = JnnPair
+        L.sgk_jnnv2_param.argtypes = [C.c_void_p, C.c_int64, Jnnv2Param]
+        L.sgk_find_polya_param.restype = JnnPair
+        L.sgk_find_polya_param.argtypes = [C.c_void_p, C.c_int64, C.c_float, C.c_float, JnnParam]
+        L._segmenter_params_bound = True
+    return L
+
+
+def shim_jnnv2_param(raw, param: Jnnv2Param):
+    """jnnv2 with any window of the domain (k_adaptor_param) -> ((x, y), shim status)"""
+    L = _param_lib()
+    _shim_lib()
+    raw = np.ascontiguousarray(raw, dtype=np.int16)
+    p = L.sgk_jnnv2_param(raw.ctypes.data, raw.size, param)
+    return (int(p.x), int(p.y)), L.sgk_shim_status()
+
+
+def shim_find_polya_param(pa, top: float, bot: float, param: JnnParam):
+    L = _param_lib()
+    _shim_lib()
+    pa = np.ascontiguousarray(pa, dtype=np.float32)
+    p = L.sgk_find_polya_param(pa.ctypes.data, pa.size, top, bot, param)
+    check(L.sgk_shim_status(), "sgk_find_polya_param")
+    return int(p.x), int(p.y)
+
+
 def _shim_lib():
     L = load_library()
     if not getattr(L, "_shims_bound", False):
@@ -861,6 +930,16 @@ class Job:
         """detector parameters of the job's SGK_TOOL_EVENT submits from now on (copied); None: the presets by `rna`"""
         check(self.L.sgk_job_set_event_params(self.h, C.byref(params) if params is not None else None),
               "sgk_job_set_event_params")
+
+    def set_jnn_params(self, params: "JnnParam" = None):
+        """segmenter parameters of the job's jnn submits from now on (copied); None: the presets by `rna`"""
+        check(_param_lib().sgk_job_set_jnn_params(self.h, C.byref(params) if params is not None else None),
+              "sgk_job_set_jnn_params")
+
+    def set_prefix_params(self, params: "PrefixParams" = None):
+        """adaptor / polyA parameters of the job's prefix submits from now on (copied); None: the presets by `pore`"""
+        check(_param_lib().sgk_job_set_prefix_params(self.h, C.byref(params) if params is not None else None),
+              "sgk_job_set_prefix_params")
 
     def close(self):
         if self.h:

@@ -76,8 +76,9 @@ int sgk_stat_pa(const sgk_batch_t *b, sgk_stat_rec_t *out, float *pa_out, void *
     return sgk_stat_pa_opt(b, out, pa_out, ws, ws_bytes, stream, nullptr);
 }
 
-int sgk_jnn_opt(const sgk_batch_t *b, int rna, const uint64_t *seg_slots, int32_t *seg_x, int32_t *seg_y,
-                uint32_t *n_segs, void *ws, size_t ws_bytes, void *stream, const sgk_stat_options_t *opt) {
+// the one body of sgk_jnn_opt (the preset by `rna`) and sgk_jnn_param (the caller's set, checked)
+static int jnn_batch(const sgk_batch_t *b, const JnnP &p, const uint64_t *seg_slots, int32_t *seg_x, int32_t *seg_y, uint32_t *n_segs,
+                     void *ws, size_t ws_bytes, void *stream, const sgk_stat_options_t *opt) {
     int rc = check_batch(b);
     if (rc != SGK_OK) return rc;
     if (b->n_reads == 0) return SGK_OK;
@@ -93,7 +94,12 @@ int sgk_jnn_opt(const sgk_batch_t *b, int rna, const uint64_t *seg_slots, int32_
     a.err_count = static_cast<uint32_t *>(ws);
     if ((rc = prepare_order(a, ws, ws_bytes, static_cast<hipStream_t>(stream))) != SGK_OK) return rc;
     if ((rc = prepare_long(a, ws, ws_bytes, opt ? opt->long_min : 0, LC_AUTO_DIV_JNN, static_cast<hipStream_t>(stream))) != SGK_OK) return rc;
-    return launch_jnn(a, jnn_preset(rna), static_cast<hipStream_t>(stream));
+    return launch_jnn(a, p, static_cast<hipStream_t>(stream));
+}
+
+int sgk_jnn_opt(const sgk_batch_t *b, int rna, const uint64_t *seg_slots, int32_t *seg_x, int32_t *seg_y,
+                uint32_t *n_segs, void *ws, size_t ws_bytes, void *stream, const sgk_stat_options_t *opt) {
+    return jnn_batch(b, jnn_preset(rna), seg_slots, seg_x, seg_y, n_segs, ws, ws_bytes, stream, opt);
 }
 
 int sgk_jnn(const sgk_batch_t *b, int rna, const uint64_t *seg_slots, int32_t *seg_x, int32_t *seg_y,
@@ -101,8 +107,10 @@ int sgk_jnn(const sgk_batch_t *b, int rna, const uint64_t *seg_slots, int32_t *s
     return sgk_jnn_opt(b, rna, seg_slots, seg_x, seg_y, n_segs, ws, ws_bytes, stream, nullptr);
 }
 
-int sgk_prefix_opt(const sgk_batch_t *b, int rna, int pore, sgk_prefix_rec_t *out, void *ws, size_t ws_bytes,
-                   void *stream, const sgk_stat_options_t *opt) {
+// the one body of sgk_prefix_opt (the presets by `pore`: window 2000, today's launchers, poly == nullptr) and
+// sgk_prefix_param (the caller's sets by their route)
+static int prefix_batch(const sgk_batch_t *b, int rna, const AdaptP &ap, int window, bool generic, const PolyP *poly,
+                        sgk_prefix_rec_t *out, void *ws, size_t ws_bytes, void *stream, const sgk_stat_options_t *opt) {
     int rc = check_batch(b);
     if (rc != SGK_OK) return rc;
     if (b->n_reads == 0) return SGK_OK;
@@ -111,15 +119,109 @@ int sgk_prefix_opt(const sgk_batch_t *b, int rna, int pore, sgk_prefix_rec_t *ou
     a.kernels = opt ? opt->kernels : 0;
     a.long_fault = opt ? opt->debug_fault : 0u;
     a.prefix = out;
+    // (k_adaptor_param has no long-read split: the long reads' header is cleared and nothing is listed)
+    const int32_t long_min = (generic || window != 2000) ? -1 : (opt ? opt->long_min : 0);
     if ((rc = prepare_order(a, ws, ws_bytes, static_cast<hipStream_t>(stream))) != SGK_OK) return rc;
-    if ((rc = prepare_long(a, ws, ws_bytes, opt ? opt->long_min : 0, LC_AUTO_DIV_PREFIX, static_cast<hipStream_t>(stream))) != SGK_OK) return rc;
+    if ((rc = prepare_long(a, ws, ws_bytes, long_min, LC_AUTO_DIV_PREFIX, static_cast<hipStream_t>(stream))) != SGK_OK) return rc;
     prepare_literal(a, ws, ws_bytes);
-    return launch_prefix(a, rna, pore, static_cast<hipStream_t>(stream));
+    return launch_prefix_param(a, rna, ap, window, generic, poly, static_cast<hipStream_t>(stream));
+}
+
+int sgk_prefix_opt(const sgk_batch_t *b, int rna, int pore, sgk_prefix_rec_t *out, void *ws, size_t ws_bytes,
+                   void *stream, const sgk_stat_options_t *opt) {
+    return prefix_batch(b, rna, adaptor_preset(pore), 2000, false, nullptr, out, ws, ws_bytes, stream, opt);
 }
 
 int sgk_prefix(const sgk_batch_t *b, int rna, int pore, sgk_prefix_rec_t *out, void *ws, size_t ws_bytes,
                void *stream) {
     return sgk_prefix_opt(b, rna, pore, out, ws, ws_bytes, stream, nullptr);
+}
+
+// ---- caller-supplied segmenter parameters: the domain, the presets, the route (host arithmetic only)
+static bool is_finite_f32(float v) { return v - v == 0.0f; }
+static bool jnn_core_ok(const sgk_jnn_param_t *p) {  // what jnn and polyA share
+    return p->window >= 32 && p->window <= (1 << 24) && p->corrector >= 1 && p->error >= 0 && p->seg_dist >= 0 &&
+           is_finite_f32(p->stall_len) && p->stall_len >= 0.0f;
+}
+int sgk_jnn_params_check(const sgk_jnn_param_t *p) {
+    if (!p || !jnn_core_ok(p) || !is_finite_f32(p->std_scale)) return SGK_ERR_ARG;
+    return SGK_OK;
+}
+int sgk_prefix_params_check(const sgk_prefix_params_t *p) {
+    if (!p || (p->flags & ~SGK_PREFIX_PARAMS_GENERIC) || p->reserved) return SGK_ERR_ARG;
+    const sgk_jnnv2_param_t &v = p->adaptor;
+    if (v.window < 2 || v.window > SGK_ADAPTOR_WINDOW_MAX || v.lo_thresh < 1 || v.hi_thresh < v.lo_thresh || v.seg_dist < 0 ||
+        !is_finite_f32(v.std_scale))
+        return SGK_ERR_ARG;
+    if (!jnn_core_ok(&p->polya) || !is_finite_f32(p->shift) || !is_finite_f32(p->band) || !(p->band >= 0.0f)) return SGK_ERR_ARG;
+    return SGK_OK;
+}
+int sgk_prefix_params_preset(int rna, int pore, sgk_prefix_params_t *out) {
+    (void)rna;  // (the sets do not depend on it: sgk_prefix runs the polyA finder only for rna)
+    if (!out || (pore != SGK_PORE_R9 && pore != SGK_PORE_R10 && pore != SGK_PORE_RNA004)) return SGK_ERR_ARG;
+    memset(out, 0, sizeof *out);
+    const AdaptP ap = adaptor_preset(pore);
+    out->adaptor.std_scale = ap.std_scale; out->adaptor.seg_dist = ap.seg_dist; out->adaptor.window = 2000;
+    out->adaptor.stall_len = 1.0f; out->adaptor.hi_thresh = ap.hi_thresh; out->adaptor.lo_thresh = ap.lo_thresh;
+    const JnnP pp = jnn_polya_preset();
+    out->polya.std_scale = pp.std_scale; out->polya.corrector = pp.corrector; out->polya.seg_dist = pp.seg_dist;
+    out->polya.window = pp.window; out->polya.stall_len = pp.stall_len; out->polya.error = pp.error;
+    out->shift = 30.0f; out->band = 20.0f;
+    return SGK_OK;
+}
+static bool same_bits(float a, float b) { return memcmp(&a, &b, 4) == 0; }
+static AdaptP to_adaptp(const sgk_jnnv2_param_t &v) {
+    AdaptP ap;
+    ap.std_scale = v.std_scale; ap.seg_dist = v.seg_dist; ap.lo_thresh = v.lo_thresh; ap.hi_thresh = v.hi_thresh;
+    return ap;
+}
+static PolyP to_polyp(const sgk_prefix_params_t *p) {
+    PolyP q;
+    q.p.std_scale = -1.0f; q.p.corrector = p->polya.corrector; q.p.seg_dist = p->polya.seg_dist; q.p.window = p->polya.window;
+    q.p.stall_len = p->polya.stall_len; q.p.error = p->polya.error; q.p.top = 0.0f; q.p.bot = 0.0f;
+    q.shift = p->shift; q.band = p->band;
+    return q;
+}
+int sgk_prefix_route(const sgk_prefix_params_t *p) {
+    if (sgk_prefix_params_check(p) != SGK_OK) return SGK_ERR_ARG;
+    int route = 0;
+    bool adaptor_preset_set = false;
+    for (int pore : {SGK_PORE_R9, SGK_PORE_RNA004}) {
+        const AdaptP ap = adaptor_preset(pore);
+        adaptor_preset_set = adaptor_preset_set || (p->adaptor.window == 2000 && same_bits(p->adaptor.std_scale, ap.std_scale) &&
+                                                    p->adaptor.seg_dist == ap.seg_dist && p->adaptor.lo_thresh == ap.lo_thresh &&
+                                                    p->adaptor.hi_thresh == ap.hi_thresh);
+    }
+    if (!adaptor_preset_set || (p->flags & SGK_PREFIX_PARAMS_GENERIC)) route |= SGK_PREFIX_ROUTE_ADAPTOR_PARAM;
+    const JnnP pp = jnn_polya_preset();
+    const bool polya_preset_set = p->polya.corrector == pp.corrector && p->polya.seg_dist == pp.seg_dist && p->polya.window == pp.window &&
+                                  same_bits(p->polya.stall_len, pp.stall_len) && p->polya.error == pp.error &&
+                                  same_bits(p->shift, 30.0f) && same_bits(p->band, 20.0f);
+    if (!polya_preset_set) route |= polya_wave_ok(to_polyp(p)) ? SGK_PREFIX_ROUTE_POLYA_WAVE_PARAM : SGK_PREFIX_ROUTE_POLYA_LANE_PARAM;
+    return route;
+}
+
+int sgk_jnn_param(const sgk_batch_t *b, const sgk_jnn_param_t *p, const uint64_t *seg_slots, int32_t *seg_x, int32_t *seg_y,
+                  uint32_t *n_segs, void *ws, size_t ws_bytes, void *stream, const sgk_stat_options_t *opt) {
+    if (sgk_jnn_params_check(p) != SGK_OK) return SGK_ERR_ARG;
+    JnnP q;
+    q.std_scale = p->std_scale; q.corrector = p->corrector; q.seg_dist = p->seg_dist; q.window = p->window;
+    q.stall_len = p->stall_len; q.error = p->error; q.top = p->top; q.bot = p->bot;
+    return jnn_batch(b, q, seg_slots, seg_x, seg_y, n_segs, ws, ws_bytes, stream, opt);
+}
+
+int sgk_prefix_param(const sgk_batch_t *b, int rna, const sgk_prefix_params_t *p, sgk_prefix_rec_t *out, void *ws, size_t ws_bytes,
+                     void *stream, const sgk_stat_options_t *opt) {
+    const int route = sgk_prefix_route(p);
+    if (route < 0) return SGK_ERR_ARG;
+    const PolyP poly = to_polyp(p);
+    const bool polya_param = (route & (SGK_PREFIX_ROUTE_POLYA_WAVE_PARAM | SGK_PREFIX_ROUTE_POLYA_LANE_PARAM)) != 0;
+    return prefix_batch(b, rna, to_adaptp(p->adaptor), p->adaptor.window, (route & SGK_PREFIX_ROUTE_ADAPTOR_PARAM) != 0,
+                        polya_param ? &poly : nullptr, out, ws, ws_bytes, stream, opt);
+}
+
+int sgk_debug_roll_means(int window, uint32_t n, float *out, void *stream) {
+    return launch_k_roll_means_param(static_cast<hipStream_t>(stream), window, n, out);
 }
 
 int sgk_stat_plan(int tool, uint32_t n_reads, uint64_t n_samples, uint32_t max_read_len, const sgk_stat_options_t *opt,

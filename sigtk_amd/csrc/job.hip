@@ -163,6 +163,10 @@ struct sgk_job {
     sgk_event_options_t ev_opt;   // sgk_job_set_options (all zero: the defaults)
     sgk_event_params_t ev_params; // sgk_job_set_event_params
     bool has_ev_params = false;
+    sgk_jnn_param_t jnn_params;       // sgk_job_set_jnn_params
+    bool has_jnn_params = false;
+    sgk_prefix_params_t prefix_params; // sgk_job_set_prefix_params
+    bool has_prefix_params = false;
     sgk_stat_options_t st_opt;
 };
 
@@ -223,6 +227,30 @@ int sgk_job_set_event_params(sgk_job_t *j, const sgk_event_params_t *params) {
     if (sgk_event_params_route(params) < 0) return SGK_ERR_ARG;  // (the submits route by the same call: sgk_event_param)
     j->ev_params = *params;
     j->has_ev_params = true;
+    return SGK_OK;
+}
+
+int sgk_job_set_jnn_params(sgk_job_t *j, const sgk_jnn_param_t *params) {
+    if (!j) return SGK_ERR_ARG;
+    if (!params) {
+        j->has_jnn_params = false;
+        return SGK_OK;
+    }
+    if (sgk_jnn_params_check(params) != SGK_OK) return SGK_ERR_ARG;
+    j->jnn_params = *params;
+    j->has_jnn_params = true;
+    return SGK_OK;
+}
+
+int sgk_job_set_prefix_params(sgk_job_t *j, const sgk_prefix_params_t *params) {
+    if (!j) return SGK_ERR_ARG;
+    if (!params) {
+        j->has_prefix_params = false;
+        return SGK_OK;
+    }
+    if (sgk_prefix_route(params) < 0) return SGK_ERR_ARG;  // (the submits route by the same call: sgk_prefix_param)
+    j->prefix_params = *params;
+    j->has_prefix_params = true;
     return SGK_OK;
 }
 
@@ -786,6 +814,9 @@ int sgk_job_submit(sgk_job_t *j, int tool, int rna, int pore, int flags) {
             else if (ev)
                 rc = sgk_event_opt(&view, rna, j->d_slots.as<uint64_t>(), j->d_out[0].as<sgk_event_rec_t>(),
                                    j->d_cnt.as<uint32_t>(), j->d_ws.p, j->d_ws.cap, st, &j->ev_opt);
+            else if (j->has_jnn_params)
+                rc = sgk_jnn_param(&view, &j->jnn_params, j->d_slots.as<uint64_t>(), j->d_out[0].as<int32_t>(),
+                                   j->d_out[1].as<int32_t>(), j->d_cnt.as<uint32_t>(), j->d_ws.p, j->d_ws.cap, st, &j->st_opt);
             else
                 rc = sgk_jnn_opt(&view, rna, j->d_slots.as<uint64_t>(), j->d_out[0].as<int32_t>(),
                                  j->d_out[1].as<int32_t>(), j->d_cnt.as<uint32_t>(), j->d_ws.p, j->d_ws.cap, st, &j->st_opt);
@@ -849,7 +880,11 @@ int sgk_job_submit(sgk_job_t *j, int tool, int rna, int pore, int flags) {
             if ((rc = j->d_out[0].ensure(nr * sizeof(sgk_prefix_rec_t))) != SGK_OK) return rc;
             j->ws_bytes = sgk_prefix_workspace_bytes(j->n_reads, j->n_samples, j->max_len);
             if ((rc = j->d_ws.ensure(j->ws_bytes)) != SGK_OK) return rc;
-            rc = sgk_prefix_opt(&view, rna, pore, j->d_out[0].as<sgk_prefix_rec_t>(), j->d_ws.p, j->d_ws.cap, st, &j->st_opt);
+            if (j->has_prefix_params)
+                rc = sgk_prefix_param(&view, rna, &j->prefix_params, j->d_out[0].as<sgk_prefix_rec_t>(), j->d_ws.p, j->d_ws.cap, st,
+                                      &j->st_opt);
+            else
+                rc = sgk_prefix_opt(&view, rna, pore, j->d_out[0].as<sgk_prefix_rec_t>(), j->d_ws.p, j->d_ws.cap, st, &j->st_opt);
             if (rc != SGK_OK) return rc;
             if ((rc = fetch_long_hdr(j, st)) != SGK_OK) return rc;
             if ((rc = d2h(j->h_out[0], j->d_out[0], nr * sizeof(sgk_prefix_rec_t), st)) != SGK_OK) return rc;

@@ -336,6 +336,55 @@ sgk_jnn_pair_t sgk_jnnv2(const int16_t *sig, int64_t nsample, sgk_jnnv2_param_t 
     return p;
 }
 
+// any window of the domain (sgk_prefix_params_check's adaptor part), always on k_adaptor_param
+sgk_jnn_pair_t sgk_jnnv2_param(const int16_t *sig, int64_t nsample, sgk_jnnv2_param_t param) {
+    sgk_jnn_pair_t p = {-1, -1};
+    g_shim_rc = SGK_OK;
+    sgk_prefix_params_t chk;
+    sgk_prefix_params_preset(0, SGK_PORE_R9, &chk);
+    chk.adaptor = param;
+    if (sgk_prefix_params_check(&chk) != SGK_OK) { g_shim_rc = SGK_ERR_ARG; return p; }
+    if (nsample <= param.window) return p;  // "Not enough data to trim" (src/jnn.c:172-176)
+    if (!sig) { g_shim_rc = SGK_ERR_ARG; return p; }
+    DeviceBatch db;
+    if ((g_shim_rc = upload_one(sig, nsample, db)) != SGK_OK) return p;
+    DevBuf d_out;
+    if ((g_shim_rc = d_out.alloc(sizeof(sgk_prefix_rec_t))) != SGK_OK) return p;
+    StatArgs a;
+    memset(&a, 0, sizeof a);
+    a.b = db.view;
+    a.prefix = d_out.as<sgk_prefix_rec_t>();
+    AdaptP ap;
+    ap.std_scale = param.std_scale; ap.seg_dist = param.seg_dist; ap.lo_thresh = param.lo_thresh; ap.hi_thresh = param.hi_thresh;
+    if ((g_shim_rc = launch_k_adaptor_param(nullptr, a, ap, param.window)) != SGK_OK) return p;
+    sgk_prefix_rec_t rec;
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&rec, d_out.p, sizeof rec, hipMemcpyDeviceToHost) != hipSuccess) {
+        g_shim_rc = SGK_ERR_HIP;
+        return p;
+    }
+    p.x = rec.adapt_x;
+    p.y = rec.adapt_y;
+    return p;
+}
+
+sgk_jnn_pair_t sgk_find_polya_param(const float *raw, int64_t nsample, float top, float bot, sgk_jnn_param_t param) {
+    sgk_jnn_pair_t p = {-1, -1};
+    sgk_prefix_params_t chk;
+    sgk_prefix_params_preset(1, SGK_PORE_R9, &chk);
+    chk.polya = param;
+    if (sgk_prefix_params_check(&chk) != SGK_OK) { g_shim_rc = SGK_ERR_ARG; return p; }
+    param.std_scale = -1.0f;  // the fixed thresholds
+    param.top = top;
+    param.bot = bot;
+    int ns = 0;
+    sgk_jnn_pair_t *segs = sgk_jnn_pa(raw, nsample, param, &ns);
+    if (segs) {
+        if (ns > 0) p = segs[0];
+        free(segs);
+    }
+    return p;
+}
+
 sgk_jnn_pair_t sgk_find_adaptor(const int16_t *raw, int64_t nsample, int8_t pore) {
     const AdaptP ap = adaptor_preset(pore);
     sgk_jnnv2_param_t q;

@@ -161,6 +161,12 @@ struct AdaptP {
     float std_scale;
     int seg_dist, lo_thresh, hi_thresh;
 };
+// a caller's polyA set (sgk_prefix_params_t): jnn_core's parameters (std_scale, top, bot unused) and the band of
+// src/cfunc.c:191, top = (m_a + shift) + band, bot = (m_a + shift) - band
+struct PolyP {
+    JnnP p;
+    float shift, band;
+};
 JnnP jnn_preset(int rna);          // jnn_print's presets (src/jnn.c:313-319)
 JnnP jnn_polya_preset();           // JNNV1_R9_POLYA == JNNV1_RNA004_POLYA (src/jnn.h:52-72)
 AdaptP adaptor_preset(int pore);   // find_adaptor's presets (src/jnn.c:181-188)
@@ -171,6 +177,10 @@ int launch_stat(const StatArgs &a, hipStream_t st);  // a.pa_out != null: fused 
 int launch_jnn(const StatArgs &a, const JnnP &p, hipStream_t st);
 int launch_prefix(const StatArgs &a, int rna, int pore, hipStream_t st);
 int launch_adaptor(const StatArgs &a, const AdaptP &p, hipStream_t st);  // jnnv2 only: prefix[r].adapt_x / adapt_y
+// prefix with a caller's parameters (sgk_prefix_param): `window` 2000 and !generic take launch_adaptor, anything else
+// k_adaptor_param; poly == nullptr: the presets' polyA kernels, else the parametrised ones (polya_wave_ok: which)
+int launch_prefix_param(const StatArgs &a, int rna, const AdaptP &ap, int window, bool generic, const PolyP *poly, hipStream_t st);
+inline bool polya_wave_ok(const PolyP &q) { return q.p.stall_len == 1.0f && q.p.error < q.p.corrector; }
 
 // ---- one launch per kernel, defined in the unit that holds the kernel (without relocatable device code a kernel is
 // launched from its own translation unit); the launchers above (stat_launch.hip) are made of these.  name: the profile
@@ -182,10 +192,16 @@ int launch_k_median(const char *name, int region, bool pa, bool flagged, hipStre
 int launch_k_jnn(const char *name, hipStream_t st, const StatArgs &a, const JnnP &p);
 int launch_k_polya(hipStream_t st, const StatArgs &a);
 int launch_k_adaptor(hipStream_t st, const StatArgs &a, const AdaptP &p);
+int launch_k_polya_param(hipStream_t st, const StatArgs &a, const PolyP &q);
+// stat_param.hip -- one read per wavefront, any jnnv2 window of 2 .. 13 981; the test entry of its division
+int launch_k_adaptor_param(hipStream_t st, const StatArgs &a, const AdaptP &p, int window);
+int launch_k_roll_means_param(hipStream_t st, int window, uint32_t n, float *out);
 // stat_wave.hip -- one read per wavefront, four per workgroup
 int launch_k_stat_wave(const char *name, int region, bool pa, uint32_t grid, hipStream_t st, const StatArgs &a);
 int launch_k_jnn_wave(const char *name, uint32_t grid, hipStream_t st, const StatArgs &a, const JnnP &p);
 int launch_k_polya_wave(hipStream_t st, const StatArgs &a);
+// (stat_param.hip, on k_polya_wave_t<true> of stat_wave.h; polya_wave_ok(q) only)
+int launch_k_polya_wave_param(hipStream_t st, const StatArgs &a, const PolyP &q);
 int launch_k_adaptor_wave(const char *name, uint32_t grid, hipStream_t st, const StatArgs &a, const AdaptP &p);
 // stat_long.hip -- k_long_chains<kind>, LC_PARTS workgroups per long read the batch can hold
 enum { LC_STAT = 0, LC_JNN = 1, LC_ADAPT = 2 };

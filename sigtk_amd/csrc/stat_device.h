@@ -236,12 +236,28 @@ __device__ __forceinline__ float roll_mean(int tot) { return sgk_div_f32<ADW>((f
 // smallest integer total whose rolling mean is >= x (resp. > x): roll_mean is non-decreasing in tot, so
 // the run finder's float comparisons t < bot / t > bot (src/jnn.c:139-163) become integer comparisons
 // tot < T_lt / tot >= T_gt.  Binary search over [0, 2000*1200].
-__device__ inline int roll_threshold(float x, bool strict) {
+// Where the window comes from (the window source of roll_threshold and adaptor_find): WinPreset is the constant 2000 of
+// both presets with the constant division above; WinParam (k_adaptor_param, stat_param.hip) holds a caller's window, 2 ..
+// 13 981, and divides at run time -- the library is built with -fhip-fp32-correctly-rounded-divide-sqrt, which makes
+// the f32 `/` the correctly rounded IEEE quotient (tot <= 1200 * 13 981 <= 2^24 and the window are exact in f32, the
+// quotient is 0 or a normal number); tests/test_gpu_segmenter_params.py runs it for every total of every tested window.
+struct WinPreset {
+    __device__ __forceinline__ int w() const { return ADW; }
+    __device__ __forceinline__ float mean(int tot) const { return roll_mean(tot); }
+};
+struct WinParam {
+    int win;
+    float winf;
+    __device__ __forceinline__ int w() const { return win; }
+    __device__ __forceinline__ float mean(int tot) const { return (float)tot / winf; }
+};
+template <typename WS = WinPreset>
+__device__ inline int roll_threshold(float x, bool strict, const WS ws = WS{}) {
     if (x != x) return strict ? 0x7fffffff : 0;  // NaN threshold: no t is < or > it
-    int lo = 0, hi = ADW * 1200 + 1;  // answer in [lo, hi]
+    int lo = 0, hi = ws.w() * 1200 + 1;  // answer in [lo, hi]
     while (lo < hi) {
         const int mid = (lo + hi) >> 1;
-        const float t = roll_mean(mid);
+        const float t = ws.mean(mid);
         const bool ok = strict ? (t > x) : (t >= x);   // NaN x: never ok -> hi stays -> nothing is >= / > x
         if (ok) hi = mid; else lo = mid + 1;
     }

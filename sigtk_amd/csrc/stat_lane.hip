@@ -455,8 +455,9 @@ __global__ __launch_bounds__(64) void k_jnn(StatArgs a, JnnP p) {
 
 // find_polya (src/jnn.c:352-374): first segment of jnn_pa on pA[adapt_y..n) with fixed thresholds
 // top = (m_a+30)+20, bot = (m_a+30)-20 (src/cfunc.c:191); polyA preset src/jnn.h:52-72.
-__global__ __launch_bounds__(64) void k_polya(StatArgs a) {
-    __shared__ __attribute__((aligned(16))) char lds[RowPrefetch::LDS_BYTES];
+// PARAM: the caller's set `q` (any of the domain: JnnAuto is the whole automaton) in place of the preset and of 30 / 20
+template <bool PARAM>
+__device__ __forceinline__ void polya_lane(const StatArgs &a, const PolyP &q, char *lds) {
     const uint32_t r = blockIdx.x * 64 + lane_id();
     const bool valid = r < a.b.n_reads;
     Region g = {0, 0};
@@ -469,10 +470,10 @@ __global__ __launch_bounds__(64) void k_polya(StatArgs a) {
     }
     int skip;
     RowPrefetch rs = make_stream(lds, a.b, g.start, valid && g.len > 0, skip);
-    const float mid = m_a + 30.0f;
+    const float mid = m_a + (PARAM ? q.shift : 30.0f);
     JnnAuto A;
-    const JnnP pp = {-1.0f, 50, 200, 250, 1.0f, 30, 0.0f, 0.0f};  // JNNV1_R9_POLYA, src/jnn.h:52-61
-    A.init(mid + 20.0f, mid - 20.0f, pp.corrector, pp.seg_dist, pp.window, pp.stall_len, pp.error);
+    const JnnP pp = PARAM ? q.p : JnnP{-1.0f, 50, 200, 250, 1.0f, 30, 0.0f, 0.0f};  // JNNV1_R9_POLYA, src/jnn.h:52-61
+    A.init(mid + (PARAM ? q.band : 20.0f), mid - (PARAM ? q.band : 20.0f), pp.corrector, pp.seg_dist, pp.window, pp.stall_len, pp.error);
     int px = -1, py = -1;
     auto emit = [&](int k, int x, int y) {
         if (k == 0) { px = x; py = y; }
@@ -486,6 +487,14 @@ __global__ __launch_bounds__(64) void k_polya(StatArgs a) {
         a.prefix[r].polya_x = px;
         a.prefix[r].polya_y = py;
     }
+}
+__global__ __launch_bounds__(64) void k_polya(StatArgs a) {
+    __shared__ __attribute__((aligned(16))) char lds[RowPrefetch::LDS_BYTES];
+    polya_lane<false>(a, PolyP{}, lds);
+}
+__global__ __launch_bounds__(64) void k_polya_param(StatArgs a, PolyP q) {
+    __shared__ __attribute__((aligned(16))) char lds[RowPrefetch::LDS_BYTES];
+    polya_lane<true>(a, q, lds);
 }
 
 // ---------------------------------------------------------------- find_adaptor / jnnv2 (src/jnn.c:99-188)
@@ -682,6 +691,10 @@ int launch_k_jnn(const char *name, hipStream_t st, const StatArgs &a, const JnnP
 }
 int launch_k_polya(hipStream_t st, const StatArgs &a) {
     SGK_LAUNCH("k_polya", k_polya, (a.b.n_reads + 63) / 64, 64, st, a);
+    return SGK_OK;
+}
+int launch_k_polya_param(hipStream_t st, const StatArgs &a, const PolyP &q) {
+    SGK_LAUNCH("k_polya_param", k_polya_param, (a.b.n_reads + 63) / 64, 64, st, a, q);
     return SGK_OK;
 }
 int launch_k_adaptor(hipStream_t st, const StatArgs &a, const AdaptP &p) {

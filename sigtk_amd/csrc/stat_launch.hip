@@ -184,6 +184,13 @@ static int launch_region_stats(int region, const StatArgs &a, bool lanes, bool l
 }
 
 int launch_prefix(const StatArgs &a, int rna, int pore, hipStream_t st) {
+    return launch_prefix_param(a, rna, adaptor_preset(pore), 2000, false, nullptr, st);
+}
+
+// generic: k_adaptor_param whatever the window (it has no long-read split: a.longs is not looked at); poly: the
+// parametrised polyA kernels -- one read per wavefront where polya_wave_ok holds, else (and where the caller forces the
+// lane kernels) one read per lane
+int launch_prefix_param(const StatArgs &a, int rna, const AdaptP &ap, int window, bool generic, const PolyP *poly, hipStream_t st) {
     const uint32_t nr = a.b.n_reads;
     if (nr == 0) return SGK_OK;
     // The adaptor and polyA finders: one read per wavefront unless the caller forces the lane kernels (k_adaptor_wave 4.3
@@ -194,10 +201,11 @@ int launch_prefix(const StatArgs &a, int rna, int pore, hipStream_t st) {
     const bool lanes = lane_per_read(2, a);
     const bool lane_regions = lanes || lane_per_read(4, a);
     // (launch_adaptor joins its side stream inside: the kernels behind read every read's adapt_x / adapt_y)
-    int rc = launch_adaptor(a, adaptor_preset(pore), st);
+    int rc = (generic || window != 2000) ? launch_k_adaptor_param(st, a, ap, window) : launch_adaptor(a, ap, st);
     if (rc == SGK_OK) rc = launch_region_stats(REG_ADAPT, a, lanes, lane_regions, st);
     if (rc != SGK_OK || !rna) return rc;
-    rc = lanes ? launch_k_polya(st, a) : launch_k_polya_wave(st, a);
+    if (!poly) rc = lanes ? launch_k_polya(st, a) : launch_k_polya_wave(st, a);
+    else rc = (lanes || !polya_wave_ok(*poly)) ? launch_k_polya_param(st, a, *poly) : launch_k_polya_wave_param(st, a, *poly);
     if (rc != SGK_OK) return rc;
     return launch_region_stats(REG_POLYA, a, lanes, lane_regions, st);
 }

@@ -700,6 +700,117 @@ __device__ __forceinline__ int mask_select(uint32_t m16, int cur, int k) {
     return l * SS_SPL + __builtin_amdgcn_readlane(__ffs((int)m) - 1, l);
 }
 
+__host__ __device__ inline JnnP jnn_polya_params() {  // JNNV1_R9_POLYA == JNNV1_RNA004_POLYA, src/jnn.h:52-72
+    return JnnP{-1.0f, 50, 200, 250, 1.0f, 30, 0.0f, 0.0f};
+}
+
+// ---------------------------------------------------------------- find_polya, one WAVE per read
+// jnn_pa on pA[adapt_y .. n) with the fixed thresholds of cfunc.c:191 and the polyA preset (src/jnn.h:52-72), first
+// merged segment only.  x -> rm_outlierf(signal_in_picoamps(x)) is monotone in the raw value, so the in-range test
+// bot < pA < top is an interval test on the raw sample (its bounds by bisection over the 65 536 raw values, with the
+// float expression itself): no pA is formed.  With error = 30 the automaton has next to no sync points (31 out-of-range
+// samples in a row), so instead of chunks the wave goes through the tail tile by tile (64 x 16 samples, coalesced) with
+// the automaton's state in scalars and JUMPS: a segment opens at the next in-range sample and ends at the
+// (error + 1 - err)-th out-of-range sample behind it, both found on the tile's 16-bit lane masks (next set bit; k-th set
+// bit by a popcount scan).  It stops as soon as the first merged segment can no longer change -- usually after a few
+// tiles, where the lane-per-read kernel waits for the slowest of 64 reads.
+// (jnn_chunks was tried first for this: its chunks degenerate, 11.3 ms against the lane kernel's 5.8 ms on 50 000 reads.)
+template <typename PRED>
+__device__ inline int first_true_i16(PRED pred) {  // smallest v in [-32768, 32767] with pred(v), 32768 if none (pred monotone)
+    int lo = -32768, hi = 32768;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (pred(mid)) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+// PARAM: the caller's set `q` (polya_wave_ok(q): stall_len 1, so that the first-segment rule is the window's, and error <
+// corrector, so that the correction of jnn.c:228,238 cannot fire) in place of the preset and of 30 / 20
+template <bool PARAM>
+__global__ __launch_bounds__(256) void k_polya_wave_t(StatArgs a, PolyP q) {
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = lane_id();
+    const uint32_t widx = blockIdx.x * 4 + wv;
+    if (widx >= a.b.n_reads) return;
+    const uint32_t r = a.order ? a.order[widx] : widx;
+    const Region g = get_region(REG_TAIL, a.b, a.prefix, r);
+    int px = -1, py = -1;
+    if (g.len > 0) {
+        const Scale sc = make_scale(a.b.digitisation[r], a.b.offset[r], a.b.range[r]);
+        const float mid = a.prefix[r].adapt_mean + (PARAM ? q.shift : 30.0f);
+        const float top = mid + (PARAM ? q.band : 20.0f), bot = mid - (PARAM ? q.band : 20.0f);
+        const JnnP pp = PARAM ? q.p : jnn_polya_params();
+        auto f = [&](int v) { return clampf_pa(to_pa((int16_t)v, sc)); };
+        int vlo, vhi;  // in range <=> vlo <= raw <= vhi
+        if (sc.unit >= 0.0f) {
+            vlo = first_true_i16([&](int v) { return f(v) > bot; });
+            vhi = first_true_i16([&](int v) { return !(f(v) < top); }) - 1;
+        } else {
+            vlo = first_true_i16([&](int v) { return f(v) < top; });
+            vhi = first_true_i16([&](int v) { return !(f(v) > bot); }) - 1;
+        }
+        // a NaN anywhere (unit, offset, thresholds) makes every comparison of the reference false: nothing is in range
+        if (!(sc.unit == sc.unit) || !(sc.offf == sc.offf) || !(top == top)) { vlo = 1; vhi = 0; }
+        WaveRead wr;
+        wr.init(a.b, g);
+        const int hi_r = vhi + 1, lo_r = vlo - 1;  // in range <=> lo_r < raw < hi_r
+        // automaton state (wave-uniform): open, errors so far, trailing tolerated errors, start; first merged segment
+        int opn = 0, err = 0, run = 0, start = 0, last_y = 0;
+        bool found = false, done = false;
+        WaveTile cur_t, nxt_t;
+        wr.load(cur_t, 0);
+        for (int t = 0; t < wr.ntiles && !done; ++t) {
+            if (t + 1 < wr.ntiles) wr.load(nxt_t, t + 1);
+            int q_lo, q_hi;
+            wr.range(t, 0, q_lo, q_hi);
+            uint32_t inm = 0u;
+#pragma unroll
+            for (int e = 0; e < SS_SPL; ++e) {
+                const int iv = (e & 1) ? (int)(int16_t)(cur_t.w[e / 2] >> 16) : (int)(int16_t)(cur_t.w[e / 2] & 0xffffu);
+                inm |= ((uint32_t)((iv - hi_r) & (lo_r - iv)) >> 31) << e;
+            }
+            const int l0 = q_lo - lane * SS_SPL, l1 = q_hi - lane * SS_SPL;
+            uint32_t vm = l0 <= 0 ? 0xffffu : (l0 >= SS_SPL ? 0u : (0xffffu >> l0) << l0);
+            vm = l1 >= SS_SPL ? vm : (l1 <= 0 ? 0u : vm & ((1u << l1) - 1u));
+            inm &= vm;
+            const uint32_t outm = ~inm & vm;
+            const int jbase = t * SS_TILE - wr.skip;  // sample index (in the tail) of tile-local position 0
+            int cur = q_lo;
+            for (;;) {
+                if (!opn) {
+                    const int ps = mask_next(inm, cur);
+                    if (ps < 0) break;
+                    start = jbase + ps; opn = 1; err = 0; run = 0; cur = ps + 1;
+                } else {
+                    const int need = pp.error + 1 - err;
+                    const int pc = wave_last_i(wave_incl_scan_i(__popc(mask_from(outm, cur))));
+                    if (pc < need) {  // the segment outlives the tile
+                        err += pc;
+                        const int li = mask_last(inm, cur, q_hi);
+                        run = li >= 0 ? q_hi - 1 - li : run + (q_hi - cur);
+                        break;
+                    }
+                    const int pe = mask_select(outm, cur, need);
+                    const int li = mask_last(inm, cur, pe);
+                    const int perr = li >= 0 ? pe - 1 - li : run + (pe - cur);
+                    const int i = jbase + pe, end = i - perr;
+                    if (i - start >= pp.window) {  // kept (stall_len = 1: the first-segment rule is the same)
+                        if (!found) { px = start; py = end; found = true; }
+                        else if (start - last_y < pp.seg_dist) py = end;
+                        else { done = true; break; }  // the first merged segment is final
+                        last_y = end;
+                    }
+                    opn = 0; err = 0; run = 0; cur = pe + 1;
+                }
+            }
+            cur_t = nxt_t;
+        }
+    }
+    if (lane == 0) {
+        a.prefix[r].polya_x = px;
+        a.prefix[r].polya_y = py;
+    }
+}
 // ---------------------------------------------------------------- find_adaptor / jnnv2, one WAVE per read
 // Same arithmetic as k_adaptor, laid out as k_stat_wave: tiles of 64 x SS_SPL window indices; a lane holds the trailing
 // samples x[i..i+16) and the leading samples x[i+2000..i+2016) of its 16 indices, forms the 16 differences of the
@@ -859,19 +970,21 @@ __device__ __forceinline__ void adaptor_init_rec(sgk_prefix_rec_t *o, int64_t n)
 }
 // jnnv2's thresholds from the two sums over the m rolling means (src/jnn.c:106-124) and its run finder (k_adaptor's RunFinder,
 // src/jnn.c:126-167) from flip to flip, by one wave; writes adapt_x / adapt_y
-__device__ inline void adaptor_find(const WaveRead &wr, int first_total, float s, float q, float mf, const AdaptP &ap,
-                                    sgk_prefix_rec_t *o, uint4 *ring = nullptr) {
+// WS: the window source (stat_device.h); sweep(f): one sweep over the rolling totals of the windows of wr, as roll_sweep
+template <typename WS, typename SWEEP>
+__device__ __forceinline__ void adaptor_find_ws(const WaveRead &wr, float s, float q, float mf, const AdaptP &ap,
+                                                sgk_prefix_rec_t *o, const WS ws, SWEEP sweep) {
     const int lane = lane_id(), q0 = lane * SS_SPL;
     const float mn = s / mf;
     const float sd = sqrtf(q / mf);
     const float bot = mn - sd * ap.std_scale;
-    const int t_lt = roll_threshold(bot, false), t_gt = roll_threshold(bot, true);
+    const int t_lt = roll_threshold(bot, false, ws), t_gt = roll_threshold(bot, true, ws);
     int in_run = 0, start = 0, end = 0, nseg = 0, last_x = 0, last_y = 0, ans_x = 0, ans_y = 0, found = 0;
     auto settle = [&]() {
         const int len = last_y - last_x;
         if (!found && !(len > ap.hi_thresh) && !(len < ap.lo_thresh)) { found = 1; ans_x = last_x; ans_y = last_y; }
     };
-    roll_sweep(wr, first_total, [&](int t, const int (&tot)[SS_SPL]) {
+    sweep([&](int t, const int (&tot)[SS_SPL]) {
         int q_lo, q_hi;
         wr.range(t, 0, q_lo, q_hi);
         uint32_t bm = 0u, am = 0u;
@@ -906,12 +1019,16 @@ __device__ inline void adaptor_find(const WaveRead &wr, int first_total, float s
             }
         }
         return found != 0;
-    }, ring);
+    });
     if (nseg > 0) settle();
     if (lane == 0) {
-        if (found) { o->adapt_x = ans_x + ADW / 2 - 1; o->adapt_y = ans_y + ADW / 2 - 1; }
+        if (found) { o->adapt_x = ans_x + ws.w() / 2 - 1; o->adapt_y = ans_y + ws.w() / 2 - 1; }
         else { o->adapt_x = 0; o->adapt_y = 0; }
     }
+}
+__device__ inline void adaptor_find(const WaveRead &wr, int first_total, float s, float q, float mf, const AdaptP &ap,
+                                    sgk_prefix_rec_t *o, uint4 *ring = nullptr) {
+    adaptor_find_ws(wr, s, q, mf, ap, o, WinPreset{}, [&](auto f) { roll_sweep(wr, first_total, f, ring); });
 }
 
 }  // namespace sgk

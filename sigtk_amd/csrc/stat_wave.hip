@@ -170,114 +170,9 @@ __global__ __launch_bounds__(256) void k_jnn_wave(StatArgs a, JnnP p) {
     if (lane == 0) a.n_segs[r] = total;
 }
 
-__host__ __device__ inline JnnP jnn_polya_params() {  // JNNV1_R9_POLYA == JNNV1_RNA004_POLYA, src/jnn.h:52-72
-    return JnnP{-1.0f, 50, 200, 250, 1.0f, 30, 0.0f, 0.0f};
-}
-
 // ---------------------------------------------------------------- find_polya, one WAVE per read
-// jnn_pa on pA[adapt_y .. n) with the fixed thresholds of cfunc.c:191 and the polyA preset (src/jnn.h:52-72), first
-// merged segment only.  x -> rm_outlierf(signal_in_picoamps(x)) is monotone in the raw value, so the in-range test
-// bot < pA < top is an interval test on the raw sample (its bounds by bisection over the 65 536 raw values, with the
-// float expression itself): no pA is formed.  With error = 30 the automaton has next to no sync points (31 out-of-range
-// samples in a row), so instead of chunks the wave goes through the tail tile by tile (64 x 16 samples, coalesced) with
-// the automaton's state in scalars and JUMPS: a segment opens at the next in-range sample and ends at the
-// (error + 1 - err)-th out-of-range sample behind it, both found on the tile's 16-bit lane masks (next set bit; k-th set
-// bit by a popcount scan).  It stops as soon as the first merged segment can no longer change -- usually after a few
-// tiles, where the lane-per-read kernel waits for the slowest of 64 reads.
-// (jnn_chunks was tried first for this: its chunks degenerate, 11.3 ms against the lane kernel's 5.8 ms on 50 000 reads.)
-template <typename PRED>
-__device__ inline int first_true_i16(PRED pred) {  // smallest v in [-32768, 32767] with pred(v), 32768 if none (pred monotone)
-    int lo = -32768, hi = 32768;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (pred(mid)) hi = mid; else lo = mid + 1;
-    }
-    return lo;
-}
-
-__global__ __launch_bounds__(256) void k_polya_wave(StatArgs a) {
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = lane_id();
-    const uint32_t widx = blockIdx.x * 4 + wv;
-    if (widx >= a.b.n_reads) return;
-    const uint32_t r = a.order ? a.order[widx] : widx;
-    const Region g = get_region(REG_TAIL, a.b, a.prefix, r);
-    int px = -1, py = -1;
-    if (g.len > 0) {
-        const Scale sc = make_scale(a.b.digitisation[r], a.b.offset[r], a.b.range[r]);
-        const float mid = a.prefix[r].adapt_mean + 30.0f;
-        const float top = mid + 20.0f, bot = mid - 20.0f;
-        const JnnP pp = jnn_polya_params();
-        auto f = [&](int v) { return clampf_pa(to_pa((int16_t)v, sc)); };
-        int vlo, vhi;  // in range <=> vlo <= raw <= vhi
-        if (sc.unit >= 0.0f) {
-            vlo = first_true_i16([&](int v) { return f(v) > bot; });
-            vhi = first_true_i16([&](int v) { return !(f(v) < top); }) - 1;
-        } else {
-            vlo = first_true_i16([&](int v) { return f(v) < top; });
-            vhi = first_true_i16([&](int v) { return !(f(v) > bot); }) - 1;
-        }
-        // a NaN anywhere (unit, offset, thresholds) makes every comparison of the reference false: nothing is in range
-        if (!(sc.unit == sc.unit) || !(sc.offf == sc.offf) || !(top == top)) { vlo = 1; vhi = 0; }
-        WaveRead wr;
-        wr.init(a.b, g);
-        const int hi_r = vhi + 1, lo_r = vlo - 1;  // in range <=> lo_r < raw < hi_r
-        // automaton state (wave-uniform): open, errors so far, trailing tolerated errors, start; first merged segment
-        int opn = 0, err = 0, run = 0, start = 0, last_y = 0;
-        bool found = false, done = false;
-        WaveTile cur_t, nxt_t;
-        wr.load(cur_t, 0);
-        for (int t = 0; t < wr.ntiles && !done; ++t) {
-            if (t + 1 < wr.ntiles) wr.load(nxt_t, t + 1);
-            int q_lo, q_hi;
-            wr.range(t, 0, q_lo, q_hi);
-            uint32_t inm = 0u;
-#pragma unroll
-            for (int e = 0; e < SS_SPL; ++e) {
-                const int iv = (e & 1) ? (int)(int16_t)(cur_t.w[e / 2] >> 16) : (int)(int16_t)(cur_t.w[e / 2] & 0xffffu);
-                inm |= ((uint32_t)((iv - hi_r) & (lo_r - iv)) >> 31) << e;
-            }
-            const int l0 = q_lo - lane * SS_SPL, l1 = q_hi - lane * SS_SPL;
-            uint32_t vm = l0 <= 0 ? 0xffffu : (l0 >= SS_SPL ? 0u : (0xffffu >> l0) << l0);
-            vm = l1 >= SS_SPL ? vm : (l1 <= 0 ? 0u : vm & ((1u << l1) - 1u));
-            inm &= vm;
-            const uint32_t outm = ~inm & vm;
-            const int jbase = t * SS_TILE - wr.skip;  // sample index (in the tail) of tile-local position 0
-            int cur = q_lo;
-            for (;;) {
-                if (!opn) {
-                    const int ps = mask_next(inm, cur);
-                    if (ps < 0) break;
-                    start = jbase + ps; opn = 1; err = 0; run = 0; cur = ps + 1;
-                } else {
-                    const int need = pp.error + 1 - err;
-                    const int pc = wave_last_i(wave_incl_scan_i(__popc(mask_from(outm, cur))));
-                    if (pc < need) {  // the segment outlives the tile
-                        err += pc;
-                        const int li = mask_last(inm, cur, q_hi);
-                        run = li >= 0 ? q_hi - 1 - li : run + (q_hi - cur);
-                        break;
-                    }
-                    const int pe = mask_select(outm, cur, need);
-                    const int li = mask_last(inm, cur, pe);
-                    const int perr = li >= 0 ? pe - 1 - li : run + (pe - cur);
-                    const int i = jbase + pe, end = i - perr;
-                    if (i - start >= pp.window) {  // kept (stall_len = 1: the first-segment rule is the same)
-                        if (!found) { px = start; py = end; found = true; }
-                        else if (start - last_y < pp.seg_dist) py = end;
-                        else { done = true; break; }  // the first merged segment is final
-                        last_y = end;
-                    }
-                    opn = 0; err = 0; run = 0; cur = pe + 1;
-                }
-            }
-            cur_t = nxt_t;
-        }
-    }
-    if (lane == 0) {
-        a.prefix[r].polya_x = px;
-        a.prefix[r].polya_y = py;
-    }
-}
+// k_polya_wave is k_polya_wave_t<false> of stat_wave.h (the kernel is a template there so that stat_param.hip can
+// instantiate it with a caller's set; as a device function called from two kernels the preset kernel took more registers)
 
 __global__ __launch_bounds__(256) void k_adaptor_wave(StatArgs a, AdaptP ap) {
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = lane_id();
@@ -378,7 +273,7 @@ int launch_k_jnn_wave(const char *name, uint32_t grid, hipStream_t st, const Sta
     return SGK_OK;
 }
 int launch_k_polya_wave(hipStream_t st, const StatArgs &a) {
-    SGK_LAUNCH("k_polya_wave", k_polya_wave, (a.b.n_reads + 3) / 4, 256, st, a);
+    SGK_LAUNCH("k_polya_wave", k_polya_wave_t<false>, (a.b.n_reads + 3) / 4, 256, st, a, PolyP{});
     return SGK_OK;
 }
 int launch_k_adaptor_wave(const char *name, uint32_t grid, hipStream_t st, const StatArgs &a, const AdaptP &p) {

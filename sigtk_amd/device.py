@@ -277,11 +277,16 @@ def pipeline(b: DeviceReads, arena: "EventArena", rna: int, pa_out: Optional[tor
     return stat_out, pa_out
 
 
-def prefix(b: DeviceReads, rna: int, pore: int) -> torch.Tensor:
+def prefix(b: DeviceReads, rna: int, pore: int, params: "api.PrefixParams" = None) -> torch.Tensor:
+    """sgk_prefix_opt, or with `params` sgk_prefix_param (`pore` is then ignored: the sets are the caller's)"""
     L = api.load_library()
     out = torch.zeros(max(b.n_reads, 1) * api.PREFIX_DTYPE.itemsize, dtype=torch.uint8, device=b.samples.device)
     view = b.view()
     ws = _workspace(b, "sgk_prefix_workspace_bytes")
+    if params is not None:
+        api.check(api._param_lib().sgk_prefix_param(C.byref(view), int(rna), C.byref(params), _ptr(out), _ptr(ws), ws.numel(),
+                                                    _stream_ptr(), C.addressof(api.STAT_OPTIONS)), "sgk_prefix_param")
+        return out
     api.check(L.sgk_prefix_opt(C.byref(view), int(rna), int(pore), _ptr(out), _ptr(ws), ws.numel(), _stream_ptr(),
                                C.byref(api.STAT_OPTIONS)), "sgk_prefix_opt")
     return out
@@ -301,9 +306,15 @@ class SegArena:
         self.ws = torch.zeros(max(n, 64), dtype=torch.uint8, device=dev)
 
 
-def jnn(b: DeviceReads, arena: SegArena, rna: int) -> None:
+def jnn(b: DeviceReads, arena: SegArena, rna: int, params: "api.JnnParam" = None) -> None:
+    """sgk_jnn_opt, or with `params` sgk_jnn_param (`rna` is then ignored)"""
     L = api.load_library()
     view = b.view()
+    if params is not None:
+        api.check(api._param_lib().sgk_jnn_param(C.byref(view), C.byref(params), _ptr(arena.slots), _ptr(arena.x), _ptr(arena.y),
+                                                 _ptr(arena.n_segs), _ptr(arena.ws), arena.ws.numel(), _stream_ptr(),
+                                                 C.addressof(api.STAT_OPTIONS)), "sgk_jnn_param")
+        return
     api.check(L.sgk_jnn_opt(C.byref(view), int(rna), _ptr(arena.slots), _ptr(arena.x), _ptr(arena.y),
                             _ptr(arena.n_segs), _ptr(arena.ws), arena.ws.numel(), _stream_ptr(), C.byref(api.STAT_OPTIONS)),
               "sgk_jnn_opt")

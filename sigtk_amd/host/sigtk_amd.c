@@ -36,6 +36,7 @@
 #include "blow5.h"
 #include "zstd_dec.h"
 #include "fmt.h"
+#include "segopt.h"
 #include "sref.h"
 #include "ss.h"
 #include "version.h"
@@ -380,6 +381,8 @@ typedef struct {
     int mode, nthreads, host_decode;
     int gpu_text;        /* --gpu-text (pa / event, whole-file mode): the rows come from the GPU as text */
     const sgk_event_params_t *ev_params; /* event --detector: every job's detector parameters (NULL: the presets) */
+    const sgk_jnn_param_t *jnn_params;       /* jnn --segmenter (NULL: the presets) */
+    const sgk_prefix_params_t *prefix_params; /* prefix --adaptor / --polya (NULL: the presets) */
     uint64_t text_bytes; /* ... their bytes over PCIe */
     int zrec;            /* records go to the GPU as they sit in the file (zlib / zstd records, svb-zd or uncompressed signal, auxiliary columns of known types) */
     sgk_aux_field_t *aux_tab; /* ... those columns, in header order */
@@ -1023,9 +1026,12 @@ static void *writer_main(void *arg) {
 
 /* event --detector: a new job takes the command line's detector parameters */
 static void job_detector(const pipe_t *P, sgk_job_t *job) {
-    if (!P->ev_params) return;
-    const int rc = sgk_job_set_event_params(job, P->ev_params);
-    if (rc != SGK_OK) gpu_fail("sgk_job_set_event_params", rc);
+    int rc;
+    if (P->ev_params && (rc = sgk_job_set_event_params(job, P->ev_params)) != SGK_OK) gpu_fail("sgk_job_set_event_params", rc);
+    /* ... and jnn --segmenter, prefix --adaptor / --polya their segmenter parameters */
+    if (P->jnn_params && (rc = sgk_job_set_jnn_params(job, P->jnn_params)) != SGK_OK) gpu_fail("sgk_job_set_jnn_params", rc);
+    if (P->prefix_params && (rc = sgk_job_set_prefix_params(job, P->prefix_params)) != SGK_OK)
+        gpu_fail("sgk_job_set_prefix_params", rc);
 }
 
 /* ------------------------------------------------------------------ reader thread
@@ -1204,6 +1210,7 @@ static struct option long_options[] = {
     {"compact", no_argument, 0, 'c'},       {"gpus", required_argument, 0, 0},   {"batch-samples", required_argument, 0, 0},
     {"threads", required_argument, 0, 't'}, {"host-decode", no_argument, 0, 0},  {"host-inflate", no_argument, 0, 0},
     {"gpu-text", no_argument, 0, 0},        {"aux-slack", required_argument, 0, 0}, {"detector", required_argument, 0, 0},
+    {"segmenter", required_argument, 0, 0}, {"adaptor", required_argument, 0, 0}, {"polya", required_argument, 0, 0},
     {0, 0, 0, 0}};
 
 /* event --detector W1,W2,THR1,THR2,PEAK_HEIGHT: exactly five fields, none empty, nothing behind a number, windows as
@@ -1286,6 +1293,8 @@ static int cmain(int argc, char *argv[], const char *mode_s) {
     int n_gpus = 1, nthreads = 0, host_decode = 0, host_inflate = 0, batch_set = 0, gpu_text = 0;
     uint64_t aux_slack = 256; /* bytes of room per array column of a zlib record sent to the GPU (load_parse) */
     sgk_event_params_t det;   /* event --detector */
+    double seg_v[8], ad_v[5], pl_v[7];   /* jnn --segmenter, prefix --adaptor, prefix --polya */
+    int have_seg = 0, have_ad = 0, have_pl = 0;
     int have_det = 0, verbosity = 0;   /* -v / --verbose: 4 and up names the detector route of event --detector */
     /* default batch: small (16 M samples) where the GPU stage is short -- a job's buffers are then cheap to set up
      * and the host stages overlap sooner; 64 M for jnn / prefix, whose one-read-per-lane kernels take as long for
@@ -1333,6 +1342,63 @@ static int cmain(int argc, char *argv[], const char *mode_s) {
                 exit(EXIT_FAILURE);
             }
             have_det = 1;
+        } else if (c == 0 && longindex >= 15 && longindex <= 17) {
+            static const char *const name[3] = {"--segmenter", "--adaptor", "--polya"}, *const tool[3] = {"jnn", "prefix", "prefix"};
+            static const char *const form[3] = {"STD_SCALE,CORRECTOR,SEG_DIST,WINDOW,STALL_LEN,ERROR[,TOP,BOT] (TOP,BOT exactly when STD_SCALE <= 0)",
+                                                "STD_SCALE,SEG_DIST,WINDOW,HI_THRESH,LO_THRESH", "CORRECTOR,SEG_DIST,WINDOW,STALL_LEN,ERROR,SHIFT,BAND"};
+            const int k = longindex - 15;
+            const char *why = "";
+            if (strcmp(mode_s, tool[k]) != 0) {
+                ERROR("cmain", "%s is an option of the %s subtool", name[k], tool[k]);
+                exit(EXIT_FAILURE);
+            }
+            const int rc = k == 0 ? segopt_segmenter(optarg, seg_v, &why) : k == 1 ? segopt_adaptor(optarg, ad_v, &why) : segopt_polya(optarg, pl_v, &why);
+            if (rc != 0) {
+                ERROR("cmain", "%s wants %s; '%s' has %s", name[k], form[k], optarg, why);
+                exit(EXIT_FAILURE);
+            }
+            if (k == 0) have_seg = 1; else if (k == 1) have_ad = 1; else have_pl = 1;
+        }
+    }
+    /* the domain is the library's (host-only calls): refused before any file is opened */
+    sgk_jnn_param_t seg_p;
+    sgk_prefix_params_t pre_p;
+    memset(&seg_p, 0, sizeof seg_p);
+    memset(&pre_p, 0, sizeof pre_p);
+    if (have_seg) {
+        seg_p.std_scale = (float)seg_v[0]; seg_p.corrector = (int)seg_v[1]; seg_p.seg_dist = (int)seg_v[2]; seg_p.window = (int)seg_v[3];
+        seg_p.stall_len = (float)seg_v[4]; seg_p.error = (int)seg_v[5]; seg_p.top = (float)seg_v[6]; seg_p.bot = (float)seg_v[7];
+        if (sgk_jnn_params_check(&seg_p) != SGK_OK) {
+            ERROR("cmain", "%s", "--segmenter: values out of domain (WINDOW 32 .. 16777216, CORRECTOR >= 1, ERROR >= 0, SEG_DIST >= 0, STALL_LEN >= 0)");
+            exit(EXIT_FAILURE);
+        }
+    }
+    if (have_ad || have_pl) {
+        /* one definition of the domain, the library's: the given sets over a preset (the file's pore, known once it is
+         * open, picks the preset of the set that is not given) */
+        sgk_prefix_params_t chk;
+        sgk_jnn_param_t q;
+        memset(&q, 0, sizeof q);
+        if (sgk_prefix_params_preset(1, SGK_PORE_R9, &chk) != SGK_OK) exit(EXIT_FAILURE);
+        if (have_ad) {
+            chk.adaptor.std_scale = (float)ad_v[0]; chk.adaptor.seg_dist = (int)ad_v[1]; chk.adaptor.window = (int)ad_v[2];
+            chk.adaptor.hi_thresh = (int)ad_v[3]; chk.adaptor.lo_thresh = (int)ad_v[4];
+            if (sgk_prefix_params_check(&chk) != SGK_OK) {
+                ERROR("cmain", "%s", "--adaptor: values out of domain (WINDOW 2 .. 13981, LO_THRESH >= 1, HI_THRESH >= LO_THRESH, SEG_DIST >= 0)");
+                exit(EXIT_FAILURE);
+            }
+        }
+        if (have_pl) {
+            q.std_scale = -1.0f; q.corrector = (int)pl_v[0]; q.seg_dist = (int)pl_v[1]; q.window = (int)pl_v[2];
+            q.stall_len = (float)pl_v[3]; q.error = (int)pl_v[4];
+            chk.polya = q;
+            chk.shift = (float)pl_v[5];
+            chk.band = (float)pl_v[6];
+            if (sgk_prefix_params_check(&chk) != SGK_OK) {
+                ERROR("cmain", "%s", "--polya: values out of domain (WINDOW 32 .. 16777216, CORRECTOR >= 1, ERROR >= 0, SEG_DIST >= 0, STALL_LEN >= 0, BAND >= 0)");
+                exit(EXIT_FAILURE);
+            }
+            pre_p.polya = q;
         }
     }
     if (is_ent && (argc - optind != 1 || fp_help == stdout)) {
@@ -1358,6 +1424,19 @@ static int cmain(int argc, char *argv[], const char *mode_s) {
         fprintf(fp_help, "   --host-inflate             decompress zlib / zstd records on the host threads instead of the GPU\n");
         fprintf(fp_help, "   --gpu-text                 pa / event, whole-file mode: format the rows on the GPU and fetch them as text\n");
         fprintf(fp_help, "   --aux-slack INT            test option\n");
+        if (strcmp(mode_s, "jnn") == 0) {
+            fprintf(fp_help, "   --segmenter STD_SCALE,CORRECTOR,SEG_DIST,WINDOW,STALL_LEN,ERROR[,TOP,BOT]\n");
+            fprintf(fp_help, "                              the segmenter's parameters in place of the presets (WINDOW 32 .. 16777216;\n");
+            fprintf(fp_help, "                              TOP,BOT: the fixed thresholds, given exactly when STD_SCALE <= 0)\n");
+        }
+        if (strcmp(mode_s, "prefix") == 0) {
+            fprintf(fp_help, "   --adaptor STD_SCALE,SEG_DIST,WINDOW,HI_THRESH,LO_THRESH\n");
+            fprintf(fp_help, "                              the adaptor finder's parameters in place of the presets (WINDOW 2 .. 13981)\n");
+            fprintf(fp_help, "   --polya CORRECTOR,SEG_DIST,WINDOW,STALL_LEN,ERROR,SHIFT,BAND\n");
+            fprintf(fp_help, "                              the polyA finder's parameters in place of the presets; its thresholds are\n");
+            fprintf(fp_help, "                              (adaptor mean + SHIFT) +- BAND [30, 20]\n");
+            fprintf(fp_help, "   -v, --verbose INT          4 and up: name the kernels these parameters take\n");
+        }
         exit(fp_help == stdout ? EXIT_SUCCESS : EXIT_FAILURE);
     }
 
@@ -1449,6 +1528,31 @@ static int cmain(int argc, char *argv[], const char *mode_s) {
             fprintf(stderr, "[event] detector route: %s\n", route == SGK_EVENT_ROUTE_PRESET ? "preset" :
                     route == SGK_EVENT_ROUTE_PRESET_WINDOWS ? "preset windows" : "generic");
         }
+    }
+    P.jnn_params = (have_seg && mode == MODE_JNN) ? &seg_p : NULL;
+    if ((have_ad || have_pl) && mode == MODE_PREFIX) {
+        /* the set that is not given stays the preset of the file's pore */
+        sgk_prefix_params_t preset;
+        int rc = sgk_prefix_params_preset(opt.rna, opt.pore, &preset);
+        if (rc != SGK_OK) gpu_fail("sgk_prefix_params_preset", rc);
+        const sgk_jnn_param_t q = pre_p.polya;
+        pre_p = preset;
+        if (have_ad) {
+            pre_p.adaptor.std_scale = (float)ad_v[0]; pre_p.adaptor.seg_dist = (int)ad_v[1]; pre_p.adaptor.window = (int)ad_v[2];
+            pre_p.adaptor.hi_thresh = (int)ad_v[3]; pre_p.adaptor.lo_thresh = (int)ad_v[4];
+        }
+        if (have_pl) {
+            pre_p.polya = q;
+            pre_p.shift = (float)pl_v[5];
+            pre_p.band = (float)pl_v[6];
+        }
+        const int route = sgk_prefix_route(&pre_p);
+        if (route < 0) gpu_fail("sgk_prefix_route", route);
+        if (verbosity >= 4)
+            fprintf(stderr, "[prefix] adaptor route: %s; polyA route: %s\n", (route & SGK_PREFIX_ROUTE_ADAPTOR_PARAM) ? "generic" : "preset",
+                    (route & SGK_PREFIX_ROUTE_POLYA_WAVE_PARAM) ? "wave, parameters" :
+                    (route & SGK_PREFIX_ROUTE_POLYA_LANE_PARAM) ? "lane, parameters" : "preset");
+        P.prefix_params = &pre_p;
     }
     run_pipeline(&P, n_gpus, t_init);
     fflush(stdout);
