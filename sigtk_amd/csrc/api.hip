@@ -386,8 +386,8 @@ int sgk_pa_host(const sgk_host_batch_t *hb, float *pa_out) {
     if (hb->n_reads == 0) return SGK_OK;
     if (!pa_out) return SGK_ERR_ARG;
     DevBuf d_out;
-    if ((rc = d_out.alloc((size_t)db.n_samples * sizeof(float))) != SGK_OK) return rc;
-    if ((rc = sgk_pa(&db.view, d_out.as<float>(), nullptr)) != SGK_OK) return rc;
+    SGK_TRY(d_out.alloc((size_t)db.n_samples * sizeof(float)));
+    SGK_TRY(sgk_pa(&db.view, d_out.as<float>(), nullptr));
     SGK_HIP_TRY(hipDeviceSynchronize());
     for (uint32_t r = 0; r < hb->n_reads; ++r) {
         if (!db.lengths[r]) continue;
@@ -411,12 +411,12 @@ static int event_collect(const void *d_samples, bool float_input, const DeviceBa
     const uint64_t nslots = slots[nr];
     DevBuf d_slots, d_ev, d_nev, d_ws;
     int rc;
-    if ((rc = d_slots.alloc((nr + 1) * sizeof(uint64_t))) != SGK_OK) return rc;
-    if ((rc = d_ev.alloc(nslots * sizeof(sgk_event_rec_t))) != SGK_OK) return rc;
-    if ((rc = d_nev.alloc((size_t)nr * 4)) != SGK_OK) return rc;
+    SGK_TRY(d_slots.alloc((nr + 1) * sizeof(uint64_t)));
+    SGK_TRY(d_ev.alloc(nslots * sizeof(sgk_event_rec_t)));
+    SGK_TRY(d_nev.alloc((size_t)nr * 4));
     const size_t wsb = params ? sgk_event_workspace_bytes_param(nr, db.n_samples, db.max_len, opt, params)
                               : sgk_event_workspace_bytes_opt(nr, db.n_samples, db.max_len, opt);
-    if ((rc = d_ws.alloc(wsb)) != SGK_OK) return rc;
+    SGK_TRY(d_ws.alloc(wsb));
     SGK_HIP_TRY(hipMemcpy(d_slots.p, slots.data(), (nr + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
     // (an uploaded view is a valid batch; the view of pA input has no scaling arrays)
     const EvBatch b = {d_samples, float_input, view->offsets, view->lengths, view->digitisation, view->offset, view->range,

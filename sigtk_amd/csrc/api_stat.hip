@@ -44,8 +44,8 @@ int sgk_stat_opt(const sgk_batch_t *b, sgk_stat_rec_t *out, void *ws, size_t ws_
     a.kernels = opt ? opt->kernels : 0;
     a.long_fault = opt ? opt->debug_fault : 0u;
     a.stat = out;
-    if ((rc = prepare_order(a, ws, ws_bytes, static_cast<hipStream_t>(stream))) != SGK_OK) return rc;
-    if ((rc = prepare_long(a, ws, ws_bytes, opt ? opt->long_min : 0, LC_AUTO_DIV_STAT, static_cast<hipStream_t>(stream))) != SGK_OK) return rc;
+    SGK_TRY(prepare_order(a, ws, ws_bytes, static_cast<hipStream_t>(stream)));
+    SGK_TRY(prepare_long(a, ws, ws_bytes, opt ? opt->long_min : 0, LC_AUTO_DIV_STAT, static_cast<hipStream_t>(stream)));
     prepare_literal(a, ws, ws_bytes);
     return launch_stat(a, static_cast<hipStream_t>(stream));
 }
@@ -66,8 +66,8 @@ int sgk_stat_pa_opt(const sgk_batch_t *b, sgk_stat_rec_t *out, float *pa_out, vo
     a.long_fault = opt ? opt->debug_fault : 0u;
     a.stat = out;
     a.pa_out = pa_out;  // written by the first pass of k_stat_wave (lane-per-read kernels: by the median pass)
-    if ((rc = prepare_order(a, ws, ws_bytes, static_cast<hipStream_t>(stream))) != SGK_OK) return rc;
-    if ((rc = prepare_long(a, ws, ws_bytes, opt ? opt->long_min : 0, LC_AUTO_DIV_STAT, static_cast<hipStream_t>(stream))) != SGK_OK) return rc;
+    SGK_TRY(prepare_order(a, ws, ws_bytes, static_cast<hipStream_t>(stream)));
+    SGK_TRY(prepare_long(a, ws, ws_bytes, opt ? opt->long_min : 0, LC_AUTO_DIV_STAT, static_cast<hipStream_t>(stream)));
     prepare_literal(a, ws, ws_bytes);
     return launch_stat(a, static_cast<hipStream_t>(stream));
 }
@@ -92,8 +92,8 @@ static int jnn_batch(const sgk_batch_t *b, const JnnP &p, const uint64_t *seg_sl
     a.seg_y = seg_y;
     a.n_segs = n_segs;
     a.err_count = static_cast<uint32_t *>(ws);
-    if ((rc = prepare_order(a, ws, ws_bytes, static_cast<hipStream_t>(stream))) != SGK_OK) return rc;
-    if ((rc = prepare_long(a, ws, ws_bytes, opt ? opt->long_min : 0, LC_AUTO_DIV_JNN, static_cast<hipStream_t>(stream))) != SGK_OK) return rc;
+    SGK_TRY(prepare_order(a, ws, ws_bytes, static_cast<hipStream_t>(stream)));
+    SGK_TRY(prepare_long(a, ws, ws_bytes, opt ? opt->long_min : 0, LC_AUTO_DIV_JNN, static_cast<hipStream_t>(stream)));
     return launch_jnn(a, p, static_cast<hipStream_t>(stream));
 }
 
@@ -121,8 +121,8 @@ static int prefix_batch(const sgk_batch_t *b, int rna, const AdaptP &ap, int win
     a.prefix = out;
     // (k_adaptor_param has no long-read split: the long reads' header is cleared and nothing is listed)
     const int32_t long_min = (generic || window != 2000) ? -1 : (opt ? opt->long_min : 0);
-    if ((rc = prepare_order(a, ws, ws_bytes, static_cast<hipStream_t>(stream))) != SGK_OK) return rc;
-    if ((rc = prepare_long(a, ws, ws_bytes, long_min, LC_AUTO_DIV_PREFIX, static_cast<hipStream_t>(stream))) != SGK_OK) return rc;
+    SGK_TRY(prepare_order(a, ws, ws_bytes, static_cast<hipStream_t>(stream)));
+    SGK_TRY(prepare_long(a, ws, ws_bytes, long_min, LC_AUTO_DIV_PREFIX, static_cast<hipStream_t>(stream)));
     prepare_literal(a, ws, ws_bytes);
     return launch_prefix_param(a, rna, ap, window, generic, poly, static_cast<hipStream_t>(stream));
 }
@@ -289,9 +289,9 @@ int sgk_stat_host_opt(const sgk_host_batch_t *hb, sgk_stat_rec_t *out, const sgk
     if (nr == 0) return SGK_OK;
     if (!out) return SGK_ERR_ARG;
     DevBuf d_out, d_ws;
-    if ((rc = d_out.alloc(nr * sizeof(sgk_stat_rec_t))) != SGK_OK) return rc;
-    if ((rc = d_ws.alloc(stat_ws(hb->n_reads, db.view.n_samples, db.view.max_read_len))) != SGK_OK) return rc;
-    if ((rc = sgk_stat_opt(&db.view, d_out.as<sgk_stat_rec_t>(), d_ws.p, stat_ws(hb->n_reads, db.view.n_samples, db.view.max_read_len), nullptr, opt)) != SGK_OK) return rc;
+    SGK_TRY(d_out.alloc(nr * sizeof(sgk_stat_rec_t)));
+    SGK_TRY(d_ws.alloc(stat_ws(hb->n_reads, db.view.n_samples, db.view.max_read_len)));
+    SGK_TRY(sgk_stat_opt(&db.view, d_out.as<sgk_stat_rec_t>(), d_ws.p, stat_ws(hb->n_reads, db.view.n_samples, db.view.max_read_len), nullptr, opt));
     SGK_HIP_TRY(hipDeviceSynchronize());
     SGK_HIP_TRY(hipMemcpy(out, d_out.p, nr * sizeof(sgk_stat_rec_t), hipMemcpyDeviceToHost));
     return SGK_OK;
@@ -308,11 +308,10 @@ int sgk_prefix_host_opt(const sgk_host_batch_t *hb, int rna, int pore, sgk_prefi
     if (nr == 0) return SGK_OK;
     if (!out) return SGK_ERR_ARG;
     DevBuf d_out, d_ws;
-    if ((rc = d_out.alloc(nr * sizeof(sgk_prefix_rec_t))) != SGK_OK) return rc;
-    if ((rc = d_ws.alloc(stat_ws(hb->n_reads, db.view.n_samples, db.view.max_read_len))) != SGK_OK) return rc;
-    if ((rc = sgk_prefix_opt(&db.view, rna, pore, d_out.as<sgk_prefix_rec_t>(), d_ws.p, stat_ws(hb->n_reads, db.view.n_samples, db.view.max_read_len), nullptr,
-                             opt)) != SGK_OK)
-        return rc;
+    SGK_TRY(d_out.alloc(nr * sizeof(sgk_prefix_rec_t)));
+    SGK_TRY(d_ws.alloc(stat_ws(hb->n_reads, db.view.n_samples, db.view.max_read_len)));
+    SGK_TRY(sgk_prefix_opt(&db.view, rna, pore, d_out.as<sgk_prefix_rec_t>(), d_ws.p, stat_ws(hb->n_reads, db.view.n_samples, db.view.max_read_len), nullptr,
+                           opt));
     SGK_HIP_TRY(hipDeviceSynchronize());
     SGK_HIP_TRY(hipMemcpy(out, d_out.p, nr * sizeof(sgk_prefix_rec_t), hipMemcpyDeviceToHost));
     return SGK_OK;
@@ -336,11 +335,11 @@ int sgk_jnn_host_opt(const sgk_host_batch_t *hb, int rna, sgk_segs_host_t *out, 
     const std::vector<uint64_t> slots = make_slots(db.lengths, [](uint32_t n) { return sgk_jnn_slots_for(n); });
     const uint64_t nslots = slots[nr];
     DevBuf d_slots, d_x, d_y, d_n, d_ws;
-    if ((rc = d_slots.alloc((nr + 1) * sizeof(uint64_t))) != SGK_OK) return rc;
-    if ((rc = d_x.alloc(nslots * 4)) != SGK_OK) return rc;
-    if ((rc = d_y.alloc(nslots * 4)) != SGK_OK) return rc;
-    if ((rc = d_n.alloc((size_t)nr * 4)) != SGK_OK) return rc;
-    if ((rc = d_ws.alloc(jnn_ws(nr, db.view.n_samples, db.view.max_read_len))) != SGK_OK) return rc;
+    SGK_TRY(d_slots.alloc((nr + 1) * sizeof(uint64_t)));
+    SGK_TRY(d_x.alloc(nslots * 4));
+    SGK_TRY(d_y.alloc(nslots * 4));
+    SGK_TRY(d_n.alloc((size_t)nr * 4));
+    SGK_TRY(d_ws.alloc(jnn_ws(nr, db.view.n_samples, db.view.max_read_len)));
     SGK_HIP_TRY(hipMemcpy(d_slots.p, slots.data(), (nr + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
     rc = sgk_jnn_opt(&db.view, rna, d_slots.as<uint64_t>(), d_x.as<int32_t>(), d_y.as<int32_t>(), d_n.as<uint32_t>(),
                      d_ws.p, jnn_ws(nr, db.view.n_samples, db.view.max_read_len), nullptr, opt);

@@ -28,6 +28,7 @@
 // (as k_svbzd_encode's does); the bits of the last, partial dword stay for the next tile.  The code builder's node arrays
 // share the stage's LDS: 8.4 KB per stream, which would allow 19 streams per compute unit as k_inflate has; the kernel's 180
 // vector registers allow two waves per SIMD, 8 streams per compute unit, and that is the limit in force.
+#include "job_launch.h"
 #include "sgk_common.h"
 
 namespace sgk {

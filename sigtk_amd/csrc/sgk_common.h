@@ -20,6 +20,12 @@ void set_hip_error(hipError_t e, const char *what, const char *file, int line);
             return SGK_ERR_HIP;                                           \
         }                                                                 \
     } while (0)
+// the same for the project's own calls: a return code other than SGK_OK leaves the enclosing function
+#define SGK_TRY(expr)                                                     \
+    do {                                                                  \
+        const int _rc = (expr);                                           \
+        if (_rc != SGK_OK) return _rc;                                    \
+    } while (0)
 
 // ---- per-kernel timing (sgk_profile_*) ----------------------------------------------
 // RAII: records a hipEvent pair around one kernel launch when profiling is enabled.

@@ -215,12 +215,11 @@ int stat_f32(const float *x, int n, float *out3) {
     if (!x || n <= 0) return SGK_ERR_ARG;
     if (sgk_device_count() <= 0) return SGK_ERR_NODEVICE;
     DevBuf d_x, d_o, d_s;
-    int rc;
-    if ((rc = d_x.alloc((size_t)n * sizeof(float))) != SGK_OK) return rc;
-    if ((rc = d_o.alloc(3 * sizeof(float))) != SGK_OK) return rc;
-    if ((rc = d_s.alloc((size_t)n * sizeof(float))) != SGK_OK) return rc;
+    SGK_TRY(d_x.alloc((size_t)n * sizeof(float)));
+    SGK_TRY(d_o.alloc(3 * sizeof(float)));
+    SGK_TRY(d_s.alloc((size_t)n * sizeof(float)));
     SGK_HIP_TRY(hipMemcpy(d_x.p, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-    if ((rc = launch_stat_f32(d_x.as<float>(), n, d_o.as<float>(), d_s.as<float>(), nullptr)) != SGK_OK) return rc;
+    SGK_TRY(launch_stat_f32(d_x.as<float>(), n, d_o.as<float>(), d_s.as<float>(), nullptr));
     SGK_HIP_TRY(hipDeviceSynchronize());
     SGK_HIP_TRY(hipMemcpy(out3, d_o.p, 3 * sizeof(float), hipMemcpyDeviceToHost));
     return SGK_OK;

@@ -71,7 +71,7 @@ __device__ inline uint32_t text_items(const TextArgs &a, uint32_t r) {
     return n < cap ? n : (uint32_t)cap;  // an overflowing read is written with what fitted, as k_gather_events does
 }
 
-// ---- tiles of every read, one 1024-thread workgroup (the shape of k_layout in job.hip)
+// ---- tiles of every read, one 1024-thread workgroup (the shape of k_layout in job_kernels.hip)
 template <int KIND>
 __global__ __launch_bounds__(1024) void k_text_tiles(TextArgs a) {
     text_tiles_body(a, [&](uint32_t r) { return text_items<KIND>(a, r); });

@@ -64,7 +64,7 @@ static inline bool tile_list_carve(void *w_, size_t bytes, uint32_t n_rows, Tile
 
 #if defined(__HIPCC__)
 
-// ---- tiles of every row, one 1024-thread workgroup (the shape of k_layout in job.hip); items(r) = items of row r
+// ---- tiles of every row, one 1024-thread workgroup (the shape of k_layout in job_kernels.hip); items(r) = items of row r
 template <class Items>
 __device__ inline void text_tiles_body(const TileList &a, Items items) {
     __shared__ uint32_t part[1024];

@@ -17,6 +17,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "job_launch.h"
 #include "sgk_common.h"
 
 namespace sgk {

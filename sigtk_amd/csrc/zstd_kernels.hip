@@ -18,6 +18,7 @@
 //     else from the frame's own bytes in global memory; completed 1 KB chunks of the ring leave as 16-byte stores;
 //   * the content checksum (XXH64), when the frame carries one: its four lanes of stripes on four lanes.
 // Every loop is bounded by input bytes, output room or the declared sequence count: a hostile frame ends with a status.
+#include "job_launch.h"
 #include "sgk_common.h"
 
 #include <map>
