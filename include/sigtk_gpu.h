@@ -1171,6 +1171,48 @@ int sgk_job_set_prefix_params(sgk_job_t *job, const sgk_prefix_params_t *params)
 /* tests: out[i] = the quotient k_adaptor_param forms for the rolling total i, 0 <= i < n (device pointer) */
 int sgk_debug_roll_means(int window, uint32_t n, float *out, void *stream);
 
+/* ---- stat and jnn on batches of float (pA) signals (additive to 0.2.3) -----------------------------------------------
+ * The batched counterparts of meanf / stdvf / medianf (src/stat.h:17-63), jnn_pa (src/jnn.c:295-306) and find_polya
+ * (src/jnn.c:352-374) for signals that are floats already: normalised or rescaled signals, pA kept from sgk_pa /
+ * sgk_stat_pa, the levels of sgk_sref_levels.  (The per-read shims above take one array per call and launch.)
+ * A float batch is x, offsets, lengths, n_reads, max_read_len, n_values, all device pointers: read r is
+ * x[offsets[r] .. offsets[r] + lengths[r]).  x is 4-byte aligned and offsets[r] is ANY element index: no alignment, head
+ * room or tail room is asked of the caller.  Reads may touch but not overlap, in any order; lengths[r] <= max_read_len <
+ * 2^31 (the reference's n is an int: a larger max_read_len is SGK_ERR_ARG); n_values is the readable length of x.
+ * Memory contract: no byte outside [x, x + n_values) is read -- in fact none outside the reads --, no result depends on
+ * a value outside the read's own range, and nothing but the documented outputs and the workspace is written.
+ * One wavefront per read, longest reads first; a read is never split over workgroups: a read of 10^6 values is slow and
+ * right, like k_adaptor_param's.  Both calls are asynchronous on `stream`, allocate nothing and make no host round trip.
+ * The workspace is 16-byte aligned; one smaller than *_workspace_bytes is SGK_ERR_WORKSPACE with nothing written.
+ * Without a GPU they return SGK_ERR_NODEVICE, after the argument checks; n_reads == 0 is SGK_OK.  DESIGN.md 3.18.
+ *
+ * sgk_stat_f32: mean, std, median are bit for bit meanf, stdvf, medianf of the read (sequential float sums in sample
+ * order; the order statistic of rank n / 2; a median that is a zero, and any array holding a NaN, redone with the
+ * reference's own selection; mean and std of an array holding a NaN or an infinity redone with x86's NaN rules).  flags
+ * is 0, or SGK_MEDIAN_INEXACT where such a median found no scratch row (see sgk_stat): never with a workspace of
+ * sgk_stat_f32_workspace_bytes while the read fits SGK_LITERAL_MAX_BYTES.  A read of no values has NaN in all three. */
+typedef struct sgk_statf_rec {
+    float mean, std, median;
+    uint32_t flags;
+} sgk_statf_rec_t; /* 16 bytes */
+size_t sgk_stat_f32_workspace_bytes(uint32_t n_reads, uint64_t n_values, uint32_t max_read_len);
+int sgk_stat_f32(const float *x, const uint64_t *offsets, const uint32_t *lengths, uint32_t n_reads, uint32_t max_read_len,
+                 uint64_t n_values, sgk_statf_rec_t *out, void *workspace, size_t workspace_bytes, void *stream);
+/* sgk_jnn_f32: the segments of read r are bit for bit jnn_pa(x_r, n, *p, &n_segs): rm_outlierf clamps to [0, 1200] (a
+ * NaN passes the clamp and is then out of range), with p->std_scale > 0 the thresholds come from meanf / stdvf of the
+ * clamped values, else they are p->top, p->bot; then jnn_core, every compare in float.  p is checked with
+ * sgk_jnn_params_check (refused: SGK_ERR_ARG before any device work).  top / bot (device, n_reads each, or both NULL;
+ * one of them NULL is SGK_ERR_ARG) give each read its own fixed thresholds and are allowed only with p->std_scale <= 0:
+ * with the polyA preset of a pore the first segment of read r is then find_polya(x_r, n, top[r], bot[r], pore).
+ * The slot arena, sgk_jnn_slots_for, the use of a read's upper slots as scratch and the report of a read that overflowed
+ * its slots (n_segs[r] the true count, the surplus dropped, the uint32 at the start of the workspace the number of such
+ * reads) are those of sgk_jnn_param.  Sets with error < corrector, error <= 31 and window >= 128 run in chunks, a lane
+ * per chunk; the others, and reads whose staging overflowed, take the literal loop, one read per lane. */
+size_t sgk_jnn_f32_workspace_bytes(uint32_t n_reads, uint64_t n_values, uint32_t max_read_len);
+int sgk_jnn_f32(const float *x, const uint64_t *offsets, const uint32_t *lengths, uint32_t n_reads, uint32_t max_read_len,
+                uint64_t n_values, const sgk_jnn_param_t *p, const float *top, const float *bot, const uint64_t *seg_slots,
+                int32_t *seg_x, int32_t *seg_y, uint32_t *n_segs, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -358,6 +358,8 @@ ABI_SYMBOLS = [
     "sgk_prefix_params_preset", "sgk_jnn_params_check", "sgk_prefix_params_check", "sgk_prefix_route", "sgk_jnn_param",
     "sgk_prefix_param", "sgk_jnnv2_param", "sgk_find_polya_param", "sgk_job_set_jnn_params", "sgk_job_set_prefix_params",
     "sgk_debug_roll_means",
+    # stat and jnn on batches of float signals (csrc/statf_kernels.hip, jnnf_kernels.hip)
+    "sgk_stat_f32_workspace_bytes", "sgk_stat_f32", "sgk_jnn_f32_workspace_bytes", "sgk_jnn_f32",
     "sgk_meanf", "sgk_meani16", "sgk_stdvf", "sgk_stdvi16", "sgk_medianf", "sgk_mediani16", "sgk_shim_status",
 ]
 
@@ -784,6 +786,30 @@ def _param_lib():
         L.sgk_find_polya_param.restype = JnnPair
         L.sgk_find_polya_param.argtypes = [C.c_void_p, C.c_int64, C.c_float, C.c_float, JnnParam]
         L._segmenter_params_bound = True
+    return L
+
+
+# ---- stat and jnn on batches of float signals (include/sigtk_gpu.h, csrc/statf_kernels.hip, jnnf_kernels.hip) ----
+class StatFRec(C.Structure):   # sgk_statf_rec_t
+    _fields_ = [("mean", C.c_float), ("std", C.c_float), ("median", C.c_float), ("flags", C.c_uint32)]
+
+
+STATF_DTYPE = np.dtype([("mean", "<f4"), ("std", "<f4"), ("median", "<f4"), ("flags", "<u4")])
+MEDIAN_INEXACT = 4
+
+
+def _float_lib():
+    L = load_library()
+    if not getattr(L, "_float_batch_bound", False):
+        for f in ("sgk_stat_f32_workspace_bytes", "sgk_jnn_f32_workspace_bytes"):
+            getattr(L, f).restype = C.c_size_t
+            getattr(L, f).argtypes = [C.c_uint32, C.c_uint64, C.c_uint32]
+        batch = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64]
+        L.sgk_stat_f32.restype = C.c_int
+        L.sgk_stat_f32.argtypes = batch + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.sgk_jnn_f32.restype = C.c_int
+        L.sgk_jnn_f32.argtypes = batch + [C.POINTER(JnnParam)] + [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p]
+        L._float_batch_bound = True
     return L
 
 

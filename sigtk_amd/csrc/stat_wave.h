@@ -398,13 +398,19 @@ __device__ __forceinline__ uint32_t jnn_long_cap(const StatArgs &a, uint32_t r, 
     const uint64_t cap = a.seg_slots[r + 1] - a.seg_slots[r];
     return (uint32_t)((cap - cap / 2) / (uint32_t)jnn_long_chunks(nq));
 }
-template <typename CAND>
-__device__ __forceinline__ void jnn_chunks(const WaveRead &wr, int64_t n, int hi_r, int lo_r, int error, int keep_min,
-                                           CAND &candidate, int C, int gchunk0) {
+// Where the blocks' in-range masks come from is the SOURCE's business (`src`): JnnSrcRaw below forms them from int16 samples
+// and integer thresholds; the float batch (jnnf_kernels.hip) reads masks it made from floats.  A source has
+//   skew(q)        how far q lies behind the start of its line (the lane's first line is moved back by it)
+//   load_line(q)   requests the line of JW_LINE positions at q (a multiple of JW_LINE behind skew) into the source
+//   block_mask(h)  bit e: position e of block h of the loaded line is in range (positions outside the read: anything)
+// `skip`: q of the read's sample 0.
+template <typename SRC, typename CAND>
+__device__ __forceinline__ void jnn_chunks_src(SRC &src, int skip, int64_t n, int error, int keep_min, CAND &candidate, int C,
+                                               int gchunk0) {
     const int lane = lane_id();
     const int E1 = error + 1;
-    // ---- chunks in q space (q = sample index + wr.skip; chunk bounds are multiples of 8 -> 16-byte aligned loads)
-    const int64_t nq = wr.skip + n;
+    // ---- chunks in q space (q = sample index + skip; chunk bounds are multiples of 8 -> 16-byte aligned loads)
+    const int64_t nq = skip + n;
     const int64_t K = ((nq + C - 1) / C + 7) & ~(int64_t)7;
     const int LEAD = (E1 + 7) & ~7;
     const int gc = gchunk0 + lane;
@@ -462,61 +468,15 @@ __device__ __forceinline__ void jnn_chunks(const WaveRead &wr, int64_t n, int hi
         return (uint32_t)(x >> 32);
     };
 
-    // Every lane streams its own chunk, a whole 128-byte line (two blocks) per step, from a line boundary: the masks of
-    // both blocks are formed first, the next line is requested into the registers that frees, and is in flight under
-    // the automaton's two blocks.  (Round 5.  Until then a lane took 64 bytes per step with the next 64 in flight: the
-    // two halves of a line were requested a whole step apart, 3.6 us during which 4 MB pass through an XCD's 4 MB L2,
-    // and 60 % of the lines were fetched twice -- 15 of the kernel's 90 GB at 125 000 x 100 000, in a kernel that runs
-    // at 5.8 TB/s.  Earlier attempts kept two whole lines per lane in registers: 115 registers instead of 89, four waves
-    // per SIMD instead of five, 16.4 ms against 15.6; the LDS row stager of the lane-per-read kernels lost to its
-    // barriers.)
-    // lo_r < v < hi_r  <=>  lp1 <= v <= hm1 on int16 samples (thresholds beyond the int16 range: always / never)
-    const bool never = hi_r <= -32768 || lo_r >= 32767;
-    const int hm1_i = hi_r - 1 > 32767 ? 32767 : hi_r - 1, lp1_i = lo_r + 1 < -32768 ? -32768 : lo_r + 1;
-    const s16x2 hm1 = {(short)hm1_i, (short)hm1_i}, lp1 = {(short)lp1_i, (short)lp1_i};
-    auto spread16 = [](uint32_t x) {  // bit k -> bit 2k
-        x = (x | (x << 8)) & 0x00FF00FFu;
-        x = (x | (x << 4)) & 0x0F0F0F0Fu;
-        x = (x | (x << 2)) & 0x33333333u;
-        x = (x | (x << 1)) & 0x55555555u;
-        return x;
-    };
-    constexpr int JW_LINE = 2 * JW_BLOCK;  // samples per 128-byte line
-    qb -= (wr.rb + qb) & (int64_t)(JW_LINE - 1);  // (starting earlier only adds to what the sync search knows)
-    uint32_t ln[JW_LINE / 2];
-    auto load_line = [&](int64_t q) {
-        const int64_t last = wr.n_total - 8;
-#pragma unroll
-        for (int v = 0; v < JW_LINE / 8; ++v) {
-            int64_t pp = wr.rb + q + 8 * v;
-            pp = pp < last ? pp : last;
-            pp = pp < 0 ? 0 : pp;
-            const uint4 u = *reinterpret_cast<const uint4 *>(wr.samples + pp);
-            ln[4 * v] = u.x; ln[4 * v + 1] = u.y; ln[4 * v + 2] = u.z; ln[4 * v + 3] = u.w;
-        }
-    };
-    // bit e of the result: lo_r < sample e < hi_r of the block in ln[16 h ..].  Two samples per instruction (one by one
-    // this was 18 issue cycles per sample): saturating packed subtractions leave the sign of (hi_r - 1) - v and of
-    // v - (lo_r + 1) in bits 15 / 31 of a word -- either set: out of range --, the words' flags are collected by
-    // shifting (even samples in the low half, odd ones in the high half) and the two halves interleaved at the end.
-    auto block_mask = [&](int h) -> uint32_t {
-        uint32_t acc = 0u;
-#pragma unroll
-        for (int k = 0; k < JW_BLOCK / 2; ++k) {
-            const s16x2 v = __builtin_bit_cast(s16x2, ln[h * (JW_BLOCK / 2) + k]);
-            const uint32_t d = __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(hm1, v)) |
-                               __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(v, lp1));
-            acc = (d & 0x80008000u) | ((acc >> 1) & 0x7fff7fffu);
-        }
-        return never ? 0u : ~(spread16(acc & 0xffffu) | (spread16(acc >> 16) << 1));
-    };
+    constexpr int JW_LINE = 2 * JW_BLOCK;  // positions per line
+    qb -= src.skew(qb);  // (starting earlier only adds to what the sync search knows)
     // the automaton over the block of 32 samples at q
     auto step = [&](uint32_t inm, int64_t q) {
         const bool busy = active && (srchm | runm) && q < nq;
         if (!busy) return;
         uint32_t vmask = 0xffffffffu;
-        if (q < wr.skip || q + JW_BLOCK > nq) {  // a block on the read's edge
-            const int64_t a0 = wr.skip - q, a1 = nq - q;
+        if (q < skip || q + JW_BLOCK > nq) {  // a block on the read's edge
+            const int64_t a0 = skip - q, a1 = nq - q;
             const int lo = a0 < 0 ? 0 : (a0 > 32 ? 32 : (int)a0), hi = a1 > 32 ? 32 : (a1 < 0 ? 0 : (int)a1);
             vmask = (lo >= 32 ? 0u : (0xffffffffu >> lo) << lo) & (hi >= 32 ? 0xffffffffu : ((1u << hi) - 1u));
         }
@@ -542,20 +502,84 @@ __device__ __forceinline__ void jnn_chunks(const WaveRead &wr, int64_t n, int hi
                 if (m) { hi = __ffs((int)m); ends_here = true; }  // (hi can be 32: the sync sample is the block's last)
             }
         }
-        if (runm && lo < hi) run_block(inm, outm, (int)(q - wr.skip), lo, hi);
+        if (runm && lo < hi) run_block(inm, outm, (int)(q - skip), lo, hi);
         if (ends_here) runm = 0;  // done
         const uint32_t stop = inm | ~vmask;  // samples that are not out of range
         oc = stop ? __clz((int)stop) : oc + 32;
     };
-    load_line(qb);
+    src.load_line(qb);
     for (;;) {
         if (!__any(active && (srchm | runm) && qb < nq)) break;
-        const uint32_t m0 = block_mask(0), m1 = block_mask(1);
-        load_line(qb + JW_LINE);
+        const uint32_t m0 = src.block_mask(0), m1 = src.block_mask(1);
+        src.load_line(qb + JW_LINE);
         step(m0, qb);
         step(m1, qb + JW_BLOCK);
         qb += JW_LINE;
     }
+}
+
+// The source of the int16 kernels: in <=> lo_r < raw < hi_r on the samples of `wr`.
+// Every lane streams its own chunk, a whole 128-byte line (two blocks) per step, from a line boundary: the masks of
+// both blocks are formed first, the next line is requested into the registers that frees, and is in flight under
+// the automaton's two blocks.  (Round 5.  Until then a lane took 64 bytes per step with the next 64 in flight: the
+// two halves of a line were requested a whole step apart, 3.6 us during which 4 MB pass through an XCD's 4 MB L2,
+// and 60 % of the lines were fetched twice -- 15 of the kernel's 90 GB at 125 000 x 100 000, in a kernel that runs
+// at 5.8 TB/s.  Earlier attempts kept two whole lines per lane in registers: 115 registers instead of 89, four waves
+// per SIMD instead of five, 16.4 ms against 15.6; the LDS row stager of the lane-per-read kernels lost to its
+// barriers.)
+struct JnnSrcRaw {
+    static constexpr int JW_LINE = 2 * JW_BLOCK;  // samples per 128-byte line
+    const WaveRead &wr;
+    // lo_r < v < hi_r  <=>  lp1 <= v <= hm1 on int16 samples (thresholds beyond the int16 range: always / never)
+    bool never;
+    s16x2 hm1, lp1;
+    uint32_t ln[JW_LINE / 2];
+    __device__ __forceinline__ JnnSrcRaw(const WaveRead &wr_, int hi_r, int lo_r) : wr(wr_) {
+        never = hi_r <= -32768 || lo_r >= 32767;
+        const int hm1_i = hi_r - 1 > 32767 ? 32767 : hi_r - 1, lp1_i = lo_r + 1 < -32768 ? -32768 : lo_r + 1;
+        hm1 = s16x2{(short)hm1_i, (short)hm1_i};
+        lp1 = s16x2{(short)lp1_i, (short)lp1_i};
+    }
+    __device__ __forceinline__ int64_t skew(int64_t qb) const { return (wr.rb + qb) & (int64_t)(JW_LINE - 1); }
+    __device__ __forceinline__ void load_line(int64_t q) {
+        const int64_t last = wr.n_total - 8;
+#pragma unroll
+        for (int v = 0; v < JW_LINE / 8; ++v) {
+            int64_t pp = wr.rb + q + 8 * v;
+            pp = pp < last ? pp : last;
+            pp = pp < 0 ? 0 : pp;
+            const uint4 u = *reinterpret_cast<const uint4 *>(wr.samples + pp);
+            ln[4 * v] = u.x; ln[4 * v + 1] = u.y; ln[4 * v + 2] = u.z; ln[4 * v + 3] = u.w;
+        }
+    }
+    static __device__ __forceinline__ uint32_t spread16(uint32_t x) {  // bit k -> bit 2k
+        x = (x | (x << 8)) & 0x00FF00FFu;
+        x = (x | (x << 4)) & 0x0F0F0F0Fu;
+        x = (x | (x << 2)) & 0x33333333u;
+        x = (x | (x << 1)) & 0x55555555u;
+        return x;
+    }
+    // bit e of the result: lo_r < sample e < hi_r of the block in ln[16 h ..].  Two samples per instruction (one by one
+    // this was 18 issue cycles per sample): saturating packed subtractions leave the sign of (hi_r - 1) - v and of
+    // v - (lo_r + 1) in bits 15 / 31 of a word -- either set: out of range --, the words' flags are collected by
+    // shifting (even samples in the low half, odd ones in the high half) and the two halves interleaved at the end.
+    __device__ __forceinline__ uint32_t block_mask(int h) const {
+        uint32_t acc = 0u;
+#pragma unroll
+        for (int k = 0; k < JW_BLOCK / 2; ++k) {
+            const s16x2 v = __builtin_bit_cast(s16x2, ln[h * (JW_BLOCK / 2) + k]);
+            const uint32_t d = __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(hm1, v)) |
+                               __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(v, lp1));
+            acc = (d & 0x80008000u) | ((acc >> 1) & 0x7fff7fffu);
+        }
+        return never ? 0u : ~(spread16(acc & 0xffffu) | (spread16(acc >> 16) << 1));
+    }
+};
+template <typename CAND>
+__device__ __forceinline__ void jnn_chunks(const WaveRead &wr, int64_t n, int hi_r, int lo_r, int error, int keep_min,
+                                           CAND &candidate, int C, int gchunk0) {
+    JnnSrcRaw src(wr, hi_r, lo_r);
+    jnn_chunks_src(src, wr.skip, n, error, keep_min, candidate, C, gchunk0);
 }
 
 // The merge of the kept segments (src/jnn.c:246-258), 64 chunks per round, in chunk order.  A chunk's kept segments are

@@ -320,6 +320,103 @@ def jnn(b: DeviceReads, arena: SegArena, rna: int, params: "api.JnnParam" = None
               "sgk_jnn_opt")
 
 
+# ---------------------------------------------------------------------- float (pA) batches: sgk_stat_f32, sgk_jnn_f32
+@dataclass
+class FloatReads:
+    """A batch of float signals resident in HBM: read r is x[offsets[r] : offsets[r] + lengths[r]], at any element
+    offset.  `x` may be a view that starts at any element of its storage (4-byte alignment is all the library asks)."""
+    x: torch.Tensor         # float32 [n_values]
+    offsets: torch.Tensor   # int64 (uint64 bits) [n_reads]
+    lengths: torch.Tensor   # int32 (uint32 bits) [n_reads]
+    n_reads: int
+    max_read_len: int
+    n_values: int
+    offsets_host: np.ndarray
+    lengths_host: np.ndarray
+
+    def view(self):
+        """the six leading arguments of sgk_stat_f32 / sgk_jnn_f32"""
+        return (_ptr(self.x), _ptr(self.offsets), _ptr(self.lengths), self.n_reads, self.max_read_len, self.n_values)
+
+
+def float_reads(x: torch.Tensor, offsets, lengths) -> FloatReads:
+    """A float batch over values that are on the device already (pA from sgk_pa, a normalised signal ...)."""
+    offsets = np.asarray(offsets, dtype=np.int64)
+    lengths = np.asarray(lengths, dtype=np.int64)
+    assert x.dtype == torch.float32 and x.is_contiguous() and offsets.size == lengths.size
+    assert lengths.size == 0 or (int(lengths.min()) >= 0 and int((offsets + lengths).max()) <= x.numel())
+    n = max(lengths.size, 1)
+    off_d = torch.zeros(n, dtype=torch.int64, device=x.device)
+    len_d = torch.zeros(n, dtype=torch.int32, device=x.device)
+    off_d[:offsets.size] = torch.from_numpy(offsets)
+    len_d[:lengths.size] = torch.from_numpy(lengths.astype(np.int32))
+    return FloatReads(x=x, offsets=off_d, lengths=len_d, n_reads=int(lengths.size),
+                      max_read_len=int(lengths.max()) if lengths.size else 0, n_values=int(x.numel()),
+                      offsets_host=offsets.astype(np.uint64), lengths_host=lengths.astype(np.uint32))
+
+
+def upload_float_reads(arrays, device: torch.device, leads=None, fill=None) -> FloatReads:
+    """Float arrays packed one behind the other.  leads[r] is the number of gap elements in front of read r (default
+    0: the reads touch), `fill` what the gaps hold (default 0.0).  The allocation ends with the last read."""
+    arrays = [np.ascontiguousarray(a, dtype=np.float32) for a in arrays]
+    lens = np.array([a.size for a in arrays], dtype=np.int64)
+    lead = np.zeros(lens.size, dtype=np.int64) if leads is None else np.asarray(leads, dtype=np.int64)
+    assert lead.size == lens.size and (lens.size == 0 or int(lead.min()) >= 0)
+    offsets = np.cumsum(lead + lens) - lens
+    host = np.full(int((lead + lens).sum()), 0.0 if fill is None else fill, dtype=np.float32)
+    for a, o in zip(arrays, offsets.tolist()):
+        host[o:o + a.size] = a
+    return float_reads(torch.from_numpy(host).to(device), offsets, lens)
+
+
+def _float_workspace(fb: FloatReads, size_fn_name: str) -> torch.Tensor:
+    n = int(getattr(api._float_lib(), size_fn_name)(fb.n_reads, fb.n_values, fb.max_read_len))
+    return torch.zeros(max(n, 64), dtype=torch.uint8, device=fb.x.device)
+
+
+def stat_f32(fb: FloatReads, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sgk_stat_f32 -> uint8 tensor holding n_reads sgk_statf_rec_t (view it with api.STATF_DTYPE)."""
+    L = api._float_lib()
+    out = torch.zeros(max(fb.n_reads, 1) * api.STATF_DTYPE.itemsize, dtype=torch.uint8, device=fb.x.device)
+    if ws is None:
+        ws = _float_workspace(fb, "sgk_stat_f32_workspace_bytes")
+    api.check(L.sgk_stat_f32(*fb.view(), _ptr(out), _ptr(ws), ws.numel(), _stream_ptr()), "sgk_stat_f32")
+    return out
+
+
+class FloatSegArena:
+    """The segment arena of sgk_jnn_f32 (SegArena's layout): sgk_jnn_slots_for(n) slots per read, or the caller's
+    `slots` (n_reads + 1 increasing slot indices)."""
+
+    def __init__(self, fb: FloatReads, slots=None):
+        dev = fb.x.device
+        if slots is None:
+            slots = np.zeros(fb.n_reads + 1, dtype=np.int64)
+            np.cumsum(fb.lengths_host.astype(np.int64) // 32 + 2, out=slots[1:])
+        slots = np.asarray(slots, dtype=np.int64)
+        assert slots.size == fb.n_reads + 1
+        self.slots_host = slots
+        self.slots = torch.from_numpy(slots).to(dev)
+        self.x = torch.empty(max(int(slots[-1]), 1), dtype=torch.int32, device=dev)
+        self.y = torch.empty(max(int(slots[-1]), 1), dtype=torch.int32, device=dev)
+        self.n_segs = torch.zeros(max(fb.n_reads, 1), dtype=torch.int32, device=dev)
+        self.ws = _float_workspace(fb, "sgk_jnn_f32_workspace_bytes")
+
+    def n_overflowed(self) -> int:
+        """reads whose segments overflowed their slots in the last call (synchronises)"""
+        return int(self.ws[:4].cpu().numpy().view(np.uint32)[0])
+
+
+def jnn_f32(fb: FloatReads, arena: FloatSegArena, params: "api.JnnParam", top: Optional[torch.Tensor] = None,
+            bot: Optional[torch.Tensor] = None) -> None:
+    """sgk_jnn_f32: jnn_pa of every read with `params`; top / bot (float32 tensors, one value per read) give each read
+    its own fixed thresholds (params.std_scale <= 0)."""
+    L = api._float_lib()
+    api.check(L.sgk_jnn_f32(*fb.view(), C.byref(params), _ptr(top), _ptr(bot), _ptr(arena.slots), _ptr(arena.x),
+                            _ptr(arena.y), _ptr(arena.n_segs), _ptr(arena.ws), arena.ws.numel(), _stream_ptr()),
+              "sgk_jnn_f32")
+
+
 def pa(b: DeviceReads, out: torch.Tensor) -> None:
     L = api.load_library()
     view = b.view()
