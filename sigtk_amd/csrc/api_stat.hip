@@ -170,11 +170,6 @@ int sgk_prefix_params_preset(int rna, int pore, sgk_prefix_params_t *out) {
     return SGK_OK;
 }
 static bool same_bits(float a, float b) { return memcmp(&a, &b, 4) == 0; }
-static AdaptP to_adaptp(const sgk_jnnv2_param_t &v) {
-    AdaptP ap;
-    ap.std_scale = v.std_scale; ap.seg_dist = v.seg_dist; ap.lo_thresh = v.lo_thresh; ap.hi_thresh = v.hi_thresh;
-    return ap;
-}
 static PolyP to_polyp(const sgk_prefix_params_t *p) {
     PolyP q;
     q.p.std_scale = -1.0f; q.p.corrector = p->polya.corrector; q.p.seg_dist = p->polya.seg_dist; q.p.window = p->polya.window;
@@ -204,10 +199,7 @@ int sgk_prefix_route(const sgk_prefix_params_t *p) {
 int sgk_jnn_param(const sgk_batch_t *b, const sgk_jnn_param_t *p, const uint64_t *seg_slots, int32_t *seg_x, int32_t *seg_y,
                   uint32_t *n_segs, void *ws, size_t ws_bytes, void *stream, const sgk_stat_options_t *opt) {
     if (sgk_jnn_params_check(p) != SGK_OK) return SGK_ERR_ARG;
-    JnnP q;
-    q.std_scale = p->std_scale; q.corrector = p->corrector; q.seg_dist = p->seg_dist; q.window = p->window;
-    q.stall_len = p->stall_len; q.error = p->error; q.top = p->top; q.bot = p->bot;
-    return jnn_batch(b, q, seg_slots, seg_x, seg_y, n_segs, ws, ws_bytes, stream, opt);
+    return jnn_batch(b, to_jnnp(*p), seg_slots, seg_x, seg_y, n_segs, ws, ws_bytes, stream, opt);
 }
 
 int sgk_prefix_param(const sgk_batch_t *b, int rna, const sgk_prefix_params_t *p, sgk_prefix_rec_t *out, void *ws, size_t ws_bytes,

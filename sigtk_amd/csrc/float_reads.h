@@ -1,5 +1,6 @@
 // float_reads.h -- a batch of float (pA) reads on the device, one WAVE per read: what sgk_stat_f32 (statf_kernels.hip) and
-// sgk_jnn_f32 (jnnf_kernels.hip) share.
+// sgk_jnn_f32 (jnnf_kernels.hip) share.  sgk_meanf / sgk_stdvf / sgk_medianf (shims.hip) are a batch of one read on
+// launch_statf; sgk_jnn_pa keeps a single-array kernel of its own (shims.hip says why).
 //
 // A float batch is x, offsets, lengths: read r is x[offsets[r] .. offsets[r] + lengths[r]); x is 4-byte aligned and an
 // offset is any element index.  The wave works in q space: q = i + skip, where skip (0 .. 3) is the number of elements
@@ -66,6 +67,9 @@ struct FloatRead {  // wave-uniform
 // ORDER_MIN_READS reads or more, sorted into the workspace at ws + 64 (order_workspace_bytes)
 int float_batch_check(const float *x, const uint64_t *offsets, const uint32_t *lengths, uint32_t n_reads, uint32_t max_read_len);
 int float_batch_order(FloatBatch &b, void *ws, hipStream_t st);
+// What sgk_stat_f32 launches once its arguments are checked (b.order is the launcher's to fill; ws: 16-byte aligned, of
+// the size sgk_stat_f32_workspace_bytes gives).  The float stat shims call it directly.
+int launch_statf(FloatBatch b, uint32_t max_read_len, sgk_statf_rec_t *out, void *ws, hipStream_t st);
 
 // the read a wave takes: four waves per workgroup, longest reads first where the batch has a dispatch order
 __device__ __forceinline__ bool float_wave_read(const FloatBatch &b, uint32_t &r) {
@@ -89,10 +93,10 @@ __device__ __forceinline__ void fr_sweep(const FloatRead &fr, F f) {
     }
 }
 
-// One sequential float sum of the reference over the read: term(x[i]) for i = 0 .. n - 1 in sample order (seqsum.h; the
-// form of ss_chain_f32 of shims.hip on tiles that start at a 16-byte boundary).  Terms can have any sign: the chain is
-// oriented by the sign of its accumulator, tiles holding a term of the other sign, a NaN or an infinity are added
-// natively.  side(t, v, vm) sees every tile's values first (histograms, flags).
+// One sequential float sum of the reference over the read: term(x[i]) for i = 0 .. n - 1 in sample order (seqsum.h, on
+// tiles that start at a 16-byte boundary).  Terms can have any sign: the chain is oriented by the sign of its
+// accumulator, tiles holding a term of the other sign, a NaN or an infinity are added natively.  side(t, v, vm) sees
+// every tile's values first (histograms, flags).
 template <typename TERM, typename SIDE>
 __device__ inline float fr_chain(const FloatRead &fr, TERM term, SIDE side) {
     const int q0 = lane_id() * SS_SPL;

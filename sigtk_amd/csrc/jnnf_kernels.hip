@@ -194,9 +194,7 @@ int sgk_jnn_f32(const float *x, const uint64_t *offsets, const uint32_t *lengths
     if (ws_bytes < jnnf_ws(n_reads, n_values)) return SGK_ERR_WORKSPACE;
     if (sgk_device_count() <= 0) return SGK_ERR_NODEVICE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    JnnP q;
-    q.std_scale = p->std_scale; q.corrector = p->corrector; q.seg_dist = p->seg_dist; q.window = p->window;
-    q.stall_len = p->stall_len; q.error = p->error; q.top = p->top; q.bot = p->bot;
+    const JnnP q = to_jnnp(*p);
     char *w = static_cast<char *>(ws);
     SGK_HIP_TRY(hipMemsetAsync(w, 0, 64, st));
     FloatBatch b = {x, offsets, lengths, n_reads, nullptr};

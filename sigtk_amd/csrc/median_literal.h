@@ -58,7 +58,7 @@ __device__ inline T literal_select(T *a, int64_t n, int64_t k, LT lt) {
 // operand (the NaN's sign flips), its correctly rounded division and square root are instruction sequences, and the wave
 // kernels' sums are oriented (seqsum.h): the value is a NaN either way, its sign bit is not the reference's.  Reads whose
 // unit or offset is not finite -- only those can hold a NaN -- get their pA mean and deviation redone by one lane with
-// every operation spelled the x86 way (k_median_literal, k_stat_f32); everywhere else the results are identical.
+// every operation spelled the x86 way (k_median_literal, k_statf_literal); everywhere else the results are identical.
 // (The FIRST NaN operand: that is the order in which the reference binary this project records its goldens from -- gcc -O2,
 // oracle/Makefile -- hands the operands of `sum += x[i]`, `x[i] - m` and `d * d` to the instruction.  A compiler may swap the
 // operands of an addition or a multiplication, so where both are NaNs of different signs -- float arrays with NaNs of both

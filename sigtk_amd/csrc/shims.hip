@@ -1,19 +1,19 @@
 // shims.hip -- per-read entry points with the reference's own signatures (SURVEY.md 8b "signatures to keep"):
 // jnn_raw / jnn_pa / jnnv2 / find_adaptor / find_polya (src/jnn.h:104-109) and the six stat.h inlines
-// (src/stat.h:17-73).  Each is a batch of one over the batched kernels (or, for float input, over the single-array
-// compatibility kernels k_jnn_f32 / k_stat_f32 below); results are malloc'd by the callee and freed by the caller, as in the
-// reference.  They exist so that a maintainer can diff every function against the original; throughput comes from
-// the batch API.  On any failure (no device, out of memory, unsupported parameter) they return NULL / {-1,-1} / NaN
-// and sgk_shim_status() tells why.
+// (src/stat.h:17-73).  Each is a batch of one over the batched kernels -- meanf / stdvf / medianf included, on the
+// kernels of sgk_stat_f32 -- but for jnn_pa, which keeps the single-array kernel k_jnn_f32 below: sets on the literal
+// loop of sgk_jnn_f32 take 11 % longer per call on a batch of one than on it (profiles/float_shims.md).  Results are
+// malloc'd by the callee and freed by the caller, as in the reference.  They exist so that a maintainer can diff every
+// function against the original; throughput comes from the batch API.  On any failure (no device, out of memory,
+// unsupported parameter) they return NULL / {-1,-1} / NaN and sgk_shim_status() tells why.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <vector>
 
+#include "float_reads.h"
 #include "host_util.h"
-#include "median_literal.h"
-#include "seqsum.h"
 #include "sgk_common.h"
 #include "stat_args.h"
 #include "stat_device.h"
@@ -54,113 +54,11 @@ __global__ __launch_bounds__(64) void k_jnn_f32(const float *x, int64_t n, JnnP 
     }
 }
 
-// meanf / stdvf / medianf (src/stat.h:17-27, 36-44, 56-63) of ONE float array, for the reference-signature shims:
-// the sequential float sums on every lane of the wave (lane 0 stores), the order statistic of rank n/2 by a
-// three-level (11 + 11 + 10 bit) radix select on the order-preserving integer image of the floats.
-// one seqsum.h chain over a float array: term(x[i]) for i = 0 .. n-1, by one wave (the other waves of the workgroup
-// skip it).  Terms can have any sign: the chain is oriented by the sign of its accumulator, tiles holding a term of
-// the other sign are added natively.
-template <typename F>
-__device__ float ss_chain_f32(const float *x, int n, F term) {
-    const int lane = lane_id(), q0 = lane * SS_SPL;
-    float m = 0.0f, sg = 1.0f;
-    const int ntiles = (n + SS_TILE - 1) / SS_TILE;
-    const int head = n < SS_HEAD ? n : SS_HEAD;
-    for (int t = 0; t < ntiles; ++t) {
-        float v[SS_SPL], y[SS_SPL];
-#pragma unroll
-        for (int e = 0; e < SS_SPL; ++e) {
-            const int i = t * SS_TILE + q0 + e;
-            v[e] = i < n ? term(x[i]) * sg : 0.0f;  // (* +-1: exact)
-        }
-        if (t == 0) {  // the head natively; its terms are zeroed for the tile chain
-#pragma unroll
-            for (int e = 0; e < SS_SPL; ++e) y[e] = (q0 + e < head) ? v[e] : 0.0f;
-            if (head > 0) m = ss_serial(m, TermArr{y}, 0, (head - 1) / SS_SPL);
-#pragma unroll
-            for (int e = 0; e < SS_SPL; ++e) v[e] = (q0 + e < head) ? 0.0f : v[e];
-        }
-        const SsWalk w = ss_walk<true>(m, TermArr{v});
-        int sk;
-        if (ss_fast<true>(m, w, TermArr{v}, sk)) m = ss_finish<true>(m, TermArr{v}, w, sk);
-        if (m < 0.0f) { m = -m; sg = -sg; }
-    }
-    return m == 0.0f ? 0.0f : m * sg;
-}
-
-// The median: a three-level radix on the floats' bit keys finds the VALUE of rank n / 2.  Where that is a zero (+0 and -0
-// compare equal) or the array holds a NaN (which orders with nothing), the reference's median is the element its own
-// selection leaves at n / 2: redone literally by one lane on `scratch`, a copy of the array (median_literal.h).  An array
-// with a NaN or an infinity in it also gets its mean and deviation redone by that lane, for the sign of their NaN.
-__global__ __launch_bounds__(256) void k_stat_f32(const float *x, int n, float *out3, float *scratch) {
-    __shared__ uint32_t hist[2048];
-    __shared__ uint32_t sel_prefix, sel_rank, has_nan;
-    if (threadIdx.x == 0) has_nan = 0u;
-    if (threadIdx.x < 64) {  // wave 0: the sequential float sums through seqsum.h
-        const float s = ss_chain_f32(x, n, [](float v) { return v; });
-        const float mn = s / n;
-        const float q = ss_chain_f32(x, n, [&](float v) { return (v - mn) * (v - mn); });
-        if (threadIdx.x == 0) { out3[0] = mn; out3[1] = sqrtf(q / n); }
-    }
-    auto key = [](float f) -> uint32_t {
-        const uint32_t u = __float_as_uint(f);
-        return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    };
-    uint32_t prefix = 0u, rank = (uint32_t)(n / 2);
-    const int shifts[3] = {21, 10, 0};
-    const int bitsn[3] = {11, 11, 10};
-    uint32_t known = 0u;  // mask of the key bits fixed so far
-    for (int lvl = 0; lvl < 3; ++lvl) {
-        for (int k = threadIdx.x; k < 2048; k += 256) hist[k] = 0u;
-        __syncthreads();
-        for (int j = threadIdx.x; j < n; j += 256) {
-            const float xj = x[j];
-            if (lvl == 0 && !(fabsf(xj) < __builtin_inff())) atomicOr(&has_nan, xj != xj ? 3u : 1u);   // (1: not finite, 2: a NaN)
-            const uint32_t kk = key(xj);
-            if ((kk & known) == prefix) atomicAdd(&hist[(kk >> shifts[lvl]) & ((1u << bitsn[lvl]) - 1u)], 1u);
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint32_t acc = 0u, b = 0u;
-            const uint32_t nb = 1u << bitsn[lvl];
-            for (; b < nb; ++b) {
-                if (acc + hist[b] > rank) break;
-                acc += hist[b];
-            }
-            sel_prefix = prefix | (b << shifts[lvl]);
-            sel_rank = rank - acc;
-        }
-        __syncthreads();
-        prefix = sel_prefix;
-        rank = sel_rank;
-        known |= ((1u << bitsn[lvl]) - 1u) << shifts[lvl];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        const uint32_t u = (prefix & 0x80000000u) ? (prefix & 0x7fffffffu) : ~prefix;
-        out3[2] = __uint_as_float(u);
-        sel_rank = (__uint_as_float(u) == 0.0f || (has_nan & 2u)) ? 1u : 0u;
-        if (has_nan) x86_mean_std((int64_t)n, [&](int64_t i) { return x[i]; }, out3[0], out3[1]);
-    }
-    __syncthreads();
-    if (sel_rank) {  // (workgroup-uniform)
-        for (int j = threadIdx.x; j < n; j += 256) scratch[j] = x[j];
-        __syncthreads();
-        if (threadIdx.x == 0) out3[2] = literal_select(scratch, (int64_t)n, (int64_t)(n / 2), [](float p, float q) { return p < q; });
-    }
-}
-
-static int launch_stat_f32(const float *x, int n, float *out3, float *scratch, hipStream_t st) {
-    SGK_LAUNCH("k_stat_f32", k_stat_f32, 1, 256, st, x, n, out3, scratch);
-    return SGK_OK;
-}
-
 static int launch_jnn_f32(const float *x, int64_t n, const JnnP &p, int32_t *seg_x, int32_t *seg_y, uint32_t cap,
                           uint32_t *n_segs, hipStream_t st) {
     SGK_LAUNCH("k_jnn_f32", k_jnn_f32, 1, 64, st, x, n, p, seg_x, seg_y, cap, n_segs);
     return SGK_OK;
 }
-
 
 }  // namespace sgk
 
@@ -169,13 +67,6 @@ using namespace sgk;
 static thread_local int g_shim_rc = SGK_OK;
 
 namespace {
-
-JnnP to_jnnp(const sgk_jnn_param_t &q) {
-    JnnP p;
-    p.std_scale = q.std_scale; p.corrector = q.corrector; p.seg_dist = q.seg_dist; p.window = q.window;
-    p.stall_len = q.stall_len; p.error = q.error; p.top = q.top; p.bot = q.bot;
-    return p;
-}
 
 // one int16 read on the device, 64-sample aligned with room around it
 int upload_one(const int16_t *raw, int64_t n, DeviceBatch &db) {
@@ -211,31 +102,88 @@ int stat_i16(const int16_t *x, int n, sgk_stat_rec_t *rec) {
     return sgk_stat_host(&hb, rec);
 }
 
+// meanf / stdvf / medianf of one float array: a batch of one read on the kernels of sgk_stat_f32.  The read is the
+// array at element 0 of an allocation of its own; a second one holds this head -- what the launcher reads of the batch
+// (offset, length) and the record it writes -- with the workspace behind it.
+struct OneRead {
+    uint64_t offset;   // 0
+    uint32_t length, pad0;
+    sgk_statf_rec_t rec;
+    uint32_t pad[8];
+};
+static_assert(sizeof(OneRead) == 64, "the workspace behind it is 16-byte aligned");
+
 int stat_f32(const float *x, int n, float *out3) {
     if (!x || n <= 0) return SGK_ERR_ARG;
     if (sgk_device_count() <= 0) return SGK_ERR_NODEVICE;
-    DevBuf d_x, d_o, d_s;
+    OneRead h = {};
+    h.length = (uint32_t)n;
+    DevBuf d_x, d_w;
     SGK_TRY(d_x.alloc((size_t)n * sizeof(float)));
-    SGK_TRY(d_o.alloc(3 * sizeof(float)));
-    SGK_TRY(d_s.alloc((size_t)n * sizeof(float)));
+    SGK_TRY(d_w.alloc(sizeof h + sgk_stat_f32_workspace_bytes(1, h.length, h.length)));
     SGK_HIP_TRY(hipMemcpy(d_x.p, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-    SGK_TRY(launch_stat_f32(d_x.as<float>(), n, d_o.as<float>(), d_s.as<float>(), nullptr));
+    SGK_HIP_TRY(hipMemcpy(d_w.p, &h, sizeof h, hipMemcpyHostToDevice));
+    OneRead *d = d_w.as<OneRead>();
+    SGK_TRY(launch_statf(FloatBatch{d_x.as<float>(), &d->offset, &d->length, 1u, nullptr}, h.length, &d->rec, d + 1, nullptr));
     SGK_HIP_TRY(hipDeviceSynchronize());
-    SGK_HIP_TRY(hipMemcpy(out3, d_o.p, 3 * sizeof(float), hipMemcpyDeviceToHost));
+    SGK_HIP_TRY(hipMemcpy(&h, d, sizeof h, hipMemcpyDeviceToHost));
+    out3[0] = h.rec.mean; out3[1] = h.rec.std; out3[2] = h.rec.median;
     return SGK_OK;
 }
 
-}  // namespace
-
 // a per-read call on a long read takes the long-read path of the batch API as well (a 3 000 001-sample read: 1 ms instead
 // of 10): the workspace it needs, sized for this one read
-static int shim_long(StatArgs &a, DevBuf &ws, LongRule auto_div) {
+int shim_long(StatArgs &a, DevBuf &ws, LongRule auto_div) {
     if (a.b.max_read_len < LC_LONG_MIN / 2) return SGK_OK;   // (the lowest per-batch threshold, stat_args.h: LongRule)
     const size_t bytes = order_workspace_bytes(a.b.n_reads) + long_workspace_bytes(a.b.n_samples, a.b.max_read_len);
     int rc = ws.alloc(bytes);
     if (rc != SGK_OK) return rc;
     return prepare_long(a, ws.p, bytes, 0, auto_div, nullptr);
 }
+
+// jnnv2 of one read, what sgk_jnnv2 and sgk_jnnv2_param share behind their domain checks: upload, the record, the
+// launch -- launch(a, ap, ws): the caller's finder, ws for what it needs on the device until the call is over -- and the
+// read-back
+template <typename Launch>
+sgk_jnn_pair_t jnnv2_one(const int16_t *sig, int64_t nsample, const sgk_jnnv2_param_t &param, Launch launch) {
+    sgk_jnn_pair_t p = {-1, -1};
+    if (nsample <= param.window) return p;  // "Not enough data to trim" (src/jnn.c:172-176)
+    if (!sig) { g_shim_rc = SGK_ERR_ARG; return p; }
+    DeviceBatch db;
+    if ((g_shim_rc = upload_one(sig, nsample, db)) != SGK_OK) return p;
+    DevBuf d_out, d_ws;
+    if ((g_shim_rc = d_out.alloc(sizeof(sgk_prefix_rec_t))) != SGK_OK) return p;
+    StatArgs a;
+    memset(&a, 0, sizeof a);
+    a.b = db.view;
+    a.prefix = d_out.as<sgk_prefix_rec_t>();
+    if ((g_shim_rc = launch(a, to_adaptp(param), d_ws)) != SGK_OK) return p;
+    sgk_prefix_rec_t rec;
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&rec, d_out.p, sizeof rec, hipMemcpyDeviceToHost) != hipSuccess) {
+        g_shim_rc = SGK_ERR_HIP;
+        return p;
+    }
+    p.x = rec.adapt_x;
+    p.y = rec.adapt_y;
+    return p;
+}
+
+// find_polya (src/jnn.c:352-374): the first segment of jnn_pa with `core` on the fixed thresholds top, bot
+sgk_jnn_pair_t polya_one(const float *raw, int64_t nsample, float top, float bot, sgk_jnn_param_t core) {
+    sgk_jnn_pair_t p = {-1, -1};
+    core.std_scale = -1.0f;  // the fixed thresholds
+    core.top = top;
+    core.bot = bot;
+    int ns = 0;
+    sgk_jnn_pair_t *segs = sgk_jnn_pa(raw, nsample, core, &ns);
+    if (segs) {
+        if (ns > 0) p = segs[0];
+        free(segs);
+    }
+    return p;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -307,81 +255,32 @@ sgk_jnn_pair_t *sgk_jnn_pa(const float *raw, int64_t nsample, sgk_jnn_param_t pa
 }
 
 sgk_jnn_pair_t sgk_jnnv2(const int16_t *sig, int64_t nsample, sgk_jnnv2_param_t param) {
-    sgk_jnn_pair_t p = {-1, -1};
     g_shim_rc = SGK_OK;
-    if (param.window != 2000) { g_shim_rc = SGK_ERR_ARG; return p; }  // both presets of the reference (src/jnn.h:84-98)
-    if (nsample <= param.window) return p;  // "Not enough data to trim" (src/jnn.c:172-176)
-    if (!sig) { g_shim_rc = SGK_ERR_ARG; return p; }
-    DeviceBatch db;
-    if ((g_shim_rc = upload_one(sig, nsample, db)) != SGK_OK) return p;
-    DevBuf d_out;
-    if ((g_shim_rc = d_out.alloc(sizeof(sgk_prefix_rec_t))) != SGK_OK) return p;
-    StatArgs a;
-    memset(&a, 0, sizeof a);
-    a.b = db.view;
-    a.prefix = d_out.as<sgk_prefix_rec_t>();
-    AdaptP ap;
-    ap.std_scale = param.std_scale; ap.seg_dist = param.seg_dist; ap.lo_thresh = param.lo_thresh; ap.hi_thresh = param.hi_thresh;
-    DevBuf d_long;
-    if ((g_shim_rc = shim_long(a, d_long, LC_AUTO_DIV_PREFIX)) != SGK_OK) return p;
-    if ((g_shim_rc = launch_adaptor(a, ap, nullptr)) != SGK_OK) return p;
-    sgk_prefix_rec_t rec;
-    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&rec, d_out.p, sizeof rec, hipMemcpyDeviceToHost) != hipSuccess) {
-        g_shim_rc = SGK_ERR_HIP;
-        return p;
-    }
-    p.x = rec.adapt_x;
-    p.y = rec.adapt_y;
-    return p;
+    if (param.window != 2000) { g_shim_rc = SGK_ERR_ARG; return {-1, -1}; }  // both presets of the reference (src/jnn.h:84-98)
+    return jnnv2_one(sig, nsample, param, [](StatArgs &a, const AdaptP &ap, DevBuf &ws) {
+        SGK_TRY(shim_long(a, ws, LC_AUTO_DIV_PREFIX));
+        return launch_adaptor(a, ap, nullptr);
+    });
 }
 
 // any window of the domain (sgk_prefix_params_check's adaptor part), always on k_adaptor_param
 sgk_jnn_pair_t sgk_jnnv2_param(const int16_t *sig, int64_t nsample, sgk_jnnv2_param_t param) {
-    sgk_jnn_pair_t p = {-1, -1};
     g_shim_rc = SGK_OK;
     sgk_prefix_params_t chk;
     sgk_prefix_params_preset(0, SGK_PORE_R9, &chk);
     chk.adaptor = param;
-    if (sgk_prefix_params_check(&chk) != SGK_OK) { g_shim_rc = SGK_ERR_ARG; return p; }
-    if (nsample <= param.window) return p;  // "Not enough data to trim" (src/jnn.c:172-176)
-    if (!sig) { g_shim_rc = SGK_ERR_ARG; return p; }
-    DeviceBatch db;
-    if ((g_shim_rc = upload_one(sig, nsample, db)) != SGK_OK) return p;
-    DevBuf d_out;
-    if ((g_shim_rc = d_out.alloc(sizeof(sgk_prefix_rec_t))) != SGK_OK) return p;
-    StatArgs a;
-    memset(&a, 0, sizeof a);
-    a.b = db.view;
-    a.prefix = d_out.as<sgk_prefix_rec_t>();
-    AdaptP ap;
-    ap.std_scale = param.std_scale; ap.seg_dist = param.seg_dist; ap.lo_thresh = param.lo_thresh; ap.hi_thresh = param.hi_thresh;
-    if ((g_shim_rc = launch_k_adaptor_param(nullptr, a, ap, param.window)) != SGK_OK) return p;
-    sgk_prefix_rec_t rec;
-    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&rec, d_out.p, sizeof rec, hipMemcpyDeviceToHost) != hipSuccess) {
-        g_shim_rc = SGK_ERR_HIP;
-        return p;
-    }
-    p.x = rec.adapt_x;
-    p.y = rec.adapt_y;
-    return p;
+    if (sgk_prefix_params_check(&chk) != SGK_OK) { g_shim_rc = SGK_ERR_ARG; return {-1, -1}; }
+    return jnnv2_one(sig, nsample, param, [&](StatArgs &a, const AdaptP &ap, DevBuf &) {
+        return launch_k_adaptor_param(nullptr, a, ap, param.window);
+    });
 }
 
 sgk_jnn_pair_t sgk_find_polya_param(const float *raw, int64_t nsample, float top, float bot, sgk_jnn_param_t param) {
-    sgk_jnn_pair_t p = {-1, -1};
     sgk_prefix_params_t chk;
     sgk_prefix_params_preset(1, SGK_PORE_R9, &chk);
     chk.polya = param;
-    if (sgk_prefix_params_check(&chk) != SGK_OK) { g_shim_rc = SGK_ERR_ARG; return p; }
-    param.std_scale = -1.0f;  // the fixed thresholds
-    param.top = top;
-    param.bot = bot;
-    int ns = 0;
-    sgk_jnn_pair_t *segs = sgk_jnn_pa(raw, nsample, param, &ns);
-    if (segs) {
-        if (ns > 0) p = segs[0];
-        free(segs);
-    }
-    return p;
+    if (sgk_prefix_params_check(&chk) != SGK_OK) { g_shim_rc = SGK_ERR_ARG; return {-1, -1}; }
+    return polya_one(raw, nsample, top, bot, param);
 }
 
 sgk_jnn_pair_t sgk_find_adaptor(const int16_t *raw, int64_t nsample, int8_t pore) {
@@ -394,18 +293,9 @@ sgk_jnn_pair_t sgk_find_adaptor(const int16_t *raw, int64_t nsample, int8_t pore
 
 sgk_jnn_pair_t sgk_find_polya(const float *raw, int64_t nsample, float top, float bot, int8_t pore) {
     (void)pore;  // JNNV1_R9_POLYA and JNNV1_RNA004_POLYA hold the same values (src/jnn.h:52-72)
-    sgk_jnn_pair_t p = {-1, -1};
-    const JnnP pp = jnn_polya_preset();
-    sgk_jnn_param_t q;
-    q.std_scale = pp.std_scale; q.corrector = pp.corrector; q.seg_dist = pp.seg_dist; q.window = pp.window;
-    q.stall_len = pp.stall_len; q.error = pp.error; q.top = top; q.bot = bot;
-    int ns = 0;
-    sgk_jnn_pair_t *segs = sgk_jnn_pa(raw, nsample, q, &ns);
-    if (segs) {
-        if (ns > 0) p = segs[0];
-        free(segs);
-    }
-    return p;
+    sgk_prefix_params_t preset;
+    sgk_prefix_params_preset(1, SGK_PORE_R9, &preset);
+    return polya_one(raw, nsample, top, bot, preset.polya);
 }
 
 float sgk_meani16(const int16_t *x, int n) {

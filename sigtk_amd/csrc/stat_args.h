@@ -167,6 +167,18 @@ struct PolyP {
     JnnP p;
     float shift, band;
 };
+// (the one copy of each from the public structs; a jnnv2 window goes its own way, see launch_prefix_param)
+inline JnnP to_jnnp(const sgk_jnn_param_t &q) {
+    JnnP p;
+    p.std_scale = q.std_scale; p.corrector = q.corrector; p.seg_dist = q.seg_dist; p.window = q.window;
+    p.stall_len = q.stall_len; p.error = q.error; p.top = q.top; p.bot = q.bot;
+    return p;
+}
+inline AdaptP to_adaptp(const sgk_jnnv2_param_t &v) {
+    AdaptP ap;
+    ap.std_scale = v.std_scale; ap.seg_dist = v.seg_dist; ap.lo_thresh = v.lo_thresh; ap.hi_thresh = v.hi_thresh;
+    return ap;
+}
 JnnP jnn_preset(int rna);          // jnn_print's presets (src/jnn.c:313-319)
 JnnP jnn_polya_preset();           // JNNV1_R9_POLYA == JNNV1_RNA004_POLYA (src/jnn.h:52-72)
 AdaptP adaptor_preset(int pore);   // find_adaptor's presets (src/jnn.c:181-188)
@@ -209,6 +221,15 @@ int launch_k_long_chains(const char *name, int kind, hipStream_t st, const StatA
 // stat_literal.hip -- k_median_literal: min(n_reads, LIT_BLOCKS) workgroups, each with a scratch row for the batch's
 // longest read behind the long reads' part of the workspace
 constexpr uint32_t LIT_BLOCKS = 1024;
+// the scratch rows of a literal kernel (k_median_literal, k_statf_literal), one per workgroup, each of row_bytes for the
+// batch's longest read: min(n_reads, LIT_BLOCKS) of them, fewer where that would pass `room` bytes (1 024 rows for a
+// 3 000 000-sample read are 6 GB, for the sake of medians that are exactly 0 or files with a broken header), never less
+// than one.  room: what a workspace is sized for, or what a caller's workspace has
+inline size_t literal_rows(uint32_t n_reads, size_t row_bytes, size_t room = SGK_LITERAL_MAX_BYTES) {
+    size_t rows = n_reads < LIT_BLOCKS ? n_reads : LIT_BLOCKS;
+    if (row_bytes && rows * row_bytes > room) rows = room / row_bytes;
+    return rows ? rows : (n_reads ? 1 : 0);
+}
 size_t literal_workspace_bytes(uint32_t n_reads, uint32_t max_read_len);
 void prepare_literal(StatArgs &a, void *ws, size_t ws_bytes);   // fills a.lit_*; call it behind prepare_long
 int launch_k_median_literal(const char *name, int region, hipStream_t st, const StatArgs &a);

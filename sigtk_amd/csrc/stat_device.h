@@ -38,7 +38,8 @@
 //                   shims.hip uses its JnnAuto as well.
 //   statf_kernels.hip, jnnf_kernels.hip  stat and jnn on batches of FLOAT reads (sgk_stat_f32, sgk_jnn_f32), one read per
 //                   wave on float_reads.h; they use seqsum.h, the automata of this file and jnn_chunks_src / the merge of
-//                   stat_wave.h, and have their own entry points: nothing of the int16 paths goes through them.
+//                   stat_wave.h, and have their own entry points: nothing of the int16 paths goes through them.  The
+//                   float stat shims of shims.hip are a batch of one read on statf_kernels.hip.
 //   stat_launch.hip the lane / wave rule and the launchers; it holds no kernel and launches them through the
 //                   launch_k_* functions of stat_args.h, one per kernel, each defined next to its kernel.
 #pragma once

@@ -70,15 +70,11 @@ __global__ __launch_bounds__(64) void k_median_literal(StatArgs a) {
     }
 }
 
-// B = min(n_reads, LIT_BLOCKS) workgroups, each with room for the batch's longest read -- fewer where one very long
-// read would make that more than SGK_LITERAL_MAX_BYTES (1 024 rows for a 3 000 000-sample read are 6 GB, for the sake of
-// medians that are exactly 0 or files with a broken header), never less than one
+// a workgroup per scratch row (literal_rows, stat_args.h), each row with room for the batch's longest read
 static uint32_t literal_stride(uint32_t max_read_len) { return (max_read_len + 7u) & ~7u; }
 size_t literal_workspace_bytes(uint32_t n_reads, uint32_t max_read_len) {
     const size_t per = (size_t)literal_stride(max_read_len) * sizeof(int16_t);
-    size_t rows = n_reads < LIT_BLOCKS ? n_reads : LIT_BLOCKS;
-    if (per && rows * per > (size_t)SGK_LITERAL_MAX_BYTES) rows = (size_t)SGK_LITERAL_MAX_BYTES / per;
-    return (rows ? rows : (n_reads ? 1 : 0)) * per;
+    return literal_rows(n_reads, per) * per;
 }
 void prepare_literal(StatArgs &a, void *ws, size_t ws_bytes) {
     a.lit_hdr = nullptr;
@@ -92,9 +88,7 @@ void prepare_literal(StatArgs &a, void *ws, size_t ws_bytes) {
     const size_t soff = off + long_workspace_bytes(a.b.n_samples, a.b.max_read_len);
     const size_t per = (size_t)literal_stride(a.b.max_read_len) * sizeof(int16_t);
     if (per == 0 || ws_bytes < soff + per) return;
-    const size_t room = (ws_bytes - soff) / per;
-    const uint32_t want = a.b.n_reads < LIT_BLOCKS ? a.b.n_reads : LIT_BLOCKS;
-    a.lit_blocks = (uint32_t)(room < want ? room : want);   // (a workspace with room for fewer: fewer workgroups)
+    a.lit_blocks = (uint32_t)literal_rows(a.b.n_reads, per, ws_bytes - soff);   // (a workspace with room for fewer: fewer workgroups)
     a.lit_stride = literal_stride(a.b.max_read_len);
     a.lit_scratch = reinterpret_cast<int16_t *>(static_cast<char *>(ws) + soff);
 }

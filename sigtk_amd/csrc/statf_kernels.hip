@@ -1,5 +1,5 @@
 // statf_kernels.hip -- sgk_stat_f32: meanf / stdvf / medianf (src/stat.h:17-27, 36-44, 56-63) of every read of a float
-// batch, bit for bit.  What k_stat_f32 (shims.hip) does for one array per launch, in a batch shape:
+// batch, bit for bit; sgk_meanf / sgk_stdvf / sgk_medianf (shims.hip) are a batch of one read on the same two kernels:
 //   * k_statf_wave, one WAVE per read (float_reads.h), three sweeps over the read's values:
 //       1. the sequential sum (seqsum.h)               + the counts of the keys' top 11 bits + "not finite" / "a NaN"
 //       2. the sequential sum of squared deviations    + the counts of the next 11 bits among the keys that matched
@@ -142,15 +142,11 @@ __global__ __launch_bounds__(64) void k_statf_literal(FloatBatch b, sgk_statf_re
     }
 }
 
-// ---- the workspace: [0, 64) unused counters, the dispatch order, the scratch rows of k_statf_literal --
-// min(n_reads, LIT_BLOCKS) rows for the batch's longest read, fewer where that would pass SGK_LITERAL_MAX_BYTES, never
-// less than one (literal_workspace_bytes of stat_literal.hip, for floats)
+// ---- the workspace: [0, 64) unused counters, the dispatch order, the scratch rows of k_statf_literal (literal_rows,
+// stat_args.h), each with room for the batch's longest read
 static uint32_t statf_stride(uint32_t max_read_len) { return (max_read_len + 3u) & ~3u; }
 static size_t statf_rows(uint32_t n_reads, uint32_t max_read_len) {
-    const size_t per = (size_t)statf_stride(max_read_len) * sizeof(float);
-    size_t rows = n_reads < LIT_BLOCKS ? n_reads : LIT_BLOCKS;
-    if (per && rows * per > (size_t)SGK_LITERAL_MAX_BYTES) rows = (size_t)SGK_LITERAL_MAX_BYTES / per;
-    return rows ? rows : (n_reads ? 1 : 0);
+    return literal_rows(n_reads, (size_t)statf_stride(max_read_len) * sizeof(float));
 }
 static size_t statf_ws(uint32_t n_reads, uint32_t max_read_len) {
     return order_workspace_bytes(n_reads) + statf_rows(n_reads, max_read_len) * statf_stride(max_read_len) * sizeof(float);
@@ -169,6 +165,15 @@ int float_batch_order(FloatBatch &b, void *ws, hipStream_t st) {
     uint32_t *order = reinterpret_cast<uint32_t *>(static_cast<char *>(ws) + 64), *hist = order + b.n_reads;
     SGK_TRY(launch_order(b.lengths, b.n_reads, order, hist, st));
     b.order = order;
+    return SGK_OK;
+}
+
+int launch_statf(FloatBatch b, uint32_t max_read_len, sgk_statf_rec_t *out, void *ws, hipStream_t st) {
+    SGK_TRY(float_batch_order(b, ws, st));
+    SGK_LAUNCH("k_statf_wave", k_statf_wave, (b.n_reads + 3) / 4, 256, st, b, out);
+    float *scratch = reinterpret_cast<float *>(static_cast<char *>(ws) + order_workspace_bytes(b.n_reads));
+    SGK_LAUNCH("k_statf_literal", k_statf_literal, (uint32_t)statf_rows(b.n_reads, max_read_len), 64, st, b, out, scratch,
+               statf_stride(max_read_len));
     return SGK_OK;
 }
 
@@ -191,14 +196,7 @@ int sgk_stat_f32(const float *x, const uint64_t *offsets, const uint32_t *length
     if (!out || !ws || (reinterpret_cast<uintptr_t>(ws) & 15u)) return SGK_ERR_ARG;
     if (ws_bytes < statf_ws(n_reads, max_read_len)) return SGK_ERR_WORKSPACE;
     if (sgk_device_count() <= 0) return SGK_ERR_NODEVICE;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    FloatBatch b = {x, offsets, lengths, n_reads, nullptr};
-    SGK_TRY(float_batch_order(b, ws, st));
-    SGK_LAUNCH("k_statf_wave", k_statf_wave, (n_reads + 3) / 4, 256, st, b, out);
-    float *scratch = reinterpret_cast<float *>(static_cast<char *>(ws) + order_workspace_bytes(n_reads));
-    SGK_LAUNCH("k_statf_literal", k_statf_literal, (uint32_t)statf_rows(n_reads, max_read_len), 64, st, b, out, scratch,
-               statf_stride(max_read_len));
-    return SGK_OK;
+    return launch_statf(FloatBatch{x, offsets, lengths, n_reads, nullptr}, max_read_len, out, ws, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

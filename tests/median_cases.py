@@ -533,7 +533,7 @@ def range0_reads():
 
 
 def float_cases():
-    """arrays for the float-key radix of k_stat_f32 (three levels of 11, 11 and 10 bits)"""
+    """arrays for the float-key radix of k_statf_wave (three levels of 11, 11 and 10 bits)"""
     out = []
     rs = np.random.RandomState(7)
 

@@ -126,3 +126,40 @@ def test_valid_calls_without_a_gpu_are_a_loud_error(lib):
     assert c.jnn(_ok_params()) == api.SGK_ERR_NODEVICE
     assert c.jnn(api.JnnParam(-1.0, 50, 200, 250, 1.0, 30, 0.0, 0.0), top=True, bot=True) == api.SGK_ERR_NODEVICE
     assert (c.out == 0xA5).all()
+
+
+# What the parent of the commit that made the scratch-row rule one function (literal_rows, stat_args.h) returned: both
+# workspaces hold min(n_reads, 1024) rows for the longest read, fewer above SGK_LITERAL_MAX_BYTES, never less than one --
+# int16 rows behind sgk_stat's long-read part, float rows behind sgk_stat_f32's dispatch order.  n_samples = n_reads x
+# max_read_len.
+WS_N_READS = [0, 1, 2, 1023, 1024, 1025, 200000]
+WS_MAX_READ_LEN = [0, 1, 3, 4, 5000, 3000001, 0x7fffffff]
+WS_BYTES = {
+    "sgk_stat_workspace_bytes": [
+        [4749952, 4749952, 4749952, 4749952, 4749952, 4749984, 4749984],
+        [4750016, 4750032, 4750032, 4750032, 4760016, 10808640, 4316494528],
+        [4750016, 4750048, 4750048, 4750048, 4770016, 16860208, 4316494528],
+        [4754048, 4770416, 4770416, 4770416, 14984048, 285531968, 4316498560],
+        [4754048, 4770432, 4770432, 4770432, 14994048, 285531968, 4316498560],
+        [4754112, 4770496, 4770496, 4770496, 14994112, 285532032, 4316498624],
+        [5549952, 5566336, 5566336, 5566336, 15789952, 286327872, 4317294464],
+    ],
+    "sgk_stat_f32_workspace_bytes": [
+        [576, 576, 576, 576, 576, 576, 576],
+        [640, 656, 656, 656, 20640, 12000656, 8589935232],
+        [640, 672, 672, 672, 40640, 24000672, 8589935232],
+        [4672, 21040, 21040, 21040, 20464672, 264005024, 8589939264],
+        [4672, 21056, 21056, 21056, 20484672, 264005024, 8589939264],
+        [4736, 21120, 21120, 21120, 20484736, 264005088, 8589939328],
+        [800576, 816960, 816960, 816960, 21280576, 264800928, 8590735168],
+    ],
+}
+
+
+@pytest.mark.parametrize("fn", sorted(WS_BYTES))
+def test_scratch_rows_of_both_workspaces_are_what_they_were(lib, fn):
+    api.load_library()   # (binds the int16 workspace functions)
+    f = getattr(lib, fn)
+    for r, row in zip(WS_N_READS, WS_BYTES[fn]):
+        got = [int(f(r, r * m, m)) for m in WS_MAX_READ_LEN]
+        assert got == row, (fn, r, got)

@@ -122,3 +122,70 @@ def test_per_read_shims_on_a_long_read(gpu, oracle):
             assert gpu.shim_jnn_raw(raw, pg) == list(zip(ex.tolist(), ey.tolist()))
         for pore in (0, 2):
             assert gpu.shim_find_adaptor(raw, pore) == oracle.find_adaptor(raw, pore)
+
+
+def _plateaus():
+    """5 000 values: plateaus of 300 at 100 pA between excursions of 200 to 60 and to 140 pA.  Mean 100, deviation 28.3:
+    with 0.75 deviations either side, or with 80 .. 120 fixed, every plateau is in range and longer than any window
+    below, every excursion out of range and longer than any error budget: a segment per plateau"""
+    return np.tile(np.concatenate([np.full(300, 100.0), np.full(200, 60.0), np.full(300, 100.0), np.full(200, 140.0)]),
+                   5).astype(np.float32)
+
+
+def test_jnn_pa_shim_serves_sets_the_batch_entry_refuses(gpu, oracle):
+    """sgk_jnn_pa takes any jnn_param_t, sgk_jnn_f32 only the domain of sgk_jnn_params_check: whatever kernel the shim
+    runs on has to serve the sets outside it as well (windows under 32, a std_scale that is not finite)"""
+    import ctypes as C
+    inf, nan = float("inf"), float("nan")
+    sets = [dict(std_scale=0.75, corrector=50, seg_dist=50, window=20, stall_len=0.25, error=5),
+            dict(std_scale=0.75, corrector=50, seg_dist=50, window=31, stall_len=0.25, error=5),
+            dict(std_scale=-1.0, corrector=50, seg_dist=50, window=20, stall_len=0.25, error=5, top=120.0, bot=80.0),
+            dict(std_scale=inf, corrector=50, seg_dist=50, window=150, stall_len=0.25, error=5),
+            dict(std_scale=nan, corrector=50, seg_dist=50, window=150, stall_len=0.25, error=5, top=120.0, bot=80.0)]
+    reads, dig, off, rng = _reads(gpu, 0, [1, 2, 1025, 5000], 59)
+    arrays = [oracle.pa(raw, dig[r], off[r], rng[r]) for r, raw in enumerate(reads)]
+    plateaus = _plateaus()
+    L = gpu._shim_lib()
+    with np.errstate(all="ignore"):
+        for kw in sets:
+            po = oracle.jnn_param(**kw)
+            pg = gpu.JnnParam(po.std_scale, po.corrector, po.seg_dist, po.window, po.stall_len, po.error, po.top, po.bot)
+            assert gpu._param_lib().sgk_jnn_params_check(C.byref(pg)) == gpu.SGK_ERR_ARG, kw
+            for x in arrays + [plateaus]:
+                ex, ey = oracle.jnn_pa(x, po)
+                want = list(zip(ex.tolist(), ey.tolist()))
+                if x is plateaus and kw["std_scale"] != inf:   # (finite thresholds: no comparison of empty lists)
+                    assert len(want) >= 1, kw
+                assert gpu.shim_jnn_pa(x, pg) == want, (kw, x.size)
+                assert L.sgk_shim_status() == 0
+
+
+def test_float_shim_edges(gpu):
+    """what the float shims return without looking at the array"""
+    import ctypes as C
+    L = gpu._shim_lib()
+    x = np.arange(8, dtype=np.float32)
+    for f in (L.sgk_meanf, L.sgk_stdvf, L.sgk_medianf):
+        for ptr, n in ((x.ctypes.data, 0), (None, 8)):
+            assert np.isnan(f(ptr, n))
+            assert L.sgk_shim_status() == gpu.SGK_ERR_ARG
+    p = gpu.JnnParam(0.75, 50, 50, 150, 0.25, 5, 0.0, 0.0)
+    n = C.c_int(7)
+    assert not L.sgk_jnn_pa(x.ctypes.data, 0, p, C.byref(n))        # an empty read: NULL, no segments, no error
+    assert n.value == 0 and L.sgk_shim_status() == gpu.SGK_OK
+    n = C.c_int(7)
+    assert not L.sgk_jnn_pa(None, 8, p, C.byref(n))
+    assert n.value == 0 and L.sgk_shim_status() == gpu.SGK_ERR_ARG
+
+
+def test_stat_f32_shim_long_array(gpu, oracle):
+    """one array of 3 000 001 values through sgk_meanf / sgk_stdvf / sgk_medianf, and the same with a NaN in it: the
+    literal redo of mean, deviation and median (k_statf_literal) at that size"""
+    x = np.random.RandomState(61).normal(90, 12, size=3000001).astype(np.float32)
+    y = x.copy()
+    y[1500000] = np.nan
+    with np.errstate(all="ignore"):
+        for name, a in (("plain", x), ("a NaN", y)):
+            for what, g, e in zip(("mean", "std", "median"), gpu.shim_stat_f32(a), oracle.statf(a)):
+                g, e = np.float32(g), np.float32(e)
+                assert (np.isnan(g) and np.isnan(e)) or g.view(np.uint32) == e.view(np.uint32), (name, what, g, e)

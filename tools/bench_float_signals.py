@@ -10,7 +10,13 @@ Per shape, on pA of the benchmark's synthetic DNA reads (made and converted on t
   2. what a caller had before the batch entry points: the per-read shims in a loop (sgk_meanf + sgk_stdvf + sgk_medianf,
      sgk_jnn_pa) over `--sample` reads, wall clock, SCALED to the batch;
   3. as a yardstick, sgk_stat and sgk_jnn_param on the int16 reads the floats were made from.
-HIP events around each call after one warm-up call, the median of `--runs` runs."""
+HIP events around each call after one warm-up call, the median of `--runs` runs.
+
+    python tools/bench_float_signals.py --shims 5000,100000,3000001 [--runs 5] [--calls 5] [--json out.json]
+
+times the per-read float shims instead (profiles/float_shims.md): one pA read of each size, wall clock per call of
+api.shim_stat_f32 (its three calls), api.shim_jnn_pa with the DNA preset and with the literal set of 1., each run the
+mean of `--calls` calls after one warm-up call.  SIGTK_AMD_LIB selects the library, for a comparison of two builds."""
 import argparse
 import ctypes as C
 import json
@@ -43,15 +49,48 @@ def timed(call, runs):
     return statistics.median(ms), min(ms), max(ms)
 
 
+def shims(a, dev):
+    dna = api.JnnParam(0.75, 50, 50, 150, 0.25, 5, 0.0, 0.0)
+    rows = []
+    for n in (int(v) for v in a.shims.split(",")):
+        b = device.synth_reads(1, n, seed=11, kind=0, device=dev)
+        pa = torch.empty(b.n_samples, dtype=torch.float32, device=dev)
+        device.pa(b, pa)
+        torch.cuda.synchronize()
+        x = pa[int(b.offsets_host[0]):int(b.offsets_host[0]) + n].cpu().numpy()
+        med = float(np.median(x))
+        literal = api.JnnParam(-1.0, 4, 50, 150, 1.0, 5, med + 8.0, med - 8.0)   # error >= corrector
+        res = {"n": n, "library": api.LIB_PATH}
+        for name, call in (("shim_stat_f32", lambda: api.shim_stat_f32(x)), ("shim_jnn_pa_dna", lambda: api.shim_jnn_pa(x, dna)),
+                           ("shim_jnn_pa_literal", lambda: api.shim_jnn_pa(x, literal))):
+            call()
+            ms = []
+            for _ in range(a.runs):
+                t0 = time.perf_counter()
+                for _ in range(a.calls):
+                    call()
+                ms.append((time.perf_counter() - t0) / a.calls * 1e3)
+            res[name] = {"ms_per_call": ms}
+        rows.append(res)
+        print(json.dumps(res), flush=True)
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--shapes", default="10000x100000,200000x5000")
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--sample", type=int, default=8, help="reads the shim loop is timed on")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--shims", default=None, help="N1,N2,..: time the per-read float shims on one read of each size instead")
+    ap.add_argument("--calls", type=int, default=5, help="--shims: calls per run")
     a = ap.parse_args()
     L = api._float_lib()
     dev = torch.device("cuda", 0)
+    if a.shims:
+        return shims(a, dev)
     stream = lambda: int(torch.cuda.current_stream().cuda_stream)
     dna = api.JnnParam(0.75, 50, 50, 150, 0.25, 5, 0.0, 0.0)
     rows = []
