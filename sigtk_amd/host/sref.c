@@ -20,16 +20,9 @@
 #include <unistd.h>
 #include <zlib.h>
 
+#include "cli.h"
 #include "sigtk_gpu.h"
 #include "sref.h"
-#include "version.h"
-
-#define ERROR(fn, ...)                                           \
-    do {                                                         \
-        fprintf(stderr, "[%s::ERROR]\033[1;31m ", fn);           \
-        fprintf(stderr, __VA_ARGS__);                            \
-        fprintf(stderr, "\033[0m\n");                            \
-    } while (0)
 
 uint64_t fnv1a_bytes(const void *p_, size_t n) {
     const uint8_t *p = (const uint8_t *)p_;
@@ -285,16 +278,6 @@ int modelcheckmain(int argc, char *argv[]) {
 
 /* ------------------------------------------------------------------ sref */
 
-static void die_now(void) {
-    fflush(stdout); /* the header line and the batches already written stay in front of the error */
-    fflush(stderr);
-    _exit(EXIT_FAILURE);
-}
-static void gpu_fail(const char *what, int rc) {
-    ERROR("srefmain", "%s failed: %s %s", what, sgk_strerror(rc), sgk_last_hip_error());
-    die_now();
-}
-
 /* the rows of the file in order ('+' and, for DNA, '-' of every sequence), handed out in pieces of positions */
 typedef struct {
     const fasta_t *fa;
@@ -329,7 +312,7 @@ static uint32_t next_batch(row_cursor_t *c, uint64_t budget, uint32_t max_spans,
             sgk_sref_span_t *nv = (sgk_sref_span_t *)realloc(out->v, (size_t)nc * sizeof *nv);
             if (!nv) {
                 ERROR("srefmain", "%s", "out of memory");
-                die_now();
+                die_flushed();
             }
             out->v = nv;
             out->cap = nc;
@@ -365,36 +348,35 @@ static void emit(sgk_sref_pipe_t *pipe, int slot) {
     const uint8_t *text;
     uint64_t nb;
     const int rc = sgk_sref_pipe_wait(pipe, slot, &text, &nb);
-    if (rc != SGK_OK) gpu_fail("sgk_sref_pipe_wait", rc);
+    if (rc != SGK_OK) gpu_fail("srefmain", "sgk_sref_pipe_wait", rc);
     if (nb && fwrite(text, 1, (size_t)nb, stdout) != nb) {
         ERROR("srefmain", "%s", "writing to stdout failed");
-        die_now();
+        die_flushed();
     }
 }
 
 int srefmain(int argc, char *argv[]) {
     static const struct option long_options[] = {
         {"help", no_argument, 0, 'h'},          {"version", no_argument, 0, 'V'},   {"output", required_argument, 0, 'o'},
-        {"verbose", required_argument, 0, 'v'}, {"rna", no_argument, 0, 0},         {"kmer-model", required_argument, 0, 0},
-        {"batch", required_argument, 0, 0},     {0, 0, 0, 0}};
-    int longindex = 0, c;
+        {"verbose", required_argument, 0, 'v'}, {"rna", no_argument, 0, OPT_RNA},   {"kmer-model", required_argument, 0, OPT_KMER_MODEL},
+        {"batch", required_argument, 0, OPT_BATCH}, {0, 0, 0, 0}};
+    int c;
     FILE *fp_help = stderr;
     int rna = 0, hdr = 1;
     const char *model_fn = NULL;
     uint64_t budget = 16ull << 20; /* signal positions per batch: about 11 bytes of text each, ~180 MB */
-    while ((c = getopt_long(argc, argv, "o:v:hVn", long_options, &longindex)) >= 0) {
+    while ((c = getopt_long(argc, argv, "o:v:hVn", long_options, NULL)) >= 0) {
         if (c == 'V') {
-            fprintf(stdout, "sigtk %s\n", SIGTK_VERSION);
-            exit(EXIT_SUCCESS);
+            version_exit();
         } else if (c == 'h') {
             fp_help = stdout;
         } else if (c == 'n') {
             hdr = 0;
-        } else if (c == 0 && longindex == 4) {
+        } else if (c == OPT_RNA) {
             rna = 1;
-        } else if (c == 0 && longindex == 5) {
+        } else if (c == OPT_KMER_MODEL) {
             model_fn = optarg;
-        } else if (c == 0 && longindex == 6) {
+        } else if (c == OPT_BATCH) {
             budget = strtoull(optarg, NULL, 10);
             if (budget < 1) budget = 1;
             if (budget > (1ull << 31)) budget = 1ull << 31;
@@ -414,29 +396,29 @@ int srefmain(int argc, char *argv[]) {
     if (!model_fn) {
         ERROR("srefmain", "%s", "this build carries no built-in pore model: give one with --kmer-model FILE "
                                 "(columns kmer, level_mean; 6-mers for DNA, 5-mers with --rna)");
-        die_now();
+        die_flushed();
     }
     const uint32_t k = rna ? 5 : 6;
     float *levels = (float *)calloc(4096, sizeof(float));
-    if (!levels) die_now();
+    if (!levels) die_flushed();
     uint32_t k_file = 0;
     char err[512];
     if (model_read(model_fn, k, levels, &k_file, err, sizeof err) != 0) {
         ERROR("srefmain", "%s", err);
-        die_now();
+        die_flushed();
     }
     fasta_t fa;
     if (fasta_read(argv[optind], &fa) != 0) {
         ERROR("srefmain", "%s", fa.err);
-        die_now();
+        die_flushed();
     }
     if (sgk_device_count() <= 0) {
         ERROR("srefmain", "%s", "no usable GPU: sigtk-amd has no CPU compute path");
-        die_now();
+        die_flushed();
     }
     sgk_sref_pipe_t *pipe = NULL;
     int rc = sgk_sref_pipe_create(0, levels, k, &pipe);
-    if (rc != SGK_OK) gpu_fail("sgk_sref_pipe_create", rc);
+    if (rc != SGK_OK) gpu_fail("srefmain", "sgk_sref_pipe_create", rc);
     if (hdr) printf("ref_name\tref_len\tstrand\tsig_len\tsig_mean\n");
 
     row_cursor_t cur = {&fa, k, 0, rna, 0, 0};
@@ -451,11 +433,11 @@ int srefmain(int argc, char *argv[]) {
         for (uint32_t i = 0; i < n_names; i++) name_bytes += fa.rec[seq0 + i].name_len;
         if (name_bytes > 0xfffffff0ull) {
             ERROR("srefmain", "%s", "the sequence names of one batch exceed 4 GiB");
-            die_now();
+            die_flushed();
         }
         sgk_sref_stage_t st;
         rc = sgk_sref_pipe_begin(pipe, slot, n_bases, spans.n, n_names, name_bytes, &st);
-        if (rc != SGK_OK) gpu_fail("sgk_sref_pipe_begin", rc);
+        if (rc != SGK_OK) gpu_fail("srefmain", "sgk_sref_pipe_begin", rc);
         uint32_t no = 0;
         for (uint32_t i = 0; i < n_names; i++) {
             st.name_offsets[i] = no;
@@ -469,7 +451,7 @@ int srefmain(int argc, char *argv[]) {
         }
         memcpy(st.spans, spans.v, (size_t)spans.n * sizeof *spans.v);
         rc = sgk_sref_pipe_submit(pipe, slot);
-        if (rc != SGK_OK) gpu_fail("sgk_sref_pipe_submit", rc);
+        if (rc != SGK_OK) gpu_fail("srefmain", "sgk_sref_pipe_submit", rc);
         if (pending >= 0) emit(pipe, pending);
         pending = slot;
         slot ^= 1;

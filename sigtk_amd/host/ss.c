@@ -18,16 +18,9 @@
 #include <unistd.h>
 
 #include "../csrc/text_format.h"
+#include "cli.h"
 #include "sigtk_gpu.h"
 #include "ss.h"
-#include "version.h"
-
-#define ERROR(fn, ...)                                           \
-    do {                                                         \
-        fprintf(stderr, "[%s::ERROR]\033[1;31m ", fn);           \
-        fprintf(stderr, __VA_ARGS__);                            \
-        fprintf(stderr, "\033[0m\n");                            \
-    } while (0)
 
 /* ------------------------------------------------------------------ PAF */
 
@@ -150,27 +143,18 @@ static const char *ss_status_message(uint32_t st) {
 
 /* ------------------------------------------------------------------ ss paf2tsv */
 
-static void die_now(void) {
-    fflush(stdout); /* the header line and the rows already written stay in front of the error */
-    fflush(stderr);
-    _exit(EXIT_FAILURE);
-}
-static void gpu_fail(const char *what, int rc) {
-    ERROR("ssmain", "%s failed: %s %s", what, sgk_strerror(rc), sgk_last_hip_error());
-    die_now();
-}
 static void *xrealloc(void *p, size_t n) {
     void *q = realloc(p, n ? n : 1);
     if (!q) {
         ERROR("ssmain", "%s", "out of memory");
-        die_now();
+        die_flushed();
     }
     return q;
 }
 static void out_write(const void *p, size_t n) {
     if (n && fwrite(p, 1, n, stdout) != n) {
         ERROR("ssmain", "%s", "writing to stdout failed");
-        die_now();
+        die_flushed();
     }
 }
 
@@ -291,32 +275,32 @@ static void emit(sgk_ss_pipe_t *pipe, int slot) {
     uint64_t nb;
     uint32_t bad, st;
     const int rc = sgk_ss_pipe_wait(pipe, slot, &text, &nb, &bad, &st);
-    if (rc != SGK_OK) gpu_fail("sgk_ss_pipe_wait", rc);
+    if (rc != SGK_OK) gpu_fail("ssmain", "sgk_ss_pipe_wait", rc);
     out_write(text, (size_t)nb);
     if (bad != 0xffffffffu) {
         fprintf(stderr, "%s\n", ss_status_message(st));
-        die_now();
+        die_flushed();
     }
 }
 
 static void run_gpu(reader_t *r, uint64_t budget) {
     sgk_ss_pipe_t *pipe = NULL;
     int rc = sgk_ss_pipe_create(0, &pipe);
-    if (rc != SGK_OK) gpu_fail("sgk_ss_pipe_create", rc);
+    if (rc != SGK_OK) gpu_fail("ssmain", "sgk_ss_pipe_create", rc);
     batch_t b;
     memset(&b, 0, sizeof b);
     int slot = 0, pending = -1;
     while (next_batch(r, budget, &b)) {
         sgk_ss_stage_t st;
         rc = sgk_ss_pipe_begin(pipe, slot, b.ss_n, b.n, b.n, b.n, b.ids_n, &st);
-        if (rc != SGK_OK) gpu_fail("sgk_ss_pipe_begin", rc);
+        if (rc != SGK_OK) gpu_fail("ssmain", "sgk_ss_pipe_begin", rc);
         memcpy(st.ss, b.ss, b.ss_n);
         memcpy(st.records, b.rec, (size_t)b.n * sizeof *b.rec);
         memcpy(st.spans, b.span, (size_t)b.n * sizeof *b.span);
         memcpy(st.id_bytes, b.ids, b.ids_n);
         memcpy(st.id_offsets, b.id_off, ((size_t)b.n + 1) * sizeof *b.id_off);
         rc = sgk_ss_pipe_submit(pipe, slot);
-        if (rc != SGK_OK) gpu_fail("sgk_ss_pipe_submit", rc);
+        if (rc != SGK_OK) gpu_fail("ssmain", "sgk_ss_pipe_submit", rc);
         if (pending >= 0) emit(pipe, pending);
         pending = slot;
         slot ^= 1;
@@ -344,7 +328,7 @@ static void run_host(reader_t *r, uint64_t budget) {
             free(out);
             free(r->line);
             fclose(r->fp);
-            die_now();
+            die_flushed();
         }
         const size_t row_max = r->cur.rid_len + 40;
         for (uint64_t first = 0; first < r->rows; first += budget) {
@@ -389,22 +373,21 @@ static void ss_usage(FILE *fp, uint64_t budget) {
 
 int ssmain(int argc, char *argv[]) {
     static const struct option long_options[] = {{"verbose", required_argument, 0, 'v'}, {"help", no_argument, 0, 'h'},
-                                                 {"version", no_argument, 0, 'V'},       {"host-decode", no_argument, 0, 0},
-                                                 {"batch", required_argument, 0, 0},     {0, 0, 0, 0}};
-    int longindex = 0, c;
+                                                 {"version", no_argument, 0, 'V'},       {"host-decode", no_argument, 0, OPT_HOST_DECODE},
+                                                 {"batch", required_argument, 0, OPT_BATCH}, {0, 0, 0, 0}};
+    int c;
     FILE *fp_help = stderr;
     int host = 0;
     uint64_t budget = 1ull << 20; /* rows per batch: 8 bytes of table and about 45 bytes of text each */
     const uint64_t budget_default = budget;
-    while ((c = getopt_long(argc, argv, "hVv:", long_options, &longindex)) >= 0) {
+    while ((c = getopt_long(argc, argv, "hVv:", long_options, NULL)) >= 0) {
         if (c == 'V') {
-            fprintf(stdout, "sigtk %s\n", SIGTK_VERSION);
-            exit(EXIT_SUCCESS);
+            version_exit();
         } else if (c == 'h') {
             fp_help = stdout;
-        } else if (c == 0 && longindex == 3) {
+        } else if (c == OPT_HOST_DECODE) {
             host = 1;
-        } else if (c == 0 && longindex == 4) {
+        } else if (c == OPT_BATCH) {
             budget = strtoull(optarg, NULL, 10);
             if (budget < 1) budget = 1;
             if (budget > (1ull << 26)) budget = 1ull << 26;
@@ -421,11 +404,11 @@ int ssmain(int argc, char *argv[]) {
     r.fp = fopen(r.path, "r");
     if (!r.fp) {
         ERROR("ssmain", "cannot open %s", r.path);
-        die_now();
+        die_flushed();
     }
     if (!host && sgk_device_count() <= 0) {
         ERROR("ssmain", "%s", "no usable GPU: sigtk-amd has no CPU compute path (ss paf2tsv --host-decode runs on the host)");
-        die_now();
+        die_flushed();
     }
     printf("read_id\tkmer_idx\tstart_raw_idx\tend_raw_idx\n");
     if (host) run_host(&r, budget);
@@ -434,6 +417,6 @@ int ssmain(int argc, char *argv[]) {
     if (failed) ERROR("ssmain", "%s", r.err);
     free(r.line);
     fclose(r.fp);
-    if (failed) die_now();
+    if (failed) die_flushed();
     return 0;
 }

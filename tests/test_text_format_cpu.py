@@ -56,5 +56,5 @@ def test_usage_names_gpu_text(cli, tool):
 def test_header_is_plain_c_and_shared_with_the_kernels():
     """the kernels and the CLI compile the same file"""
     assert '#include "text_format.h"' in open(os.path.join(ROOT, "sigtk_amd", "csrc", "text_kernels.hip")).read()
-    assert "text_format.h" in open(os.path.join(ROOT, "sigtk_amd", "host", "sigtk_amd.c")).read()
+    assert "text_format.h" in open(os.path.join(ROOT, "sigtk_amd", "host", "selftest.c")).read()
     assert "text_kernels.hip" in build.HIP_SOURCES
