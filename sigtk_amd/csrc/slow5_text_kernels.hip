@@ -169,8 +169,7 @@ static int s5_args(const int16_t *samples, const uint64_t *offsets, const uint32
     if (heads && n_reads && (!heads->bytes || !heads->offsets)) return SGK_ERR_ARG;
     if (tails && n_reads && (!tails->bytes || !tails->offsets)) return SGK_ERR_ARG;
     if (sgk_device_count() <= 0) return SGK_ERR_NODEVICE;
-    if (!ws || (reinterpret_cast<uintptr_t>(ws) & 15u)) return SGK_ERR_ARG;
-    if (ws_bytes < sizeof(TextHdr)) return SGK_ERR_WORKSPACE;
+    SGK_TRY(text_ws_check(ws, ws_bytes, sizeof(TextHdr)));
     if (!tile_list_carve(ws, ws_bytes, n_reads, a)) return SGK_ERR_WORKSPACE;
     a->samples = samples;
     a->offsets = offsets;
@@ -204,7 +203,7 @@ int sgk_slow5_text_measure(const int16_t *samples, const uint64_t *offsets, cons
     if (!row_offsets) return SGK_ERR_ARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
     a.row_offsets = row_offsets;
-    const uint32_t grid = a.n_tiles_max < TEXT_GRID_MAX ? a.n_tiles_max : TEXT_GRID_MAX;
+    const uint32_t grid = text_grid(a);
     SGK_LAUNCH("k_slow5_text_tiles", k_slow5_text_tiles, 1, 1024, st, a);
     SGK_LAUNCH("k_slow5_text_measure", k_slow5_text_measure, grid, TEXT_TILE, st, a);
     SGK_LAUNCH("k_slow5_text_scan", k_slow5_text_scan, 1, 1024, st, a);
@@ -220,7 +219,7 @@ int sgk_slow5_text_write(const int16_t *samples, const uint64_t *offsets, const 
     if (!text && text_capacity) return SGK_ERR_ARG;
     a.text = text;
     a.text_cap = text_capacity;
-    const uint32_t grid = a.n_tiles_max < TEXT_GRID_MAX ? a.n_tiles_max : TEXT_GRID_MAX;
+    const uint32_t grid = text_grid(a);
     SGK_LAUNCH("k_slow5_text_write", k_slow5_text_write, grid, TEXT_TILE, static_cast<hipStream_t>(stream), a);
     return SGK_OK;
 }

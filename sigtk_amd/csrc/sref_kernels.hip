@@ -24,8 +24,6 @@
 #include "text_format.h"
 #include "text_tiles.h"
 
-#include <new>
-
 namespace sgk {
 
 constexpr uint32_t SREF_STAGE = 8192;       // bytes of a tile's LDS image: 256 values of up to 15 + 1 bytes and a head
@@ -279,9 +277,8 @@ static int sref_args(const sgk_sref_batch_t *b, const sgk_text_ids_t *names, voi
     int rc = sref_batch_check(b);
     if (rc != SGK_OK) return rc;
     if (sgk_device_count() <= 0) return SGK_ERR_NODEVICE;
-    if (!ws || (reinterpret_cast<uintptr_t>(ws) & 15u)) return SGK_ERR_ARG;
     if (b->n_spans && (!names || !names->bytes || !names->offsets)) return SGK_ERR_ARG;
-    if (ws_bytes < sizeof(TextHdr) + SREF_TABLE_BYTES + 16) return SGK_ERR_WORKSPACE;
+    SGK_TRY(text_ws_check(ws, ws_bytes, sizeof(TextHdr) + SREF_TABLE_BYTES + 16));
     const size_t list_bytes = (ws_bytes - SREF_TABLE_BYTES) & ~(size_t)15;
     sref_fill(b, a);
     if (!tile_list_carve(ws, list_bytes, b->n_spans, a)) return SGK_ERR_WORKSPACE;
@@ -324,7 +321,7 @@ int sgk_sref_text_measure(const sgk_sref_batch_t *b, const sgk_text_ids_t *names
     if (!row_offsets) return SGK_ERR_ARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
     a.row_offsets = row_offsets;
-    const uint32_t grid = a.n_tiles_max < TEXT_GRID_MAX ? a.n_tiles_max : TEXT_GRID_MAX;
+    const uint32_t grid = text_grid(a);
     SGK_LAUNCH("k_sref_table", k_sref_table, (a.n_levels + 255u) / 256u, 256, st, a);
     SGK_LAUNCH("k_sref_tiles", k_sref_tiles, 1, 1024, st, a);
     if (b->table_in_lds) SGK_LAUNCH("k_sref_measure_lds", k_sref_measure<true>, grid < 512u ? grid : 512u, TEXT_TILE, st, a);
@@ -342,182 +339,10 @@ int sgk_sref_text_write(const sgk_sref_batch_t *b, const sgk_text_ids_t *names, 
     hipStream_t st = static_cast<hipStream_t>(stream);
     a.text = text;
     a.text_cap = text_capacity;
-    const uint32_t grid = a.n_tiles_max < TEXT_GRID_MAX ? a.n_tiles_max : TEXT_GRID_MAX;
+    const uint32_t grid = text_grid(a);
     // (a workgroup with the table in LDS pays 64 KiB of loads before its first tile: two per CU, striding)
     if (b->table_in_lds) SGK_LAUNCH("k_sref_write_lds", k_sref_write<true>, grid < 512u ? grid : 512u, TEXT_TILE, st, a);
     else SGK_LAUNCH("k_sref_write", k_sref_write<false>, grid, TEXT_TILE, st, a);
-    return SGK_OK;
-}
-
-// ---- host pipe: batches of spans in, their text out, two slots so that one batch's download and the caller's
-// fwrite overlap the next one's upload and kernels.  Buffers grow on demand and are kept.
-struct sgk_sref_pipe {
-    int device;
-    uint32_t k;
-    float *d_levels;
-    struct Slot {
-        hipStream_t stream;
-        // pinned staging, filled by the caller between begin and submit
-        uint8_t *h_in;
-        size_t h_in_cap;
-        uint64_t n_bases, name_bytes;
-        uint32_t n_spans, n_names;
-        size_t off_spans, off_nbytes, off_noffs, in_bytes;
-        uint8_t *d_in;
-        size_t d_in_cap;
-        uint8_t *d_ws;
-        size_t d_ws_cap;
-        uint64_t *d_rows;
-        size_t d_rows_cap;
-        uint8_t *d_text, *h_text;
-        size_t d_text_cap, h_text_cap;
-        TextHdr *h_hdr;
-        uint64_t n_bytes;
-        int busy;
-    } slot[2];
-};
-
-static int pipe_grow_dev(void **p, size_t *cap, size_t need) {
-    if (need <= *cap) return SGK_OK;
-    if (*p) SGK_HIP_TRY(hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    const size_t want = need + need / 4 + 4096;
-    SGK_HIP_TRY(hipMalloc(p, want));
-    *cap = want;
-    return SGK_OK;
-}
-static int pipe_grow_host(void **p, size_t *cap, size_t need) {
-    if (need <= *cap) return SGK_OK;
-    if (*p) SGK_HIP_TRY(hipHostFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    const size_t want = need + need / 4 + 4096;
-    SGK_HIP_TRY(hipHostMalloc(p, want, hipHostMallocDefault));
-    *cap = want;
-    return SGK_OK;
-}
-
-int sgk_sref_pipe_create(int device, const float *levels, uint32_t k, sgk_sref_pipe_t **out) {
-    if (!out || !levels || k < 1 || k > 6) return SGK_ERR_ARG;
-    *out = nullptr;
-    const int ndev = sgk_device_count();
-    if (ndev <= 0) return SGK_ERR_NODEVICE;
-    if (device < 0 || device >= ndev) return SGK_ERR_ARG;
-    SGK_HIP_TRY(hipSetDevice(device));
-    sgk_sref_pipe *p = new (std::nothrow) sgk_sref_pipe();
-    if (!p) return SGK_ERR_NOMEM;
-    p->device = device;
-    p->k = k;
-    const size_t lb = sizeof(float) << (2u * k);
-    if (hipMalloc(reinterpret_cast<void **>(&p->d_levels), lb) != hipSuccess ||
-        hipMemcpy(p->d_levels, levels, lb, hipMemcpyHostToDevice) != hipSuccess) {
-        sgk_sref_pipe_destroy(p);
-        return SGK_ERR_HIP;
-    }
-    for (int s = 0; s < 2; ++s) {
-        if (hipStreamCreateWithFlags(&p->slot[s].stream, hipStreamNonBlocking) != hipSuccess ||
-            hipHostMalloc(reinterpret_cast<void **>(&p->slot[s].h_hdr), sizeof(TextHdr), hipHostMallocDefault) != hipSuccess) {
-            sgk_sref_pipe_destroy(p);
-            return SGK_ERR_HIP;
-        }
-    }
-    *out = p;
-    return SGK_OK;
-}
-
-void sgk_sref_pipe_destroy(sgk_sref_pipe_t *p) {
-    if (!p) return;
-    for (int s = 0; s < 2; ++s) {
-        sgk_sref_pipe::Slot &S = p->slot[s];
-        if (S.stream) {
-            (void)hipStreamSynchronize(S.stream);
-            (void)hipStreamDestroy(S.stream);
-        }
-        if (S.h_in) (void)hipHostFree(S.h_in);
-        if (S.h_text) (void)hipHostFree(S.h_text);
-        if (S.h_hdr) (void)hipHostFree(S.h_hdr);
-        if (S.d_in) (void)hipFree(S.d_in);
-        if (S.d_ws) (void)hipFree(S.d_ws);
-        if (S.d_rows) (void)hipFree(S.d_rows);
-        if (S.d_text) (void)hipFree(S.d_text);
-    }
-    if (p->d_levels) (void)hipFree(p->d_levels);
-    delete p;
-}
-
-int sgk_sref_pipe_begin(sgk_sref_pipe_t *p, int slot, uint64_t n_bases, uint32_t n_spans, uint32_t n_names,
-                        uint64_t name_bytes, sgk_sref_stage_t *out) {
-    if (!p || !out || slot < 0 || slot > 1) return SGK_ERR_ARG;
-    sgk_sref_pipe::Slot &S = p->slot[slot];
-    if (S.busy) return SGK_ERR_ARG;
-    SGK_HIP_TRY(hipSetDevice(p->device));
-    S.n_bases = n_bases;
-    S.n_spans = n_spans;
-    S.n_names = n_names;
-    S.name_bytes = name_bytes;
-    S.off_spans = round_up(n_bases + 16, 16);
-    S.off_nbytes = round_up(S.off_spans + (size_t)n_spans * sizeof(sgk_sref_span_t), 16);
-    S.off_noffs = round_up(S.off_nbytes + name_bytes + 16, 16);
-    S.in_bytes = round_up(S.off_noffs + ((size_t)n_names + 1) * 4, 16);
-    const int rc = pipe_grow_host(reinterpret_cast<void **>(&S.h_in), &S.h_in_cap, S.in_bytes);
-    if (rc != SGK_OK) return rc;
-    out->bases = S.h_in;
-    out->spans = reinterpret_cast<sgk_sref_span_t *>(S.h_in + S.off_spans);
-    out->name_bytes = S.h_in + S.off_nbytes;
-    out->name_offsets = reinterpret_cast<uint32_t *>(S.h_in + S.off_noffs);
-    return SGK_OK;
-}
-
-int sgk_sref_pipe_submit(sgk_sref_pipe_t *p, int slot) {
-    if (!p || slot < 0 || slot > 1) return SGK_ERR_ARG;
-    sgk_sref_pipe::Slot &S = p->slot[slot];
-    if (S.busy || !S.h_in) return SGK_ERR_ARG;
-    SGK_HIP_TRY(hipSetDevice(p->device));
-    const sgk_sref_span_t *hs = reinterpret_cast<const sgk_sref_span_t *>(S.h_in + S.off_spans);
-    uint64_t n_pos = 0;
-    for (uint32_t s = 0; s < S.n_spans; ++s) n_pos += hs[s].count;
-    const size_t ws_bytes = sgk_sref_text_workspace_bytes(S.n_spans, n_pos);
-    int rc = pipe_grow_dev(reinterpret_cast<void **>(&S.d_in), &S.d_in_cap, S.in_bytes);
-    if (rc == SGK_OK) rc = pipe_grow_dev(reinterpret_cast<void **>(&S.d_ws), &S.d_ws_cap, ws_bytes);
-    if (rc == SGK_OK) rc = pipe_grow_dev(reinterpret_cast<void **>(&S.d_rows), &S.d_rows_cap, ((size_t)S.n_spans + 1) * 8);
-    if (rc != SGK_OK) return rc;
-    SGK_HIP_TRY(hipMemcpyAsync(S.d_in, S.h_in, S.in_bytes, hipMemcpyHostToDevice, S.stream));
-    sgk_sref_batch_t b;
-    memset(&b, 0, sizeof b);
-    b.bases = S.d_in;
-    b.n_bases = S.n_bases;
-    b.spans = reinterpret_cast<const sgk_sref_span_t *>(S.d_in + S.off_spans);
-    b.n_spans = S.n_spans;
-    b.levels = p->d_levels;
-    b.k = p->k;
-    sgk_text_ids_t names = {S.d_in + S.off_nbytes, reinterpret_cast<const uint32_t *>(S.d_in + S.off_noffs)};
-    rc = sgk_sref_text_measure(&b, &names, S.d_rows, S.d_ws, ws_bytes, S.stream);
-    if (rc != SGK_OK) return rc;
-    SGK_HIP_TRY(hipMemcpyAsync(S.h_hdr, S.d_ws, sizeof(TextHdr), hipMemcpyDeviceToHost, S.stream));
-    SGK_HIP_TRY(hipStreamSynchronize(S.stream));
-    if (S.h_hdr->flags & TEXT_FLAG_WORKSPACE) return SGK_ERR_WORKSPACE;
-    S.n_bytes = S.h_hdr->n_bytes;
-    rc = pipe_grow_dev(reinterpret_cast<void **>(&S.d_text), &S.d_text_cap, S.n_bytes + 16);
-    if (rc == SGK_OK) rc = pipe_grow_host(reinterpret_cast<void **>(&S.h_text), &S.h_text_cap, S.n_bytes + 16);
-    if (rc != SGK_OK) return rc;
-    rc = sgk_sref_text_write(&b, &names, S.d_text, S.n_bytes, S.d_ws, ws_bytes, S.stream);
-    if (rc != SGK_OK) return rc;
-    if (S.n_bytes) SGK_HIP_TRY(hipMemcpyAsync(S.h_text, S.d_text, S.n_bytes, hipMemcpyDeviceToHost, S.stream));
-    SGK_HIP_TRY(hipMemcpyAsync(S.h_hdr, S.d_ws, sizeof(TextHdr), hipMemcpyDeviceToHost, S.stream));
-    S.busy = 1;
-    return SGK_OK;
-}
-
-int sgk_sref_pipe_wait(sgk_sref_pipe_t *p, int slot, const uint8_t **text, uint64_t *n_bytes) {
-    if (!p || !text || !n_bytes || slot < 0 || slot > 1) return SGK_ERR_ARG;
-    sgk_sref_pipe::Slot &S = p->slot[slot];
-    if (!S.busy) return SGK_ERR_ARG;
-    S.busy = 0;
-    SGK_HIP_TRY(hipStreamSynchronize(S.stream));
-    if (S.h_hdr->flags & TEXT_FLAG_OVERFLOW) return SGK_ERR_CAPACITY;
-    *text = S.h_text;
-    *n_bytes = S.n_bytes;
     return SGK_OK;
 }
 

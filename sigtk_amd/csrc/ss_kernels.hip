@@ -24,8 +24,6 @@
 #include "text_format.h"
 #include "text_tiles.h"
 
-#include <new>
-
 namespace sgk {
 
 constexpr uint32_t SS_PAD = 0x01010101u;  // bytes outside the string: they end a token's look-back and start nothing
@@ -354,7 +352,7 @@ static int ss_text_args(const sgk_ss_batch_t *b, const uint64_t *out_offsets, co
     const int rc = ss_batch_check(b);
     if (rc != SGK_OK) return rc;
     if (sgk_device_count() <= 0) return SGK_ERR_NODEVICE;
-    if (!ws || (reinterpret_cast<uintptr_t>(ws) & 15u)) return SGK_ERR_ARG;
+    SGK_TRY(text_ws_check(ws, ws_bytes, 0));
     if (b->n_spans && (!b->spans || !ids || !ids->bytes || !ids->offsets || !out_offsets || !pairs)) return SGK_ERR_ARG;
     if (reinterpret_cast<uintptr_t>(pairs) & 7u) return SGK_ERR_ARG;
     ss_fill(b, a);
@@ -404,7 +402,7 @@ int sgk_ss_text_measure(const sgk_ss_batch_t *b, const uint64_t *out_offsets, co
     if (!row_offsets) return SGK_ERR_ARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
     a.row_offsets = row_offsets;
-    const uint32_t grid = a.n_tiles_max < TEXT_GRID_MAX ? a.n_tiles_max : TEXT_GRID_MAX;
+    const uint32_t grid = text_grid(a);
     SGK_LAUNCH("k_ss_tiles", k_ss_tiles, 1, 1024, st, a);
     SGK_LAUNCH("k_ss_measure", k_ss_measure, grid, TEXT_TILE, st, a);
     SGK_LAUNCH("k_ss_scan", k_ss_scan, 1, 1024, st, a);
@@ -419,240 +417,8 @@ int sgk_ss_text_write(const sgk_ss_batch_t *b, const uint64_t *out_offsets, cons
     if (!text && text_capacity) return SGK_ERR_ARG;
     a.text = text;
     a.text_cap = text_capacity;
-    const uint32_t grid = a.n_tiles_max < TEXT_GRID_MAX ? a.n_tiles_max : TEXT_GRID_MAX;
+    const uint32_t grid = text_grid(a);
     SGK_LAUNCH("k_ss_write", k_ss_write, grid, TEXT_TILE, static_cast<hipStream_t>(stream), a);
-    return SGK_OK;
-}
-
-// ---- host pipe (see the header): two slots, buffers grow on demand and are kept
-struct sgk_ss_pipe {
-    int device;
-    struct Slot {
-        hipStream_t stream;
-        uint8_t *h_in;  // pinned staging, filled by the caller between begin and submit
-        size_t h_in_cap;
-        uint64_t n_ss_bytes, id_bytes;
-        uint32_t n_records, n_spans, n_ids;
-        size_t off_rec, off_spans, off_ids, off_idoffs, in_bytes;
-        uint8_t *d_in;
-        size_t d_in_cap;
-        uint32_t *d_status, *h_status;
-        size_t d_status_cap, h_status_cap;
-        int32_t *d_ends;
-        size_t d_ends_cap;
-        uint64_t *d_offs, *h_offs;
-        size_t d_offs_cap, h_offs_cap;
-        int32_t *d_pairs;
-        size_t d_pairs_cap;
-        uint8_t *d_ws;
-        size_t d_ws_cap;
-        uint64_t *d_rows;
-        size_t d_rows_cap;
-        uint8_t *d_text, *h_text;
-        size_t d_text_cap, h_text_cap;
-        TextHdr *h_hdr;
-        uint64_t n_bytes;
-        uint32_t bad_record, bad_status;
-        int busy;
-    } slot[2];
-};
-
-static int ss_grow_dev(void **p, size_t *cap, size_t need) {
-    if (need <= *cap) return SGK_OK;
-    if (*p) SGK_HIP_TRY(hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    const size_t want = need + need / 4 + 4096;
-    SGK_HIP_TRY(hipMalloc(p, want));
-    *cap = want;
-    return SGK_OK;
-}
-static int ss_grow_host(void **p, size_t *cap, size_t need) {
-    if (need <= *cap) return SGK_OK;
-    if (*p) SGK_HIP_TRY(hipHostFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    const size_t want = need + need / 4 + 4096;
-    SGK_HIP_TRY(hipHostMalloc(p, want, hipHostMallocDefault));
-    *cap = want;
-    return SGK_OK;
-}
-#define SS_GROW_DEV(field, need) ss_grow_dev(reinterpret_cast<void **>(&S.field), &S.field##_cap, (need))
-#define SS_GROW_HOST(field, need) ss_grow_host(reinterpret_cast<void **>(&S.field), &S.field##_cap, (need))
-
-int sgk_ss_pipe_create(int device, sgk_ss_pipe_t **out) {
-    if (!out) return SGK_ERR_ARG;
-    *out = nullptr;
-    const int ndev = sgk_device_count();
-    if (ndev <= 0) return SGK_ERR_NODEVICE;
-    if (device < 0 || device >= ndev) return SGK_ERR_ARG;
-    SGK_HIP_TRY(hipSetDevice(device));
-    sgk_ss_pipe *p = new (std::nothrow) sgk_ss_pipe();
-    if (!p) return SGK_ERR_NOMEM;
-    p->device = device;
-    for (int s = 0; s < 2; ++s) {
-        if (hipStreamCreateWithFlags(&p->slot[s].stream, hipStreamNonBlocking) != hipSuccess ||
-            hipHostMalloc(reinterpret_cast<void **>(&p->slot[s].h_hdr), sizeof(TextHdr), hipHostMallocDefault) != hipSuccess) {
-            sgk_ss_pipe_destroy(p);
-            return SGK_ERR_HIP;
-        }
-    }
-    *out = p;
-    return SGK_OK;
-}
-
-void sgk_ss_pipe_destroy(sgk_ss_pipe_t *p) {
-    if (!p) return;
-    for (int s = 0; s < 2; ++s) {
-        sgk_ss_pipe::Slot &S = p->slot[s];
-        if (S.stream) {
-            (void)hipStreamSynchronize(S.stream);
-            (void)hipStreamDestroy(S.stream);
-        }
-        if (S.h_in) (void)hipHostFree(S.h_in);
-        if (S.h_status) (void)hipHostFree(S.h_status);
-        if (S.h_offs) (void)hipHostFree(S.h_offs);
-        if (S.h_text) (void)hipHostFree(S.h_text);
-        if (S.h_hdr) (void)hipHostFree(S.h_hdr);
-        if (S.d_in) (void)hipFree(S.d_in);
-        if (S.d_status) (void)hipFree(S.d_status);
-        if (S.d_ends) (void)hipFree(S.d_ends);
-        if (S.d_offs) (void)hipFree(S.d_offs);
-        if (S.d_pairs) (void)hipFree(S.d_pairs);
-        if (S.d_ws) (void)hipFree(S.d_ws);
-        if (S.d_rows) (void)hipFree(S.d_rows);
-        if (S.d_text) (void)hipFree(S.d_text);
-    }
-    delete p;
-}
-
-int sgk_ss_pipe_begin(sgk_ss_pipe_t *p, int slot, uint64_t n_ss_bytes, uint32_t n_records, uint32_t n_spans, uint32_t n_ids,
-                      uint64_t id_bytes, sgk_ss_stage_t *out) {
-    if (!p || !out || slot < 0 || slot > 1) return SGK_ERR_ARG;
-    sgk_ss_pipe::Slot &S = p->slot[slot];
-    if (S.busy) return SGK_ERR_ARG;
-    SGK_HIP_TRY(hipSetDevice(p->device));
-    S.n_ss_bytes = n_ss_bytes;
-    S.n_records = n_records;
-    S.n_spans = n_spans;
-    S.n_ids = n_ids;
-    S.id_bytes = id_bytes;
-    S.off_rec = round_up(n_ss_bytes + 16, 16);
-    S.off_spans = round_up(S.off_rec + (size_t)n_records * sizeof(sgk_ss_record_t), 16);
-    S.off_ids = round_up(S.off_spans + (size_t)n_spans * sizeof(sgk_ss_span_t), 16);
-    S.off_idoffs = round_up(S.off_ids + id_bytes + 16, 16);
-    S.in_bytes = round_up(S.off_idoffs + ((size_t)n_ids + 1) * 4, 16);
-    const int rc = SS_GROW_HOST(h_in, S.in_bytes);
-    if (rc != SGK_OK) return rc;
-    out->ss = S.h_in;
-    out->records = reinterpret_cast<sgk_ss_record_t *>(S.h_in + S.off_rec);
-    out->spans = reinterpret_cast<sgk_ss_span_t *>(S.h_in + S.off_spans);
-    out->id_bytes = S.h_in + S.off_ids;
-    out->id_offsets = reinterpret_cast<uint32_t *>(S.h_in + S.off_idoffs);
-    return SGK_OK;
-}
-
-int sgk_ss_pipe_submit(sgk_ss_pipe_t *p, int slot) {
-    if (!p || slot < 0 || slot > 1) return SGK_ERR_ARG;
-    sgk_ss_pipe::Slot &S = p->slot[slot];
-    if (S.busy || !S.h_in) return SGK_ERR_ARG;
-    SGK_HIP_TRY(hipSetDevice(p->device));
-    const sgk_ss_record_t *hr = reinterpret_cast<const sgk_ss_record_t *>(S.h_in + S.off_rec);
-    const sgk_ss_span_t *hs = reinterpret_cast<const sgk_ss_span_t *>(S.h_in + S.off_spans);
-    // what the caller staged must be consistent with itself before anything is sized from it
-    for (uint32_t r = 0; r < S.n_records; ++r) {
-        if (hr[r].ss_offset > S.n_ss_bytes || hr[r].ss_len > S.n_ss_bytes - hr[r].ss_offset) return SGK_ERR_ARG;
-        if (hr[r].id >= S.n_ids || hr[r].st_k > hr[r].end_k) return SGK_ERR_ARG;
-    }
-    for (uint32_t s = 0; s < S.n_spans; ++s) {
-        if (hs[s].record >= S.n_records || (s && hs[s].record < hs[s - 1].record)) return SGK_ERR_ARG;
-        const uint64_t rows = (uint64_t)((int64_t)hr[hs[s].record].end_k - (int64_t)hr[hs[s].record].st_k);
-        if ((uint64_t)hs[s].first + hs[s].count > rows) return SGK_ERR_ARG;
-    }
-    S.n_bytes = 0;
-    S.bad_record = 0xffffffffu;
-    S.bad_status = 0;
-    S.busy = 1;
-    if (S.n_records == 0) return SGK_OK;
-    const size_t n_st = S.n_records > S.n_spans ? S.n_records : S.n_spans;
-    int rc = SS_GROW_DEV(d_in, S.in_bytes);
-    if (rc == SGK_OK) rc = SS_GROW_DEV(d_status, n_st * 4);
-    if (rc == SGK_OK) rc = SS_GROW_DEV(d_ends, n_st * 8);
-    if (rc == SGK_OK) rc = SS_GROW_HOST(h_status, (size_t)S.n_records * 4);
-    if (rc != SGK_OK) return (S.busy = 0, rc);
-    SGK_HIP_TRY(hipMemcpyAsync(S.d_in, S.h_in, S.in_bytes, hipMemcpyHostToDevice, S.stream));
-    sgk_ss_batch_t b;
-    memset(&b, 0, sizeof b);
-    b.ss = S.d_in;
-    b.n_ss_bytes = S.n_ss_bytes;
-    b.records = reinterpret_cast<const sgk_ss_record_t *>(S.d_in + S.off_rec);
-    b.n_records = S.n_records;
-    // 1. validate: the status of every record, nothing stored
-    rc = sgk_ss_decode(&b, nullptr, nullptr, S.d_status, S.d_ends, S.stream);
-    if (rc != SGK_OK) return (S.busy = 0, rc);
-    SGK_HIP_TRY(hipMemcpyAsync(S.h_status, S.d_status, (size_t)S.n_records * 4, hipMemcpyDeviceToHost, S.stream));
-    SGK_HIP_TRY(hipStreamSynchronize(S.stream));
-    uint32_t bad = S.n_records;
-    for (uint32_t r = 0; r < S.n_records; ++r) {
-        if (S.h_status[r] != 0) {
-            bad = r;
-            S.bad_record = r;
-            S.bad_status = S.h_status[r];
-            break;
-        }
-    }
-    // 2. the spans in front of the first bad record get table and text space
-    uint32_t keep = 0;
-    while (keep < S.n_spans && hs[keep].record < bad) ++keep;
-    if (keep == 0) return SGK_OK;
-    rc = SS_GROW_HOST(h_offs, (size_t)keep * 8);
-    if (rc != SGK_OK) return (S.busy = 0, rc);
-    uint64_t n_rows = 0;
-    for (uint32_t s = 0; s < keep; ++s) {
-        S.h_offs[s] = n_rows;
-        n_rows += hs[s].count;
-    }
-    const size_t ws_bytes = sgk_ss_text_workspace_bytes(keep, n_rows);
-    rc = SS_GROW_DEV(d_offs, (size_t)keep * 8);
-    if (rc == SGK_OK) rc = SS_GROW_DEV(d_pairs, (size_t)n_rows * 8 + 16);
-    if (rc == SGK_OK) rc = SS_GROW_DEV(d_ws, ws_bytes);
-    if (rc == SGK_OK) rc = SS_GROW_DEV(d_rows, ((size_t)keep + 1) * 8);
-    if (rc != SGK_OK) return (S.busy = 0, rc);
-    SGK_HIP_TRY(hipMemcpyAsync(S.d_offs, S.h_offs, (size_t)keep * 8, hipMemcpyHostToDevice, S.stream));
-    if (n_rows) SGK_HIP_TRY(hipMemsetAsync(S.d_pairs, 0xff, (size_t)n_rows * 8, S.stream));
-    b.spans = reinterpret_cast<const sgk_ss_span_t *>(S.d_in + S.off_spans);
-    b.n_spans = keep;
-    rc = sgk_ss_decode(&b, S.d_offs, S.d_pairs, S.d_status, S.d_ends, S.stream);
-    if (rc != SGK_OK) return (S.busy = 0, rc);
-    sgk_text_ids_t ids = {S.d_in + S.off_ids, reinterpret_cast<const uint32_t *>(S.d_in + S.off_idoffs)};
-    rc = sgk_ss_text_measure(&b, S.d_offs, S.d_pairs, &ids, S.d_rows, S.d_ws, ws_bytes, S.stream);
-    if (rc != SGK_OK) return (S.busy = 0, rc);
-    SGK_HIP_TRY(hipMemcpyAsync(S.h_hdr, S.d_ws, sizeof(TextHdr), hipMemcpyDeviceToHost, S.stream));
-    SGK_HIP_TRY(hipStreamSynchronize(S.stream));
-    if (S.h_hdr->flags & TEXT_FLAG_WORKSPACE) return (S.busy = 0, SGK_ERR_WORKSPACE);
-    S.n_bytes = S.h_hdr->n_bytes;
-    rc = SS_GROW_DEV(d_text, S.n_bytes + 16);
-    if (rc == SGK_OK) rc = SS_GROW_HOST(h_text, S.n_bytes + 16);
-    if (rc != SGK_OK) return (S.busy = 0, rc);
-    rc = sgk_ss_text_write(&b, S.d_offs, S.d_pairs, &ids, S.d_text, S.n_bytes, S.d_ws, ws_bytes, S.stream);
-    if (rc != SGK_OK) return (S.busy = 0, rc);
-    if (S.n_bytes) SGK_HIP_TRY(hipMemcpyAsync(S.h_text, S.d_text, S.n_bytes, hipMemcpyDeviceToHost, S.stream));
-    SGK_HIP_TRY(hipMemcpyAsync(S.h_hdr, S.d_ws, sizeof(TextHdr), hipMemcpyDeviceToHost, S.stream));
-    return SGK_OK;
-}
-
-int sgk_ss_pipe_wait(sgk_ss_pipe_t *p, int slot, const uint8_t **text, uint64_t *n_bytes, uint32_t *bad_record,
-                     uint32_t *bad_status) {
-    if (!p || !text || !n_bytes || !bad_record || !bad_status || slot < 0 || slot > 1) return SGK_ERR_ARG;
-    sgk_ss_pipe::Slot &S = p->slot[slot];
-    if (!S.busy) return SGK_ERR_ARG;
-    S.busy = 0;
-    SGK_HIP_TRY(hipStreamSynchronize(S.stream));
-    if (S.n_bytes && (S.h_hdr->flags & TEXT_FLAG_OVERFLOW)) return SGK_ERR_CAPACITY;
-    *text = S.h_text;
-    *n_bytes = S.n_bytes;
-    *bad_record = S.bad_record;
-    *bad_status = S.bad_status;
     return SGK_OK;
 }
 

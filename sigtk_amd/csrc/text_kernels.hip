@@ -306,8 +306,7 @@ static int text_args(int kind, const sgk_batch_t *b, const sgk_text_ids_t *ids, 
     if (kind < SGK_TEXT_PA || kind > SGK_TEXT_EVENT_COMPACT) return SGK_ERR_ARG;
     const int rc = check_batch(b);
     if (rc != SGK_OK) return rc;
-    if (!ws || (reinterpret_cast<uintptr_t>(ws) & 15u)) return SGK_ERR_ARG;
-    if (ws_bytes < sizeof(TextHdr)) return SGK_ERR_WORKSPACE;
+    SGK_TRY(text_ws_check(ws, ws_bytes, sizeof(TextHdr)));
     if (b->n_reads && (!ids || !ids->bytes || !ids->offsets)) return SGK_ERR_ARG;
     if (b->n_reads && kind != SGK_TEXT_PA && (!ev_slots || !events || !n_events)) return SGK_ERR_ARG;
     if (kind != SGK_TEXT_PA && (reinterpret_cast<uintptr_t>(events) & 15u)) return SGK_ERR_ALIGN;
@@ -349,7 +348,7 @@ int sgk_text_measure(int kind, const sgk_batch_t *b, const sgk_text_ids_t *ids, 
     if (!row_offsets) return SGK_ERR_ARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
     a.row_offsets = row_offsets;
-    const uint32_t grid = a.n_tiles_max < TEXT_GRID_MAX ? a.n_tiles_max : TEXT_GRID_MAX;
+    const uint32_t grid = text_grid(a);
     switch (kind) {
         case SGK_TEXT_PA:
             SGK_LAUNCH("k_text_tiles", k_text_tiles<SGK_TEXT_PA>, 1, 1024, st, a);
@@ -378,7 +377,7 @@ int sgk_text_write(int kind, const sgk_batch_t *b, const sgk_text_ids_t *ids, co
     hipStream_t st = static_cast<hipStream_t>(stream);
     a.text = text;
     a.text_cap = text_capacity;
-    const uint32_t grid = a.n_tiles_max < TEXT_GRID_MAX ? a.n_tiles_max : TEXT_GRID_MAX;
+    const uint32_t grid = text_grid(a);
     switch (kind) {
         case SGK_TEXT_PA: SGK_LAUNCH("k_text_write_pa", k_text_write<SGK_TEXT_PA>, grid, TEXT_TILE, st, a); break;
         case SGK_TEXT_EVENT: SGK_LAUNCH("k_text_write_event", k_text_write<SGK_TEXT_EVENT>, grid, TEXT_TILE, st, a); break;

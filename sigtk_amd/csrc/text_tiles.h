@@ -1,5 +1,7 @@
 // text_tiles.h -- what the device-side text writers share whatever their grammar (text_kernels.hip: pa / event /
-// event -c rows of a batch of reads; sref_kernels.hip: spans of `sref` rows).
+// event -c rows of a batch of reads; slow5_text_kernels.hip: the signal column of text SLOW5 records; sref_kernels.hip:
+// spans of `sref` rows; ss_kernels.hip: spans of `ss paf2tsv` rows).  What the host pipes of the last two share is
+// text_pipe.h.
 //
 // A writer's rows (reads, spans) have items (samples, events, signal positions).  The items of every row are cut into
 // tiles of 256, one workgroup per tile and one item per lane; a row has at least one tile, which carries its fixed
@@ -60,6 +62,13 @@ static inline bool tile_list_carve(void *w_, size_t bytes, uint32_t n_rows, Tile
     l->tile_bytes = reinterpret_cast<uint32_t *>(w + off_bytes);
     l->tile_off = reinterpret_cast<uint64_t *>(w + round_up(off_bytes + (size_t)nt * 4, 16));
     return true;
+}
+// workgroups of a measure or write kernel: they stride over the tile list
+static inline uint32_t text_grid(const TileList &l) { return l.n_tiles_max < TEXT_GRID_MAX ? l.n_tiles_max : TEXT_GRID_MAX; }
+// a caller's workspace: missing or not 16-byte aligned is SGK_ERR_ARG, fewer than min_bytes SGK_ERR_WORKSPACE
+static inline int text_ws_check(const void *ws, size_t ws_bytes, size_t min_bytes) {
+    if (!ws || (reinterpret_cast<uintptr_t>(ws) & 15u)) return SGK_ERR_ARG;
+    return ws_bytes < min_bytes ? SGK_ERR_WORKSPACE : SGK_OK;
 }
 
 #if defined(__HIPCC__)
