@@ -1213,6 +1213,50 @@ int sgk_jnn_f32(const float *x, const uint64_t *offsets, const uint32_t *lengths
                 uint64_t n_values, const sgk_jnn_param_t *p, const float *top, const float *bot, const uint64_t *seg_slots,
                 int32_t *seg_x, int32_t *seg_y, uint32_t *n_segs, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- normalised signals (additive to 0.2.3) ---------------------------------------------------------------------------
+ * y[i] = (x[i] - shift) / scale for every value of every read, in float32: one float subtraction and one correctly
+ * rounded float division, no contraction, no reciprocal, subnormal quotients kept.  With meanf / stdvf / medianf as
+ * sgk_stat_f32 delivers them (bit for bit the reference's, src/stat.h):
+ *   SGK_NORM_ZSCORE  shift = meanf(x),   scale = stdvf(x)
+ *   SGK_NORM_MEDMAD  shift = medianf(x), scale = medianf(d) * 1.4826f (one float multiply), d[i] = fabsf(x[i] - shift),
+ *                    medianf(d) the order statistic of rank n / 2, as everywhere
+ * What IEEE makes of the formula is the result: a constant read has scale == 0 and every y = 0 / 0 = NaN, a read with
+ * mad == 0 that is not constant gets +-inf and NaN; the record of such a read carries SGK_NORM_ZERO_SCALE.  A read holding
+ * a NaN or an infinity (no reference function says what its normalisation is): SGK_NORM_NONFINITE, shift and scale NaN,
+ * every y of the read NaN.  A read of no values: nothing of y is written, shift and scale NaN, flags 0.  Where
+ * sgk_stat_f32 would leave SGK_MEDIAN_INEXACT on the read's median the record keeps that bit (never with a workspace of
+ * the size function's while the read fits SGK_LITERAL_MAX_BYTES).
+ * sgk_normalise_f32 takes a float batch under the contract above (x 4-byte aligned, offsets any element index, reads may
+ * touch but not overlap, no byte outside the reads is read, asynchronous, no allocation, no host round trip).  y has x's
+ * layout, y[offsets[r] + i], and is 4-byte aligned; y may be x itself (in place), otherwise [y, y + n_values) must not
+ * overlap [x, x + n_values) (SGK_ERR_ARG).  No byte of y outside the reads is written: not a gap, not a neighbour, not
+ * the slack in front of an unaligned first value.  rec: n_reads records.  A method other than the two, or a null pointer
+ * with n_reads > 0, is SGK_ERR_ARG; a short workspace SGK_ERR_WORKSPACE with nothing written; SGK_ERR_NODEVICE comes
+ * after the argument checks; n_reads == 0 is SGK_OK.
+ * sgk_normalise is the same for an int16 batch: x is sgk_pa of the batch, written into y and normalised there.
+ * DESIGN.md 3.19. */
+#define SGK_NORM_ZSCORE 1
+#define SGK_NORM_MEDMAD 2
+#define SGK_NORM_ZERO_SCALE 1u /* sgk_norm_rec_t::flags: scale == 0 */
+#define SGK_NORM_NONFINITE 2u  /* ... the read holds a NaN or an infinity (SGK_MEDIAN_INEXACT, 4u, is the third bit) */
+typedef struct sgk_norm_rec {
+    float shift, scale;
+    uint32_t n, flags;
+} sgk_norm_rec_t; /* 16 bytes */
+size_t sgk_normalise_f32_workspace_bytes(uint32_t n_reads, uint64_t n_values, uint32_t max_read_len);
+int sgk_normalise_f32(const float *x, const uint64_t *offsets, const uint32_t *lengths, uint32_t n_reads, uint32_t max_read_len,
+                      uint64_t n_values, int method, float *y, sgk_norm_rec_t *rec, void *workspace, size_t workspace_bytes,
+                      void *stream);
+size_t sgk_normalise_workspace_bytes(uint32_t n_reads, uint64_t n_samples, uint32_t max_read_len);
+int sgk_normalise(const sgk_batch_t *batch, int method, float *y, sgk_norm_rec_t *rec, void *workspace, size_t workspace_bytes,
+                  void *stream);
+/* The job's SGK_TOOL_PA submits from now on: 0 the pA values (the default), SGK_NORM_* the normalised signal in their
+ * place (sgk_job_output_t::pa; every input format).  Any other method is SGK_ERR_ARG.  No other tool looks at it; a
+ * SGK_TOOL_PA submit with SGK_JOB_TEXT is SGK_ERR_ARG while it is set.  The job keeps the sgk_norm_rec_t records on the
+ * device and hands none of them out: shift, scale, SGK_NORM_ZERO_SCALE and SGK_NORM_NONFINITE of a read are to be had
+ * from sgk_normalise / sgk_normalise_f32 alone. */
+int sgk_job_set_normalise(sgk_job_t *job, int method);
+
 #ifdef __cplusplus
 }
 #endif

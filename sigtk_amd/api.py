@@ -360,6 +360,9 @@ ABI_SYMBOLS = [
     "sgk_debug_roll_means",
     # stat and jnn on batches of float signals (csrc/statf_kernels.hip, jnnf_kernels.hip)
     "sgk_stat_f32_workspace_bytes", "sgk_stat_f32", "sgk_jnn_f32_workspace_bytes", "sgk_jnn_f32",
+    # normalised signals (csrc/normf_kernels.hip)
+    "sgk_normalise_f32_workspace_bytes", "sgk_normalise_f32", "sgk_normalise_workspace_bytes", "sgk_normalise",
+    "sgk_job_set_normalise",
     "sgk_meanf", "sgk_meani16", "sgk_stdvf", "sgk_stdvi16", "sgk_medianf", "sgk_mediani16", "sgk_shim_status",
 ]
 
@@ -796,12 +799,18 @@ class StatFRec(C.Structure):   # sgk_statf_rec_t
 
 STATF_DTYPE = np.dtype([("mean", "<f4"), ("std", "<f4"), ("median", "<f4"), ("flags", "<u4")])
 MEDIAN_INEXACT = 4
+# sgk_norm_rec_t; the methods of sgk_normalise_f32 / sgk_normalise and the flags of a record (MEDIAN_INEXACT is the third)
+NORM_DTYPE = np.dtype([("shift", "<f4"), ("scale", "<f4"), ("n", "<u4"), ("flags", "<u4")])
+NORM_ZSCORE, NORM_MEDMAD = 1, 2
+NORM_METHODS = {"zscore": NORM_ZSCORE, "medmad": NORM_MEDMAD}
+NORM_ZERO_SCALE, NORM_NONFINITE = 1, 2
 
 
 def _float_lib():
     L = load_library()
     if not getattr(L, "_float_batch_bound", False):
-        for f in ("sgk_stat_f32_workspace_bytes", "sgk_jnn_f32_workspace_bytes"):
+        for f in ("sgk_stat_f32_workspace_bytes", "sgk_jnn_f32_workspace_bytes", "sgk_normalise_f32_workspace_bytes",
+                  "sgk_normalise_workspace_bytes"):
             getattr(L, f).restype = C.c_size_t
             getattr(L, f).argtypes = [C.c_uint32, C.c_uint64, C.c_uint32]
         batch = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64]
@@ -809,6 +818,12 @@ def _float_lib():
         L.sgk_stat_f32.argtypes = batch + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.sgk_jnn_f32.restype = C.c_int
         L.sgk_jnn_f32.argtypes = batch + [C.POINTER(JnnParam)] + [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p]
+        L.sgk_normalise_f32.restype = C.c_int
+        L.sgk_normalise_f32.argtypes = batch + [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.sgk_normalise.restype = C.c_int
+        L.sgk_normalise.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.sgk_job_set_normalise.restype = C.c_int
+        L.sgk_job_set_normalise.argtypes = [C.c_void_p, C.c_int]
         L._float_batch_bound = True
     return L
 
@@ -966,6 +981,10 @@ class Job:
         """adaptor / polyA parameters of the job's prefix submits from now on (copied); None: the presets by `pore`"""
         check(_param_lib().sgk_job_set_prefix_params(self.h, C.byref(params) if params is not None else None),
               "sgk_job_set_prefix_params")
+
+    def set_normalise(self, method: int = 0):
+        """the job's pa submits hand out the normalised signal (NORM_ZSCORE / NORM_MEDMAD) from now on; 0: pA again"""
+        check(_float_lib().sgk_job_set_normalise(self.h, int(method)), "sgk_job_set_normalise")
 
     def close(self):
         if self.h:

@@ -22,7 +22,7 @@ CLI = os.path.join(PKG, "sigtk-amd")
 CLI_ASAN = os.path.join(PKG, "sigtk-amd-asan")
 
 EVENT_SOURCES = ["event_plan.hip", "event_launch.hip","event_whole.hip", "event_seg.hip", "event_multi.hip", "event_fallback.hip", "event_param.hip"]
-HIP_SOURCES = ["api.hip", "api_stat.hip", *EVENT_SOURCES, "stat_launch.hip", "stat_lane.hip", "stat_wave.hip", "stat_long.hip", "stat_literal.hip", "stat_param.hip", "statf_kernels.hip", "jnnf_kernels.hip",
+HIP_SOURCES = ["api.hip", "api_stat.hip", *EVENT_SOURCES, "stat_launch.hip", "stat_lane.hip", "stat_wave.hip", "stat_long.hip", "stat_literal.hip", "stat_param.hip", "statf_kernels.hip", "normf_kernels.hip", "jnnf_kernels.hip",
                "misc_kernels.hip", "svb_kernels.hip", "sigtext_kernels.hip", "inflate_kernels.hip", "deflate_kernels.hip", "zstd_kernels.hip", "zrec_kernels.hip", "sigraw_kernels.hip", "ent_kernels.hip",
                "qts_kernels.hip", "text_kernels.hip", "slow5_text_kernels.hip", "sref_kernels.hip", "ss_kernels.hip", "text_pipes.hip", "job.hip", "job_submit.hip", "job_qts.hip", "job_kernels.hip", "shims.hip"]
 # Per-source flags.  The SLP vectoriser pairs the detector's f32 arithmetic into v_pk_*_f32, which issue at the cost of

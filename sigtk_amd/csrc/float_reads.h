@@ -61,6 +61,26 @@ struct FloatRead {  // wave-uniform
             }
         }
     }
+    // load's mirror: this lane's 16 positions of tile t into an array of x's layout.  yq + q is where position q goes (the
+    // read's first value at yq + skip); `aligned`: yq is a 16-byte boundary, as xb is.  A group inside the read is one
+    // 16-byte store, a group that straddles an end of the read is stored value by value, each behind its own test, and a
+    // group outside the read is not stored at all: no byte outside the read is written -- not a gap, not a neighbour, not
+    // the slack in front of an unaligned first value.  An array whose 16-byte phase differs from x's is stored value by
+    // value throughout.
+    __device__ __forceinline__ void store(float *yq, bool aligned, const float (&v)[SS_SPL], int t) const {
+        const int64_t q0 = (int64_t)t * SS_TILE + lane_id() * SS_SPL;
+#pragma unroll
+        for (int g = 0; g < SS_SPL / 4; ++g) {
+            const int64_t q = q0 + 4 * g;
+            if (aligned && q >= skip && q + 4 <= nq) {
+                *static_cast<float4 *>(__builtin_assume_aligned(yq + q, 16)) = float4{v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]};
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (q + k >= skip && q + k < nq) yq[q + k] = v[4 * g + k];
+            }
+        }
+    }
 };
 
 // host side (statf_kernels.hip): the argument checks both entry points share, and the dispatch order of a batch of
@@ -70,6 +90,8 @@ int float_batch_order(FloatBatch &b, void *ws, hipStream_t st);
 // What sgk_stat_f32 launches once its arguments are checked (b.order is the launcher's to fill; ws: 16-byte aligned, of
 // the size sgk_stat_f32_workspace_bytes gives).  The float stat shims call it directly.
 int launch_statf(FloatBatch b, uint32_t max_read_len, sgk_statf_rec_t *out, void *ws, hipStream_t st);
+// ... for a batch whose b.order the caller has filled with float_batch_order on the same workspace (sgk_normalise_f32)
+int launch_statf_ordered(const FloatBatch &b, uint32_t max_read_len, sgk_statf_rec_t *out, void *ws, hipStream_t st);
 
 // the read a wave takes: four waves per workgroup, longest reads first where the batch has a dispatch order
 __device__ __forceinline__ bool float_wave_read(const FloatBatch &b, uint32_t &r) {

@@ -30,7 +30,7 @@ struct sgk_job {
     sgk::Pair<double> dig, off, rng;
     // d_ws: the tool's workspace -- words, LongHdr behind the dispatch order (stat / jnn / prefix), the event status
     sgk::Bytes<sgk::Mem::Dev> d_ws;
-    // d_out: pa float | events sgk_event_rec_t | seg x, y int32 | stat, prefix, ent records (+ ent overflow uint16 x 2) |
+    // d_out: pa float (+ sgk_norm_rec_t with sgk_job_set_normalise) | events sgk_event_rec_t | seg x, y int32 | stat, prefix, ent records (+ ent overflow uint16 x 2) |
     //        qts blobs uint8, their offsets uint64;  h_out: the same fetched, or the dense arrays | qts samples int16
     sgk::Bytes<sgk::Mem::Dev> d_out[4];
     sgk::Bytes<sgk::Mem::Pin> h_out[4];
@@ -105,6 +105,7 @@ struct sgk_job {
     sgk_jnn_param_t jnn_params;
     sgk_prefix_params_t prefix_params;
     bool has_ev_params = false, has_jnn_params = false, has_prefix_params = false;
+    int normalise = 0;                  // sgk_job_set_normalise: SGK_TOOL_PA hands out sgk_normalise of the batch (0: pA)
 };
 
 namespace sgk {

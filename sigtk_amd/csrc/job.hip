@@ -144,6 +144,12 @@ int sgk_job_set_prefix_params(sgk_job_t *j, const sgk_prefix_params_t *params) {
     return SGK_OK;
 }
 
+int sgk_job_set_normalise(sgk_job_t *j, int method) {
+    if (!j || (method != 0 && method != SGK_NORM_ZSCORE && method != SGK_NORM_MEDMAD)) return SGK_ERR_ARG;
+    j->normalise = method;
+    return SGK_OK;
+}
+
 void sgk_job_destroy(sgk_job_t *j) {
     if (!j) return;
     (void)hipSetDevice(j->device);

@@ -92,6 +92,7 @@ extern "C" int sgk_job_submit(sgk_job_t *j, int tool, int rna, int pore, int fla
     if (tool < SGK_TOOL_PA || tool > SGK_TOOL_ENT) return SGK_ERR_ARG;
     const bool text = (flags & SGK_JOB_TEXT) != 0;
     if (text && ((tool != SGK_TOOL_PA && tool != SGK_TOOL_EVENT) || !j->have_ids)) return SGK_ERR_ARG;
+    if (text && tool == SGK_TOOL_PA && j->normalise) return SGK_ERR_ARG;  // the device formatter writes pA rows
     SGK_HIP_TRY(hipSetDevice(j->device));
     static const Result kinds[] = {Result::Pa, Result::Events, Result::Stat, Result::Segments, Result::Prefix, Result::Ent};
     static_assert(SGK_TOOL_PA == 0 && SGK_TOOL_EVENT == 1 && SGK_TOOL_STAT == 2 && SGK_TOOL_JNN == 3 && SGK_TOOL_PREFIX == 4 &&
@@ -112,7 +113,14 @@ extern "C" int sgk_job_submit(sgk_job_t *j, int tool, int rna, int pore, int fla
             }
             const size_t bytes = j->n_samples * sizeof(float);
             SGK_TRY(j->d_out[0].ensure(bytes));
-            SGK_TRY(sgk_pa(&view, j->d_out[0].as<float>(), st));
+            if (j->normalise) {  // the float array that goes home is the normalised one; the records stay on the device
+                SGK_TRY(j->d_out[1].ensure(nr * sizeof(sgk_norm_rec_t)));
+                j->ws_bytes = sgk_normalise_workspace_bytes(j->n_reads, j->n_samples, j->max_len);
+                SGK_TRY(j->d_ws.ensure(j->ws_bytes));
+                SGK_TRY(sgk_normalise(&view, j->normalise, j->d_out[0].as<float>(), j->d_out[1].as<sgk_norm_rec_t>(), j->d_ws.p,
+                                      j->d_ws.cap, st));
+            } else
+                SGK_TRY(sgk_pa(&view, j->d_out[0].as<float>(), st));
             SGK_TRY(fetch(j->h_out[0], j->d_out[0].p, bytes, st));
             break;
         }

@@ -4,76 +4,20 @@
 //       1. the sequential sum (seqsum.h)               + the counts of the keys' top 11 bits + "not finite" / "a NaN"
 //       2. the sequential sum of squared deviations    + the counts of the next 11 bits among the keys that matched
 //       3.                                               the counts of the last 10 bits
-//     The key of a float is its order-preserving integer image; the order statistic of rank n / 2 is found level by level
-//     from a 2 048-bin histogram in the wave's 8 KB of LDS.  A lane counts runs of equal bins among its 16 consecutive
-//     values and adds a run at a time: a nanopore read keeps to a few of the top-level bins, and 1 024 atomics on three
-//     LDS words per tile would otherwise cost more than the tile's HBM traffic.
+//     The order statistic of rank n / 2 is found level by level from a 2 048-bin histogram of the values' keys in the
+//     wave's 8 KB of LDS (statf_radix.h, shared with k_normf_wave).
 //   * k_statf_literal behind it (the scheme of k_median_literal, stat_literal.hip) looks at every record once and redoes
 //     the hostile ones by one lane: a median that is a zero, or of an array holding a NaN, with the reference's own
 //     selection on a scratch row of the workspace (median_literal.h); mean and deviation of an array holding a NaN or an
 //     infinity with x86's NaN rules (x86_mean_std).  Between the two kernels the record's `flags` carries what is to do.
 // A read is never split over workgroups (float_reads.h).
-#include "float_reads.h"
 #include "median_literal.h"
+#include "statf_radix.h"
 
 namespace sgk {
 
 constexpr uint32_t SF_NONFINITE = 1u, SF_PICK = 2u;  // sgk_statf_rec_t::flags between the two kernels
 static_assert((SF_NONFINITE | SF_PICK) < SGK_MEDIAN_INEXACT, "the flag a record keeps");
-constexpr int SF_BINS = 2048;
-
-__device__ __forceinline__ uint32_t statf_key(float f) {  // a < b  <=>  key(a) < key(b) (zeros: -0 below +0)
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// this lane's values whose key matches `prefix` on the bits `known` into hist[(key >> shift) & mask], a run at a time
-__device__ __forceinline__ void statf_count(const float (&x)[SS_SPL], uint32_t vm, uint32_t known, uint32_t prefix, int shift,
-                                            uint32_t mask, uint32_t *hist) {
-    uint32_t cb = 0u, cc = 0u;
-#pragma unroll
-    for (int e = 0; e < SS_SPL; ++e) {
-        const uint32_t k = statf_key(x[e]);
-        if (((vm >> e) & 1u) && (k & known) == prefix) {
-            const uint32_t b = (k >> shift) & mask;
-            if (cc && b != cb) { atomicAdd(&hist[cb], cc); cc = 0u; }
-            cb = b;
-            ++cc;
-        }
-    }
-    if (cc) atomicAdd(&hist[cb], cc);
-}
-__device__ __forceinline__ void statf_clear(uint32_t *hist) {
-#pragma unroll
-    for (int i = 0; i < SF_BINS / 64; ++i) hist[i * 64 + lane_id()] = 0u;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-// the bin that holds rank `rank` of the complete histogram (wave-uniform); rank becomes the rank inside that bin
-__device__ inline uint32_t statf_pick(const uint32_t *hist, uint32_t &rank) {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    const int lane = lane_id();
-    constexpr int PER = SF_BINS / 64;
-    uint32_t cnt[PER], lsum = 0u;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) { cnt[i] = hist[lane * PER + i]; lsum += cnt[i]; }
-    const uint32_t incl = (uint32_t)wave_incl_scan_i((int)lsum), excl = incl - lsum;
-    const bool mine = rank >= excl && rank < incl;
-    uint32_t bin = 0u, below = 0u;
-    if (mine) {
-        uint32_t acc = excl;
-#pragma unroll
-        for (int i = 0; i < PER; ++i) {
-            if (rank >= acc && rank < acc + cnt[i]) { bin = (uint32_t)(lane * PER + i); below = acc; }
-            acc += cnt[i];
-        }
-    }
-    const unsigned long long own = __ballot(mine);
-    const int l = own ? __builtin_amdgcn_readfirstlane(__ffsll((long long)own) - 1) : 0;
-    rank -= (uint32_t)__builtin_amdgcn_readlane((int)below, l);
-    return (uint32_t)__builtin_amdgcn_readlane((int)bin, l);
-}
 
 __global__ __launch_bounds__(256) void k_statf_wave(FloatBatch b, sgk_statf_rec_t *out) {
     __shared__ __attribute__((aligned(16))) uint32_t hist_all[4][SF_BINS];
@@ -88,24 +32,25 @@ __global__ __launch_bounds__(256) void k_statf_wave(FloatBatch b, sgk_statf_rec_
         return;
     }
     uint32_t rank = (uint32_t)(n / 2), hostile = 0u;
+    const auto same = [](float v) { return v; };  // the keys are those of the values themselves
     statf_clear(hist);
     const float s = fr_chain(fr, [](float v) { return v; }, [&](int, const float (&x)[SS_SPL], uint32_t vm) {
 #pragma unroll
         for (int e = 0; e < SS_SPL; ++e)
             if (((vm >> e) & 1u) && !(fabsf(x[e]) < __builtin_inff())) hostile |= x[e] != x[e] ? (SF_NONFINITE | SF_PICK) : SF_NONFINITE;
-        statf_count(x, vm, 0u, 0u, 21, 0x7ffu, hist);
+        statf_count(x, vm, 0u, 0u, 21, 0x7ffu, hist, same);
     });
     const float mn = s / n;
     uint32_t prefix = statf_pick(hist, rank) << 21;
     statf_clear(hist);
     const float q = fr_chain(fr, [&](float v) { return (v - mn) * (v - mn); }, [&](int, const float (&x)[SS_SPL], uint32_t vm) {
-        statf_count(x, vm, 0xffe00000u, prefix, 10, 0x7ffu, hist);
+        statf_count(x, vm, 0xffe00000u, prefix, 10, 0x7ffu, hist, same);
     });
     prefix |= statf_pick(hist, rank) << 10;
     statf_clear(hist);
-    fr_sweep(fr, [&](int, const float (&x)[SS_SPL], uint32_t vm) { statf_count(x, vm, 0xfffffc00u, prefix, 0, 0x3ffu, hist); });
+    fr_sweep(fr, [&](int, const float (&x)[SS_SPL], uint32_t vm) { statf_count(x, vm, 0xfffffc00u, prefix, 0, 0x3ffu, hist, same); });
     prefix |= statf_pick(hist, rank);
-    const float med = __uint_as_float((prefix & 0x80000000u) ? (prefix & 0x7fffffffu) : ~prefix);
+    const float med = statf_unkey(prefix);
     hostile = __ballot(hostile & SF_NONFINITE) ? SF_NONFINITE | (__ballot(hostile & SF_PICK) ? SF_PICK : 0u) : 0u;
     if (med == 0.0f) hostile |= SF_PICK;  // +0 and -0 compare equal: the reference's pick
     if (lane_id() == 0) out[r] = sgk_statf_rec_t{mn, sqrtf(q / n), med, hostile};
@@ -168,13 +113,16 @@ int float_batch_order(FloatBatch &b, void *ws, hipStream_t st) {
     return SGK_OK;
 }
 
-int launch_statf(FloatBatch b, uint32_t max_read_len, sgk_statf_rec_t *out, void *ws, hipStream_t st) {
-    SGK_TRY(float_batch_order(b, ws, st));
+int launch_statf_ordered(const FloatBatch &b, uint32_t max_read_len, sgk_statf_rec_t *out, void *ws, hipStream_t st) {
     SGK_LAUNCH("k_statf_wave", k_statf_wave, (b.n_reads + 3) / 4, 256, st, b, out);
     float *scratch = reinterpret_cast<float *>(static_cast<char *>(ws) + order_workspace_bytes(b.n_reads));
     SGK_LAUNCH("k_statf_literal", k_statf_literal, (uint32_t)statf_rows(b.n_reads, max_read_len), 64, st, b, out, scratch,
                statf_stride(max_read_len));
     return SGK_OK;
+}
+int launch_statf(FloatBatch b, uint32_t max_read_len, sgk_statf_rec_t *out, void *ws, hipStream_t st) {
+    SGK_TRY(float_batch_order(b, ws, st));
+    return launch_statf_ordered(b, max_read_len, out, ws, st);
 }
 
 }  // namespace sgk

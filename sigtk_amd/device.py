@@ -45,6 +45,23 @@ class DeviceReads:
     def total_samples(self) -> int:
         return int(self.lengths_host.astype(np.int64).sum())
 
+    def normalise(self, method: int, y: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None):
+        """sgk_normalise: the batch's pA signal normalised (api.NORM_ZSCORE / api.NORM_MEDMAD) -> (y, records): y a
+        float32 tensor of the samples' layout (y[offsets[r] + i]; what lies outside the reads is left as it was), records
+        a uint8 tensor holding n_reads sgk_norm_rec_t (view it with api.NORM_DTYPE)."""
+        L = api._float_lib()
+        dev = self.samples.device
+        if y is None:
+            y = torch.zeros(self.n_samples, dtype=torch.float32, device=dev)
+        rec = torch.zeros(max(self.n_reads, 1) * api.NORM_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        if ws is None:
+            n = int(L.sgk_normalise_workspace_bytes(self.n_reads, self.n_samples, self.max_read_len))
+            ws = torch.zeros(max(n, 64), dtype=torch.uint8, device=dev)
+        view = self.view()
+        api.check(L.sgk_normalise(C.addressof(view), int(method), _ptr(y), _ptr(rec), _ptr(ws), ws.numel(), _stream_ptr()),
+                  "sgk_normalise")
+        return y, rec
+
 
 def alloc_reads(lengths: np.ndarray, device: torch.device, align: int = 64, leads=None) -> DeviceReads:
     """Lay out reads of the given lengths with every read starting on an `align`-sample boundary, or, with `leads`,
@@ -320,7 +337,7 @@ def jnn(b: DeviceReads, arena: SegArena, rna: int, params: "api.JnnParam" = None
               "sgk_jnn_opt")
 
 
-# ---------------------------------------------------------------------- float (pA) batches: sgk_stat_f32, sgk_jnn_f32
+# ------------------------------------------------------- float (pA) batches: sgk_stat_f32, sgk_jnn_f32, sgk_normalise_f32
 @dataclass
 class FloatReads:
     """A batch of float signals resident in HBM: read r is x[offsets[r] : offsets[r] + lengths[r]], at any element
@@ -337,6 +354,20 @@ class FloatReads:
     def view(self):
         """the six leading arguments of sgk_stat_f32 / sgk_jnn_f32"""
         return (_ptr(self.x), _ptr(self.offsets), _ptr(self.lengths), self.n_reads, self.max_read_len, self.n_values)
+
+    def normalise_f32(self, method: int, y: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None):
+        """sgk_normalise_f32 (api.NORM_ZSCORE / api.NORM_MEDMAD) -> (y, records).  y: a float32 tensor of x's layout --
+        x itself normalises in place, None allocates one (zeros outside the reads); nothing of it outside the reads is
+        written.  records: a uint8 tensor holding n_reads sgk_norm_rec_t (view it with api.NORM_DTYPE)."""
+        L = api._float_lib()
+        if y is None:
+            y = torch.zeros_like(self.x)
+        rec = torch.zeros(max(self.n_reads, 1) * api.NORM_DTYPE.itemsize, dtype=torch.uint8, device=self.x.device)
+        if ws is None:
+            ws = _float_workspace(self, "sgk_normalise_f32_workspace_bytes")
+        api.check(L.sgk_normalise_f32(*self.view(), int(method), _ptr(y), _ptr(rec), _ptr(ws), ws.numel(), _stream_ptr()),
+                  "sgk_normalise_f32")
+        return y, rec
 
 
 def float_reads(x: torch.Tensor, offsets, lengths) -> FloatReads:

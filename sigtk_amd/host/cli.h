@@ -25,7 +25,7 @@
 enum {
     OPT_PRINT_STAT = 256, OPT_GPUS, OPT_BATCH_SAMPLES, OPT_HOST_DECODE, OPT_HOST_INFLATE, OPT_GPU_TEXT, OPT_AUX_SLACK,
     OPT_DETECTOR, OPT_SEGMENTER, OPT_ADAPTOR, OPT_POLYA,   /* (these four in this order: cmain's list_option) */
-    OPT_GPU_DEFLATE, OPT_GPU_INFLATE, OPT_RNA, OPT_KMER_MODEL, OPT_BATCH
+    OPT_GPU_DEFLATE, OPT_GPU_INFLATE, OPT_RNA, OPT_KMER_MODEL, OPT_BATCH, OPT_NORMALISE
 };
 
 /* Fatal errors can be raised on the reader, loader and writer threads while other threads still have HIP work in

@@ -2,7 +2,7 @@
  *   cmain    pa / event / stat / jnn / prefix / ent (src/cmain.c:40-156, src/ent.c:63-105)
  *   qtsmain  qts (src/qts.c:46-165)
  * Options beyond the reference's: --gpus N, --batch-samples M, -t/--threads T, --host-decode, --host-inflate, --gpu-text,
- * event --detector, jnn --segmenter, prefix --adaptor / --polya; qts --gpu-deflate, --gpu-inflate. */
+ * event --detector, jnn --segmenter, prefix --adaptor / --polya, pa --normalise; qts --gpu-deflate, --gpu-inflate. */
 #include <ctype.h>
 #include <errno.h>
 #include <float.h>
@@ -163,6 +163,7 @@ typedef struct {
     int hdr, host_decode, host_inflate, gpu_text;
     int verbosity;   /* -v / --verbose: 4 and up names the routes the given parameters take */
     int have_det, have_seg, have_ad, have_pl;
+    int normalise;   /* pa --normalise: SGK_NORM_* */
     sgk_event_params_t det;                /* event --detector */
     double seg_v[8], ad_v[5], pl_v[7];     /* jnn --segmenter, prefix --adaptor, prefix --polya */
 } copts_t;
@@ -174,7 +175,7 @@ static struct option long_options[] = {
     {"threads", required_argument, 0, 't'}, {"host-decode", no_argument, 0, OPT_HOST_DECODE}, {"host-inflate", no_argument, 0, OPT_HOST_INFLATE},
     {"gpu-text", no_argument, 0, OPT_GPU_TEXT}, {"aux-slack", required_argument, 0, OPT_AUX_SLACK}, {"detector", required_argument, 0, OPT_DETECTOR},
     {"segmenter", required_argument, 0, OPT_SEGMENTER}, {"adaptor", required_argument, 0, OPT_ADAPTOR}, {"polya", required_argument, 0, OPT_POLYA},
-    {0, 0, 0, 0}};
+    {"normalise", required_argument, 0, OPT_NORMALISE}, {0, 0, 0, 0}};
 
 /* event --detector W1,W2,THR1,THR2,PEAK_HEIGHT: exactly five fields, none empty, nothing behind a number, windows as
  * decimal integers; the domain is the library's (sgk_event_params_check, a host-only call).  Returns 0, or -1 with *why
@@ -240,6 +241,20 @@ static void list_option(int c, const tool_t *tool, copts_t *o) {
     if (k == 0) o->have_det = 1; else if (k == 1) o->have_seg = 1; else if (k == 2) o->have_ad = 1; else o->have_pl = 1;
 }
 
+/* pa --normalise zscore|medmad */
+static void normalise_option(const tool_t *tool, copts_t *o) {
+    if (tool->mode != MODE_PA) {
+        ERROR("cmain", "%s", "--normalise is an option of the pa subtool");
+        exit(EXIT_FAILURE);
+    }
+    if (strcmp(optarg, "zscore") == 0) o->normalise = SGK_NORM_ZSCORE;
+    else if (strcmp(optarg, "medmad") == 0) o->normalise = SGK_NORM_MEDMAD;
+    else {
+        ERROR("cmain", "--normalise wants zscore or medmad; '%s' is neither", optarg);
+        exit(EXIT_FAILURE);
+    }
+}
+
 static void cmain_parse(int argc, char *argv[], const tool_t *tool, copts_t *o) {
     /* `ent` has its own front end in the reference (src/ent.c:63-105): only -h/-V (and --no-header) are options,
      * exactly one file argument, no DNA/RNA or pore detection */
@@ -264,8 +279,13 @@ static void cmain_parse(int argc, char *argv[], const tool_t *tool, copts_t *o) 
             case OPT_HOST_INFLATE: o->host_inflate = 1; break;
             case OPT_GPU_TEXT: o->gpu_text = 1; break;
             case OPT_DETECTOR: case OPT_SEGMENTER: case OPT_ADAPTOR: case OPT_POLYA: list_option(c, tool, o); break;
+            case OPT_NORMALISE: normalise_option(tool, o); break;
             default: break;   /* -o, and what getopt has already complained about: ignored, as in the reference */
         }
+    }
+    if (o->normalise && o->gpu_text) {   /* the device formatter writes pA rows from the int16 samples */
+        ERROR("cmain", "%s", "--normalise cannot be combined with --gpu-text");
+        exit(EXIT_FAILURE);
     }
 }
 
@@ -362,6 +382,10 @@ static void cmain_usage(FILE *fp, const tool_t *tool) {
     fprintf(fp, "   --host-inflate             decompress zlib / zstd records on the host threads instead of the GPU\n");
     fprintf(fp, "   --gpu-text                 pa / event, whole-file mode: format the rows on the GPU and fetch them as text\n");
     fprintf(fp, "   --aux-slack INT            test option\n");
+    if (tool->mode == MODE_PA) {
+        fprintf(fp, "   --normalise zscore|medmad  print the normalised signal, (pA - shift) / scale in float, in place of pA:\n");
+        fprintf(fp, "                              zscore: mean and standard deviation; medmad: median and 1.4826 * MAD\n");
+    }
     if (tool->mode == MODE_JNN) {
         fprintf(fp, "   --segmenter STD_SCALE,CORRECTOR,SEG_DIST,WINDOW,STALL_LEN,ERROR[,TOP,BOT]\n");
         fprintf(fp, "                              the segmenter's parameters in place of the presets (WINDOW 32 .. 16777216;\n");
@@ -397,7 +421,8 @@ int cmain(int argc, char *argv[], const tool_t *tool, cli_times_t *times) {
         o.opt.rna = drna_detect(f);
         o.opt.pore = pore_detect(f);
     }
-    if (o.hdr) fputs((tool->mode == MODE_EVENT && o.opt.compact) || (tool->mode == MODE_PREFIX && o.opt.p_stat) ? tool->header_alt : tool->header, stdout);
+    if (o.hdr) fputs((tool->mode == MODE_EVENT && o.opt.compact) || (tool->mode == MODE_PREFIX && o.opt.p_stat) ||
+                   (tool->mode == MODE_PA && o.normalise) ? tool->header_alt : tool->header, stdout);
     const double t_init = devices_and_threads(&o.run, "cmain", 1);
 
     pipe_t P;
@@ -419,6 +444,7 @@ int cmain(int argc, char *argv[], const tool_t *tool, cli_times_t *times) {
     /* rows as text from the GPU: the three large-output grammars, when the whole file is read in order (with read ids
      * on the command line, and for the other subtools, the option changes nothing) */
     P.gpu_text = o.gpu_text && (tool->mode == MODE_PA || tool->mode == MODE_EVENT) && P.n_ids == 0;
+    P.normalise = o.normalise;
     run_params(&P, &o, &seg_p, &pre_p);
     run_pipeline(&P, t_init);
     fflush(stdout);

@@ -340,7 +340,8 @@ static void *writer_main(void *arg) {
     return NULL;
 }
 
-/* a new job takes the command line's parameters: event --detector, jnn --segmenter, prefix --adaptor / --polya */
+/* a new job takes the command line's parameters: event --detector, jnn --segmenter, prefix --adaptor / --polya,
+ * pa --normalise */
 static void job_create(const pipe_t *P, int k, batch_t *b) {
     int rc = sgk_job_create(k % P->n_gpus, &b->job);
     if (rc != SGK_OK) gpu_fail(NULL, "sgk_job_create", rc);
@@ -348,6 +349,7 @@ static void job_create(const pipe_t *P, int k, batch_t *b) {
     if (P->jnn_params && (rc = sgk_job_set_jnn_params(b->job, P->jnn_params)) != SGK_OK) gpu_fail(NULL, "sgk_job_set_jnn_params", rc);
     if (P->prefix_params && (rc = sgk_job_set_prefix_params(b->job, P->prefix_params)) != SGK_OK)
         gpu_fail(NULL, "sgk_job_set_prefix_params", rc);
+    if (P->normalise && (rc = sgk_job_set_normalise(b->job, P->normalise)) != SGK_OK) gpu_fail(NULL, "sgk_job_set_normalise", rc);
 }
 
 /* ------------------------------------------------------------------ reader thread

@@ -87,6 +87,7 @@ typedef struct pipe {
     const sgk_event_params_t *ev_params; /* event --detector: every job's detector parameters (NULL: the presets) */
     const sgk_jnn_param_t *jnn_params;       /* jnn --segmenter (NULL: the presets) */
     const sgk_prefix_params_t *prefix_params; /* prefix --adaptor / --polya (NULL: the presets) */
+    int normalise;       /* pa --normalise: SGK_NORM_* (0: pA) */
     uint64_t text_bytes; /* ... their bytes over PCIe */
     int zrec;            /* records go to the GPU as they sit in the file (zlib / zstd records, svb-zd or uncompressed signal, auxiliary columns of known types) */
     sgk_aux_field_t *aux_tab; /* ... those columns, in header order */

@@ -244,7 +244,7 @@ static const tool_t tools[] = {
     {"prefix", MODE_PREFIX, SGK_TOOL_PREFIX, row_prefix, 64ull << 20, "read_id\tlen_raw_signal\tadapt_start\tadapt_end\tpolya_start\tpolya_end\n",
      "read_id\tlen_raw_signal\tadapt_start\tadapt_end\tpolya_start\tpolya_end\tadapt_mean\tadapt_std\tadapt_median\tpolya_mean\tpolya_std\tpolya_median\n"},
     {"jnn", MODE_JNN, SGK_TOOL_JNN, row_jnn, 64ull << 20, "read_id\tlen_raw_signal\tnum_seg\tseg\n", NULL},
-    {"pa", MODE_PA, SGK_TOOL_PA, row_pa, 16ull << 20, "read_id\tlen_raw_signal\tpa\n", NULL},
+    {"pa", MODE_PA, SGK_TOOL_PA, row_pa, 16ull << 20, "read_id\tlen_raw_signal\tpa\n", "read_id\tlen_raw_signal\tnorm\n"},
     {"ent", MODE_ENT, SGK_TOOL_ENT, row_ent, 16ull << 20, "read_id\traw_ent\tdelta_ent\tbyte_ent\n", NULL},
     {"qts", MODE_QTS, -1, row_qts, 16ull << 20, NULL, NULL},
 };
