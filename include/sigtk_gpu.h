@@ -1257,6 +1257,55 @@ int sgk_normalise(const sgk_batch_t *batch, int method, float *y, sgk_norm_rec_t
  * from sgk_normalise / sgk_normalise_f32 alone. */
 int sgk_job_set_normalise(sgk_job_t *job, int method);
 
+/* ---- subsequence DTW of float query batches against float target batches (additive to 0.2.3) --------------------------
+ * What the rows of sgk_sref_levels are for: every query (a read's normalised event means, say) is aligned whole against
+ * every target (a strand's normalised levels), with a free start and a free end in the target.  No reference function
+ * defines this; the definition is the library's, and the results are bit for bit what it gives (tools/proto/
+ * sdtw_proto.py is its numpy model).  Query q[0..m), target t[0..n), every operation float32 with one rounding per
+ * operation and no contraction:
+ *   c(i,j) = fabsf(q[i] - t[j])
+ *   D(0,j) = c(0,j)                   S(0,j) = j
+ *   D(i,0) = D(i-1,0) + c(i,0)        S(i,0) = S(i-1,0)          (= 0)
+ *   D(i,j) = c(i,j) + best            S(i,j) = S(best's cell)
+ *            best = D(i-1,j-1);  if (D(i-1,j) < best) best = D(i-1,j);  if (D(i,j-1) < best) best = D(i,j-1);
+ *   score = min_j D(m-1,j);  end = the smallest j with that value;  start = S(m-1,end)
+ * On a tie the diagonal wins over "up" and both win over "left": the order of the two strict compares is part of the
+ * contract.  The query's values q[0 .. m) lie along target values t[start .. end], both inclusive.  score is not divided
+ * by anything.  Sums of finite values that overflow give what IEEE gives (inf < inf is false: the earlier candidate
+ * stays).  A pair whose query or target holds a NaN or an infinity: score NaN, end = start = -1, SGK_SDTW_NONFINITE (a
+ * sweep over the reads decides this first; the recurrence never sees such a value).  A pair with m == 0 or n == 0: the
+ * same outputs and SGK_SDTW_EMPTY (both bits where both hold).  With SGK_SDTW_NO_START in `options` start is -1
+ * everywhere, score, end and flags are unchanged, and the call is faster.
+ * The call is all against all, out[qi * n_targets + ti]; targets are few (the two strands of each contig).  Both batches
+ * are float batches under the contract above: q and t are 4-byte aligned, offsets are any element index, reads may touch
+ * but not overlap, no byte outside the reads is read, nothing but `out` and the workspace is written; the call is
+ * asynchronous on `stream`, allocates nothing and makes no host round trip.  n_queries == 0 or n_targets == 0 is SGK_OK
+ * with nothing written.  Unknown option bits, a null pointer with a non-zero count, max_query_len or max_target_len >=
+ * 2^31 are SGK_ERR_ARG; the workspace is 16-byte aligned, and one smaller than sgk_sdtw_f32_workspace_bytes is
+ * SGK_ERR_WORKSPACE with nothing written; SGK_ERR_NODEVICE comes after the argument checks.  lengths[r] <= max_*_len is
+ * the caller's word, as in every float batch (the lengths are device memory and the call makes no round trip, so the host
+ * cannot answer SGK_ERR_ARG); here the device checks it, since the band rows below are sized by max_target_len: every
+ * pair of a read longer than its max gets score NaN, end = start = -1 and SGK_SDTW_TOO_LONG, and the read is not looked at.
+ * One wavefront per pair, the pairs of the longest queries first; a pair is never split over wavefronts or workgroups: a
+ * target of 10^8 values is slow and right.  A query of up to 1 024 values lives in the wavefront's registers and needs no
+ * workspace beyond a flag word per read and the dispatch order; a longer one runs in passes of 1 024 rows and keeps one
+ * row of D and S per pass in one of a fixed number of slots (at most 2 048, fewer above 1 GB, never less than one) that
+ * the wavefronts in flight take: the workspace does not grow with n_queries x max_target_len.  DESIGN.md 3.20. */
+#define SGK_SDTW_NO_START 1u  /* options: start is -1 everywhere, score and end unchanged */
+#define SGK_SDTW_EMPTY 1u     /* sgk_sdtw_rec_t::flags: m == 0 or n == 0 */
+#define SGK_SDTW_NONFINITE 2u /* ... the query or the target holds a NaN or an infinity */
+#define SGK_SDTW_TOO_LONG 4u  /* ... the query or the target is longer than its batch's max_*_len */
+typedef struct sgk_sdtw_rec {
+    float score;
+    int32_t end, start;
+    uint32_t flags;
+} sgk_sdtw_rec_t; /* 16 bytes */
+size_t sgk_sdtw_f32_workspace_bytes(uint32_t n_queries, uint32_t max_query_len, uint32_t n_targets, uint32_t max_target_len);
+int sgk_sdtw_f32(const float *q, const uint64_t *q_offsets, const uint32_t *q_lengths, uint32_t n_queries,
+                 uint32_t max_query_len, uint64_t n_q_values, const float *t, const uint64_t *t_offsets,
+                 const uint32_t *t_lengths, uint32_t n_targets, uint32_t max_target_len, uint64_t n_t_values, uint32_t options,
+                 sgk_sdtw_rec_t *out /* n_queries * n_targets records */, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

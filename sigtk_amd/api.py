@@ -363,6 +363,8 @@ ABI_SYMBOLS = [
     # normalised signals (csrc/normf_kernels.hip)
     "sgk_normalise_f32_workspace_bytes", "sgk_normalise_f32", "sgk_normalise_workspace_bytes", "sgk_normalise",
     "sgk_job_set_normalise",
+    # subsequence DTW of float queries against float targets (csrc/sdtw_kernels.hip)
+    "sgk_sdtw_f32_workspace_bytes", "sgk_sdtw_f32",
     "sgk_meanf", "sgk_meani16", "sgk_stdvf", "sgk_stdvi16", "sgk_medianf", "sgk_mediani16", "sgk_shim_status",
 ]
 
@@ -806,6 +808,16 @@ NORM_METHODS = {"zscore": NORM_ZSCORE, "medmad": NORM_MEDMAD}
 NORM_ZERO_SCALE, NORM_NONFINITE = 1, 2
 
 
+class SdtwRec(C.Structure):   # sgk_sdtw_rec_t
+    _fields_ = [("score", C.c_float), ("end", C.c_int32), ("start", C.c_int32), ("flags", C.c_uint32)]
+
+
+# sgk_sdtw_rec_t; the option of sgk_sdtw_f32 and the flags of a record
+SDTW_DTYPE = np.dtype([("score", "<f4"), ("end", "<i4"), ("start", "<i4"), ("flags", "<u4")])
+SDTW_NO_START = 1
+SDTW_EMPTY, SDTW_NONFINITE, SDTW_TOO_LONG = 1, 2, 4
+
+
 def _float_lib():
     L = load_library()
     if not getattr(L, "_float_batch_bound", False):
@@ -824,6 +836,10 @@ def _float_lib():
         L.sgk_normalise.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.sgk_job_set_normalise.restype = C.c_int
         L.sgk_job_set_normalise.argtypes = [C.c_void_p, C.c_int]
+        L.sgk_sdtw_f32_workspace_bytes.restype = C.c_size_t
+        L.sgk_sdtw_f32_workspace_bytes.argtypes = [C.c_uint32] * 4
+        L.sgk_sdtw_f32.restype = C.c_int
+        L.sgk_sdtw_f32.argtypes = batch + batch + [C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L._float_batch_bound = True
     return L
 

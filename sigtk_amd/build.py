@@ -22,7 +22,7 @@ CLI = os.path.join(PKG, "sigtk-amd")
 CLI_ASAN = os.path.join(PKG, "sigtk-amd-asan")
 
 EVENT_SOURCES = ["event_plan.hip", "event_launch.hip","event_whole.hip", "event_seg.hip", "event_multi.hip", "event_fallback.hip", "event_param.hip"]
-HIP_SOURCES = ["api.hip", "api_stat.hip", *EVENT_SOURCES, "stat_launch.hip", "stat_lane.hip", "stat_wave.hip", "stat_long.hip", "stat_literal.hip", "stat_param.hip", "statf_kernels.hip", "normf_kernels.hip", "jnnf_kernels.hip",
+HIP_SOURCES = ["api.hip", "api_stat.hip", *EVENT_SOURCES, "stat_launch.hip", "stat_lane.hip", "stat_wave.hip", "stat_long.hip", "stat_literal.hip", "stat_param.hip", "statf_kernels.hip", "normf_kernels.hip", "jnnf_kernels.hip", "sdtw_kernels.hip",
                "misc_kernels.hip", "svb_kernels.hip", "sigtext_kernels.hip", "inflate_kernels.hip", "deflate_kernels.hip", "zstd_kernels.hip", "zrec_kernels.hip", "sigraw_kernels.hip", "ent_kernels.hip",
                "qts_kernels.hip", "text_kernels.hip", "slow5_text_kernels.hip", "sref_kernels.hip", "ss_kernels.hip", "text_pipes.hip", "job.hip", "job_submit.hip", "job_qts.hip", "job_kernels.hip", "shims.hip"]
 # Per-source flags.  The SLP vectoriser pairs the detector's f32 arithmetic into v_pk_*_f32, which issue at the cost of
@@ -153,7 +153,8 @@ def build_cli_asan(force: bool = False, verbose: bool = False) -> str:
 def build_tools(force: bool = False, verbose: bool = False) -> None:
     """the stand-alone programs of tools/: HIP (issue-rate microbenchmark, hardware accuracy check of v_rsq_f32, the
     certified square root on the GPU: with the library's numerics flags) and host (sqrt_check: the same form against sqrtf;
-    long_cold_check: the long detector's bound formed from the f32 sums of the window's halves)"""
+    long_cold_check: the long detector's bound formed from the f32 sums of the window's halves; sdtw_c: the definition of
+    sgk_sdtw_f32 in plain C)"""
     tdir = os.path.join(ROOT, "tools")
     math_h = os.path.join(CSRC, "tstat_math.h")
     numerics = ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]
@@ -175,6 +176,13 @@ def build_tools(force: bool = False, verbose: bool = False) -> None:
             if verbose:
                 print(" ".join(cmd), file=sys.stderr)
             subprocess.check_call(cmd)
+    # the definition of sgk_sdtw_f32 in plain C, one thread: context for tools/bench_sdtw.py, not product code
+    src, exe = os.path.join(tdir, "sdtw_c.c"), os.path.join(tdir, "sdtw_c")
+    if os.path.exists(src) and (force or not _newer(exe, [src])):
+        cmd = ["gcc", "-O2", "-std=c99", "-D_GNU_SOURCE", "-ffp-contract=off", "-o", exe, src, "-lm"]
+        if verbose:
+            print(" ".join(cmd), file=sys.stderr)
+        subprocess.check_call(cmd)
 
 
 if __name__ == "__main__":

@@ -337,7 +337,7 @@ def jnn(b: DeviceReads, arena: SegArena, rna: int, params: "api.JnnParam" = None
               "sgk_jnn_opt")
 
 
-# ------------------------------------------------------- float (pA) batches: sgk_stat_f32, sgk_jnn_f32, sgk_normalise_f32
+# ---------------------------------------- float (pA) batches: sgk_stat_f32, sgk_jnn_f32, sgk_normalise_f32, sgk_sdtw_f32
 @dataclass
 class FloatReads:
     """A batch of float signals resident in HBM: read r is x[offsets[r] : offsets[r] + lengths[r]], at any element
@@ -412,6 +412,26 @@ def stat_f32(fb: FloatReads, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
     if ws is None:
         ws = _float_workspace(fb, "sgk_stat_f32_workspace_bytes")
     api.check(L.sgk_stat_f32(*fb.view(), _ptr(out), _ptr(ws), ws.numel(), _stream_ptr()), "sgk_stat_f32")
+    return out
+
+
+def sdtw_workspace(queries: FloatReads, targets: FloatReads) -> torch.Tensor:
+    n = int(api._float_lib().sgk_sdtw_f32_workspace_bytes(queries.n_reads, queries.max_read_len, targets.n_reads,
+                                                          targets.max_read_len))
+    return torch.zeros(max(n, 64), dtype=torch.uint8, device=queries.x.device)
+
+
+def sdtw_f32(queries: FloatReads, targets: FloatReads, options: int = 0, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sgk_sdtw_f32: every query aligned against every target (subsequence DTW; api.SDTW_NO_START drops `start`) ->
+    uint8 tensor holding n_queries x n_targets sgk_sdtw_rec_t, record [qi * n_targets + ti] (view it with
+    api.SDTW_DTYPE)."""
+    L = api._float_lib()
+    out = torch.zeros(max(queries.n_reads * targets.n_reads, 1) * api.SDTW_DTYPE.itemsize, dtype=torch.uint8,
+                      device=queries.x.device)
+    if ws is None:
+        ws = sdtw_workspace(queries, targets)
+    api.check(L.sgk_sdtw_f32(*queries.view(), *targets.view(), int(options), _ptr(out), _ptr(ws), ws.numel(), _stream_ptr()),
+              "sgk_sdtw_f32")
     return out
 
 
